@@ -2,15 +2,27 @@
 """Headline benchmark: train images/s (640x640 synthetic images + 16-token captions, batch 8 per GPU)
 for the MI355X-native TOIST/MDETR hot path (BASELINE.json: metric / configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 One step = zero_grad -> encode -> decode -> SetCriterion (labels, boxes, cardinality, 5 aux layers) ->
 backward (+ flat-buffer RCCL gradient all-reduce when N > 1) -> clip_grad_norm_(0.1) -> AdamW -> EMA,
-in train mode (dropout 0.1 on).  Rank 0 prints ONE JSON line.  `roofline` times the dominant kernel
-(the bf16 MFMA implicit-GEMM family, toist_amd/csrc/gemm.hip) with HIP events on the launch stream
-inside the timed region; `cpu_baseline` times the fp32 oracle (a port of the reference's CPU path) on
-this box's host cores at N = 1.
+in train mode (dropout 0.1 on).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps once and prints the line.  Everything else is measured
+only with --full: the K-step region repeated (--repeats, `value` = the median region), `roofline` (the
+GEMM kernel families timed launch by launch, toist_amd/csrc/gemm.hip, plus rocprofv3 passes of their
+own), `cpu_baseline` (the fp32 oracle, a port of the reference's CPU path, on the host cores at N = 1)
+with the matcher index bit-match, the `secondary` configurations, and at N > 1 the parameter identity
+across ranks and the per-segment collectives.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32):
+the loss, the predictions of every decoder layer and a fixed, seeded sample of the updated parameters.
+With the same arguments the inputs are the same in every run, and so are the default (configs[1]) step's dumped
+predictions and parameters (the loss to its last bits): three gradient reductions of that step that added with float atomics in completion order
+(split-K bias column sums, the text embedding tables, the contrastive token gradient) now fold in a fixed order
+(tests/test_gpu_determinism.py).  Float atomics remain elsewhere, e.g. the per-term loss sums (no gradient
+reads them) and the mask head of --masks, so those paths are not claimed to repeat bit for bit.
 """
 import argparse
 import json
@@ -53,7 +65,12 @@ def parse():
     ap.add_argument("--mixed-sizes", action="store_true", help="configs[1] on a stream of batches of three padded image sizes (640x640, 576x704, 512x768) through "
                     "toist_amd.harness.CapturedTrainStep: one cached hipGraph per shape bucket, the library's replayed step with variable-size inputs")
     ap.add_argument("--no-secondary", action="store_true", help="do not run the short configs[2] / configs[2]-frozen / configs[4] legs (child processes) that the default N = 1 run appends as `secondary`")
-    ap.add_argument("--repeats", type=int, default=3, help="hipGraph replay: the K-step timed region is run this many times (value = the MEDIAN region; first / min reported beside it)")
+    ap.add_argument("--repeats", type=int, default=None, help="hipGraph replay: the K-step timed region is run this many times (value = the MEDIAN region; first / min reported "
+                    "beside it); default 3 with --full, else 1")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: repeated timed regions, roofline (with "
+                    "rocprofv3 passes), cpu_baseline + matcher bit-match, the secondary configurations, at N > 1 parameter identity and collectives")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, "
+                    "large arrays as a fixed, seeded sample)")
     ap.add_argument("--allow-eager-fallback", action="store_true", help="N > 1: if hipGraph capture fails, run eager instead of aborting (a different launch protocol: labelled in config.launch)")
     ap.add_argument("--no-overlap", action="store_true", help="keep the text branch on the main stream (no parallel graph branch)")
     ap.add_argument("--torch-optimizer", action="store_true", help="diagnostic: torch clip_grad_norm_ + fused AdamW + foreach EMA instead of the HIP tail")
@@ -77,7 +94,42 @@ def parse():
                     "when each branch of the LAST replayed step started and ended, in microseconds from the step's first kernel, no profiler attached")
     ap.add_argument("--host-times", action="store_true", help="diagnostic: print (stderr) the host microseconds spent inside each run_step() call of the first timed region")
     ap.add_argument("--split-graph", action="store_true", help="force the multi-GPU structure (graph: fwd+bwd | eager all-reduce | graph: clip+AdamW+EMA) on one GPU")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 3 if a.full else 1
+    if not a.full:      # a plain run does only what the headline figure needs (--profile-all asks for its launch-by-launch timing explicitly)
+        a.no_cpu_baseline = a.no_secondary = a.no_pmc = True
+        a.no_roofline = a.no_roofline or not a.profile_all
+    return a
+
+
+SETTLE_REPLAYS = 30             # a plain run's minimum number of untimed replays before its one timed region
+DUMP_SAMPLE = 1 << 22           # --dump-outputs: an array of more elements is written as this many of them (seeded indices)
+DUMP_PARAMS_PER_TENSOR = 2048   # --dump-outputs: sampled elements of each trainable parameter
+
+
+def param_sample(params, seed=0):
+    """A fixed, seeded sample of the parameters, the same indices in every run: up to DUMP_PARAMS_PER_TENSOR elements of each tensor, in order."""
+    g = torch.Generator().manual_seed(seed)
+    parts = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        idx = torch.randint(0, flat.numel(), (min(DUMP_PARAMS_PER_TENSOR, flat.numel()),), generator=g)
+        parts.append(flat[idx.to(flat.device)].float())
+    return torch.cat(parts)
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: every tensor of `arrays` as path/<name>.npy in float32; one of more than DUMP_SAMPLE elements becomes a fixed, seeded
+    sample of DUMP_SAMPLE of them (flattened)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            t = t.reshape(-1)[torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline_worker(size, threads, check_path=None):
@@ -157,7 +209,7 @@ def secondary_legs():
     out = {}
     for name, flags in legs:
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-roofline", "--no-secondary", "--repeats", "1", "--steps", "10",
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-roofline", "--no-secondary", "--repeats", "1", "--steps", "10",
                                 "--warmup", "3"] + flags, capture_output=True, text=True, timeout=420)
             line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1]
             d = json.loads(line)
@@ -229,7 +281,7 @@ def kernel_stats_live(families, steps, warmup, timeout=300, keep=None):
     tmp = tempfile.mkdtemp(prefix="toist_kt_", dir="/tmp")
     try:
         cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
-               "--no-cpu-baseline", "--no-roofline", "--no-secondary", "--steps", str(steps), "--warmup", str(warmup)]
+               "--full", "--no-cpu-baseline", "--no-roofline", "--no-secondary", "--steps", str(steps), "--warmup", str(warmup)]
         subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, timeout=timeout)
         path = os.path.join(tmp, "p_kernel_stats.csv")
         acc = {fam: [0.0, 0] for fam in families}
@@ -325,6 +377,7 @@ def bench_distillation(a, dev, rank, world):
     dt, last = timed(step)             # eager: what a loop over NEW batches gets today (the caption-driven tables of a batch are built on the host)
     launch, eager_rate, graph_rate = "eager", round(a.batch * world * a.steps / dt, 3), None
     final_loss = round(float(last.detach()), 4)
+    last_loss = last.detach()
     del last
     any_rate = None
     if world == 1 and not a.no_graph:
@@ -358,10 +411,13 @@ def bench_distillation(a, dev, rank, world):
             any_rate = graph_rate = round(a.batch * world * a.steps / dt_g, 3)
             launch = ("hipGraph replay, every step a different batch (harness.CapturedDistillStep: 1 graph, %d replays; 4 resident batches with different images, captions, "
                       "0..10 targets per image and tasks); eager list-of-dicts step: %.1f pairs/s" % (cap.replays, eager_rate))
-            dt, final_loss = dt_g, round(float(last_g.detach()), 4)
+            dt, final_loss, last_loss = dt_g, round(float(last_g.detach()), 4), last_g.detach()
         except Exception as e:      # stays on the eager number, loudly
             print(f"[bench] distillation: hipGraph capture failed ({type(e).__name__}: {e}); reporting the eager step", file=sys.stderr)
             torch.cuda.synchronize()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"loss": last_loss.reshape(1), "params_sample": param_sample(p for p in model.parameters() if p.requires_grad),
+                                      "noun_params_sample": param_sample(p for p in model_noun.parameters() if p.requires_grad)})
     if rank == 0:
         print(json.dumps({"metric": "train images/sec/node (640x640) + matcher index bit-match", "value": round(a.batch * world * a.steps / dt, 3), "unit": "images/s (pairs)",
                           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1000 * dt / a.steps, 3), "higher_is_better": True,
@@ -413,6 +469,8 @@ def bench_mixed_sizes(a, dev):
         last = cap.step(s_i, tok_i, packed=packed)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"loss": last.detach().reshape(1), "params_sample": param_sample(p for _, p in named)})
     print(json.dumps({"metric": "train images/sec/node (640x640, bs=8/GPU) + matcher index bit-match", "value": round(a.batch * a.steps / dt, 3), "unit": "images/s", "n_gpus": 1,
                       "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1000 * dt / a.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                       "dtype": "bf16", "data": "synthetic",
@@ -556,6 +614,9 @@ def main():
         if ema_stream is not None:
             torch.cuda.current_stream().wait_stream(ema_stream)     # joined before the optimizer rewrites the parameters
         cut_state["mc"] = mc
+        if a.dump_outputs:      # the step's predictions (static tensors of the captured graph): read after the timed steps
+            cut_state["pred"] = {"pred_logits": out["_stacked"]["pred_logits"], "pred_boxes": out["_stacked"]["pred_boxes"],
+                                 **({"pred_masks": out["pred_masks"]} if "pred_masks" in out else {})}
         return total
 
     def bwd_cut(name):
@@ -745,9 +806,14 @@ def main():
                 main.wait_stream(text_stream)
                 graph_b.replay()
                 return static_loss
-        for _ in range(max(a.warmup, 1)):      # W untimed steps on the path that is timed (the eager steps above only prepared the capture)
+        # W untimed steps on the path that is timed (the eager steps above only prepared the capture).  A plain run times ONE region, and the
+        # first region after a short warm-up runs 1-3 % slower than the ones after it (`repeats.first` of --full, whose `value` is the median
+        # region): it replays at least SETTLE_REPLAYS steps first, a fixed count, so every rank runs the same steps and the outputs repeat
+        warm_run = {"eager_steps": max(a.warmup, 2), "replayed_steps": max(a.warmup, 1 if a.full else SETTLE_REPLAYS)}
+        for _ in range(warm_run["replayed_steps"]):
             run_step()
     else:
+        warm_run = {"eager_steps": a.warmup}
         for _ in range(a.warmup):
             step()
         run_step = step
@@ -790,6 +856,8 @@ def main():
             dt = sorted(region_ms)[len(region_ms) // 2] * a.steps / 1000.0
     if not a.torch_optimizer:
         opt.finish()        # the late group's update of the last replay (outside the timed regions: every timed step applied one update per group)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"loss": last.reshape(1), **cut_state["pred"], "params_sample": param_sample(p for _, p in named)})
     if not a.no_roofline and use_graph:
         # kernel-level timing needs per-launch HIP events, which a replayed graph cannot carry: time the
         # same K steps once more, eagerly, on the same stream right after the timed region (every rank runs
@@ -806,7 +874,7 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
     params_identical, params_differing = None, []
-    if world > 1:
+    if world > 1 and a.full:
         # after the timed steps every rank must hold the same parameters (same broadcast start, averaged gradients, same optimizer tail)
         with torch.no_grad():
             digest = torch.stack([p.detach().double().sum() for _, p in named]).to(dev)
@@ -816,7 +884,7 @@ def main():
             params_identical = bool(torch.equal(lo, hi))
             params_differing = [named[i][0] for i in (lo != hi).nonzero().flatten().tolist()]
     collectives = None
-    if world > 1 and use_graph and split_graph and flats:
+    if world > 1 and a.full and use_graph and split_graph and flats:
         # the three gradient collectives of the step, each alone on the machine: what the RCCL ring achieves per xGMI link
         collectives = {name: parallel.measure_all_reduce(fl, bf16=a.bf16_grads) for name, fl in
                        [("transformer+heads", flats[:n_head]), ("text_encoder", flats[n_head:n_text])] +
@@ -833,6 +901,7 @@ def main():
                                    "16-token captions, detection loss (labels+boxes+cardinality" + ("+contrastive_align" if contrastive else "") + (", no aux layers" if a.frozen else ", 5 aux layers") + "), dropout 0.1, "
                                    "clip 0.1 + AdamW + EMA" + (" (torch)" if a.torch_optimizer else " (fused HIP tail)") + "; random-init weights; " +
                                    ("every step a different batch (4 resident batches, 0..10 targets per image) through fixed-address inputs" if dynamic else "one fixed batch"),
+                       "untimed_steps_run": warm_run,     # `warmup` is the argument; these ran before the timed steps (a plain replayed run: >= SETTLE_REPLAYS)
                        "global_batch": a.batch * world, "parallelism": f"dp{world}", "final_loss": round(loss_val, 4), "launch": ("%d hipGraphs (head | text || backbone layer4 | layer3 | layer2 | tail), gradient all-reduces under the backbone backward" % (3 + len(bb_graphs)) if split_graph else "hipGraph replay") if use_graph else "eager",
                        **({"mask_logit_parity": "STATED DEVIATION from SURVEY 8(d) (atol 5e-2, rtol 5e-2): pred_masks of all 800 maps at 640x640 against the fp32 oracle are within "
                                                 "1e-1 + 5e-2*|ref| element-wise (measured max abs error 0.113 on logits of magnitude <= 2.5, worst excess over 5e-2*|ref| 0.097, relative "
@@ -849,7 +918,7 @@ def main():
                               "images_per_s_median": round(a.batch * world / (srt[len(srt) // 2] * 1e-3), 1),
                               "first": round(region_ms[0], 3),
                               "note": "the K-step timed region (barrier + synchronize on both sides) run %d times back to back; `value` / `ms_per_step` are the MEDIAN region, `first` is the first" % len(region_ms)}
-        if world > 1:
+        if world > 1 and a.full:
             res["config"]["parameters_identical_across_ranks"] = params_identical
         if collectives is not None:
             res["collectives"] = collectives
@@ -889,7 +958,7 @@ def main():
                 timed = "HIP events around each launch, %d eager steps %s" % (a.steps, "after the graph-replayed timed region" if use_graph else "inside the timed region")
                 if fam in ktrace:          # per-launch flops / bytes from the eager pass's records, duration from the replayed step's kernel trace
                     ms = ktrace[fam][0] * 1e-3 * n
-                    timed = ("rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline --no-roofline --no-secondary --steps %d --warmup %d` (hipGraph replay): "
+                    timed = ("rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu-baseline --no-roofline --no-secondary --steps %d --warmup %d` (hipGraph replay): "
                              "family TotalDurationNs / Calls over %d dispatches; algorithmic flops / bytes per launch from the eager pass" % (a.steps, a.warmup, ktrace[fam][1]))
                 fam_ms[fam] = ms / a.steps
                 tfl, gbs = fl / (ms * 1e-3) / 1e12, nb / (ms * 1e-3) / 1e9

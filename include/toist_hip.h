@@ -164,7 +164,8 @@ typedef struct toist_gemm {
                                    ds_read_b64_tr_b16 (validation fallback) */
     toist_epilogue epi;
     float* workspace;           /* split_k > 1: f32 scratch of >= split_k * M * N elements (caller-owned) */
-    float* a_colsum;            /* optional, A_KROW only: a_colsum[m] += sum_k A[m][k]  (f32 atomics) --
+    float* a_colsum;            /* optional, A_KROW only: a_colsum[m] += sum_k A[m][k]  (f32 atomics; with TOIST_GEMM_COLSUM_SLICES and
+                                   split_k > 1: a_colsum[slice * M + m] = that slice's sum, no atomics) --
                                    the bias gradient of nn.Linear falls out of the wgrad GEMM's A tiles */
     const toist_group* group;   /* optional (device memory, `batch` entries): grouped launch, see toist_group */
     const void* a2;             /* optional, A_ROWK only: output columns n >= a2_from read their A rows from a2 (same ld / batch
@@ -286,6 +287,12 @@ TOIST_API int toist_contrastive_bwd(const float* proj_queries, const float* proj
                           const int32_t* match_off, const int64_t* src_idx, const int64_t* tgt_idx, const float* num_boxes, int L,
                           int B, int Q, int T, int D, float temperature, const float* upstream, float* dproj_queries,
                           float* dproj_tokens, void* stream);
+/* the same backward with the token gradient summed over the L layers in layer order (no float atomics: the same sum in every run):
+ * workspace = [L][B][T][D] fp32 scratch */
+TOIST_API int toist_contrastive_bwd_ws(const float* proj_queries, const float* proj_tokens, const uint64_t* tok_mask, const int32_t* tgt_off,
+                          const int32_t* match_off, const int64_t* src_idx, const int64_t* tgt_idx, const float* num_boxes, int L,
+                          int B, int Q, int T, int D, float temperature, const float* upstream, float* dproj_queries,
+                          float* dproj_tokens, float* workspace, void* stream);
 TOIST_API int toist_l2norm_fwd(const float* x, int rows, int D, float* y, void* stream);
 TOIST_API int toist_l2norm_bwd(const float* x, const float* dy, int rows, int D, float* dx, void* stream);
 
@@ -643,6 +650,9 @@ TOIST_API int toist_lsap(const float* cost, const int64_t* offset, const int32_t
  * output type exactly as the un-split GEMM would -- for nn.Linear GEMMs with few output tiles and a deep reduction (128 tokens,
  * K = 3072: 24 tiles on 256 CUs).  batch = 1, no group, no row map; N %% 4 == 0. */
 #define TOIST_GEMM_SPLIT_EPILOGUE 4
+/* flags bit 15: with split_k > 1 and no group, a_colsum is a [split][M] fp32 buffer that receives each k-slice's column sums (plain stores,
+ * no atomics); the caller folds the slices in order (toist_splitk_reduce_batch with M = 1) -- a bias gradient that is the same in every run */
+#define TOIST_GEMM_COLSUM_SLICES 32768
 /* tile code the dispatcher would pick for this descriptor (`tile` = 0) */
 TOIST_API int toist_gemm_pick_tile(const toist_gemm* desc);
 typedef struct toist_reduce_desc {

@@ -130,7 +130,7 @@ def test_bench_ranks_on_one_gpu_gloo(dev, world, steps):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, TOIST_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-roofline"]
+           os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu-baseline", "--no-roofline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and lines, out.stderr[-3000:]

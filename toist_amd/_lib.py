@@ -123,6 +123,7 @@ _SIGNATURES = {
     "toist_criterion_bwd": ([c_void_p] * 9 + [c_int32] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "toist_contrastive_fwd": ([c_void_p] * 8 + [c_int32] * 5 + [c_float, c_void_p, c_void_p], ctypes.c_int),
     "toist_contrastive_bwd": ([c_void_p] * 8 + [c_int32] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "toist_contrastive_bwd_ws": ([c_void_p] * 8 + [c_int32] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "toist_l2norm_fwd": ([c_void_p, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "toist_l2norm_bwd": ([c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "toist_attnmap_softmax_fwd": ([c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p], ctypes.c_int),

@@ -46,7 +46,8 @@ __global__ __launch_bounds__(CA_THREADS) void contrastive_kernel(
     float* __restrict__ losses,              // MODE 0: [L] (+=)
     const float* __restrict__ upstream,      // MODE 1: [L]
     float* __restrict__ dpq,                 // MODE 1: [L,B,Q,D] fully written
-    float* __restrict__ dpt) {               // MODE 1: [B,T,D] (+=, caller zeroes)
+    float* __restrict__ dpt,                 // MODE 1: [B,T,D] (+=, caller zeroes)
+    float* __restrict__ dpt_layers) {        // MODE 1, optional: [L,B,T,D] each layer's share, fully written (folded in layer order later)
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int DP = D + 1;
     const bool staged = T <= CA_STAGE_TOK;
@@ -153,7 +154,8 @@ __global__ __launch_bounds__(CA_THREADS) void contrastive_kernel(
         const int t = i / D, d = i - t * D;
         float acc = 0.f;
         for (int q = 0; q < Q; ++q) acc += lg[q * T + t] * sq[q * DP + d];
-        atomicAdd(ot + i, acc);
+        if (dpt_layers) dpt_layers[(size_t)(l * B + b) * T * D + i] = acc;
+        else atomicAdd(ot + i, acc);
     }
 }
 
@@ -215,7 +217,7 @@ extern "C" int toist_contrastive_fwd(const float* proj_queries, const float* pro
     TOIST_REQUIRE(temperature > 0.f, "toist_contrastive_fwd: temperature must be positive");
     hipLaunchKernelGGL(contrastive_kernel<0>, dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
                        (const unsigned long long*)tok_mask, tgt_off, match_off, (const long long*)src_idx, (const long long*)tgt_idx, num_boxes, L, B,
-                       Q, T, D, 1.f / temperature, losses, (const float*)nullptr, (float*)nullptr, (float*)nullptr);
+                       Q, T, D, 1.f / temperature, losses, (const float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
     return check_launch("toist_contrastive_fwd");
 }
 
@@ -228,8 +230,35 @@ extern "C" int toist_contrastive_bwd(const float* proj_queries, const float* pro
     TOIST_REQUIRE(temperature > 0.f, "toist_contrastive_bwd: temperature must be positive");
     hipLaunchKernelGGL(contrastive_kernel<1>, dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
                        (const unsigned long long*)tok_mask, tgt_off, match_off, (const long long*)src_idx, (const long long*)tgt_idx, num_boxes, L, B,
-                       Q, T, D, 1.f / temperature, (float*)nullptr, upstream, dproj_queries, dproj_tokens);
+                       Q, T, D, 1.f / temperature, (float*)nullptr, upstream, dproj_queries, dproj_tokens, (float*)nullptr);
     return check_launch("toist_contrastive_bwd");
+}
+
+// dpt[i] += sum_l part[l][i], the layers in order
+__global__ __launch_bounds__(256) void fold_layers_kernel(const float* __restrict__ part, int L, long long n, float* __restrict__ out) {
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        float s = 0.f;
+        for (int l = 0; l < L; ++l) s += part[(size_t)l * n + i];
+        out[i] += s;
+    }
+}
+
+extern "C" int toist_contrastive_bwd_ws(const float* proj_queries, const float* proj_tokens, const uint64_t* tok_mask, const int32_t* tgt_off,
+                                        const int32_t* match_off, const int64_t* src_idx, const int64_t* tgt_idx, const float* num_boxes, int L,
+                                        int B, int Q, int T, int D, float temperature, const float* upstream, float* dproj_queries,
+                                        float* dproj_tokens, float* workspace, void* stream) {
+    size_t lds;
+    if (int rc = contrastive_launch_ok(L, B, Q, T, D, &lds)) return rc;
+    TOIST_REQUIRE(temperature > 0.f && workspace != nullptr, "toist_contrastive_bwd_ws: temperature must be positive, workspace given");
+    hipLaunchKernelGGL(contrastive_kernel<1>, dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
+                       (const unsigned long long*)tok_mask, tgt_off, match_off, (const long long*)src_idx, (const long long*)tgt_idx, num_boxes, L, B,
+                       Q, T, D, 1.f / temperature, (float*)nullptr, upstream, dproj_queries, dproj_tokens, workspace);
+    if (int rc = check_launch("toist_contrastive_bwd_ws")) return rc;
+    const long long n = (long long)B * T * D;
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(fold_layers_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, L, n,
+                       dproj_tokens);
+    return check_launch("toist_contrastive_bwd_ws(fold)");
 }
 
 extern "C" int toist_l2norm_fwd(const float* x, int rows, int D, float* y, void* stream) {

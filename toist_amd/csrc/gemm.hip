@@ -718,7 +718,13 @@ __device__ __forceinline__ void gemm_tile(const toist_gemm& p, const int tl, bf1
     const int kper = (ktiles + p.split_k - 1) / p.split_k;
     const int kt_beg = ksl * kper;
     const int kt_end = (kt_beg + kper < ktiles) ? kt_beg + kper : ktiles;
-    if (kt_beg >= kt_end) return;
+    if (kt_beg >= kt_end) {
+        // TOIST_GEMM_COLSUM_SLICES: an empty k-slice still owns its row of bias-gradient partials (the fold reads every slice)
+        if (A_KM && p.a_colsum != nullptr && (p.flags & TOIST_GEMM_COLSUM_SLICES) && tile_n == 0)
+            for (int col = threadIdx.x; col < BM; col += blockDim.x)
+                if (m0 + col < M) p.a_colsum[(size_t)ksl * M + m0 + col] = 0.f;
+        return;
+    }
 
     // ---- per-thread piece invariants: piece i of wave w covers LDS chunks (i*4 + w)*64 + lane ----------
     ChunkA ca[ACH];
@@ -926,7 +932,9 @@ __device__ __forceinline__ void gemm_tile(const toist_gemm& p, const int tl, bf1
         for (int col = tid; col < BM; col += 256) {
             float t = 0.f;
             for (int r = 0; r < BK; ++r) t += red[r * BM + col];
-            if (m0 + col < M) atomicAdd(p.a_colsum + (p.group ? p.group[bz].colsum_off : 0) + m0 + col, t);
+            if (m0 + col >= M) continue;
+            if (p.flags & TOIST_GEMM_COLSUM_SLICES) p.a_colsum[(size_t)ksl * M + m0 + col] = t;    // one writer per (slice, column): folded in order later
+            else atomicAdd(p.a_colsum + (p.group ? p.group[bz].colsum_off : 0) + m0 + col, t);
         }
     }
 
@@ -3307,6 +3315,9 @@ extern "C" int toist_gemm_bf16(const toist_gemm* desc, void* stream) {
                           !(d.flags & TOIST_GEMM_DEFER_REDUCE) && (d.tile & 255) != 131 && !d.a_colsum,
                       "toist_gemm_bf16: TOIST_GEMM_SPLIT_EPILOGUE needs a workspace, batch = 1, no group / row map / accumulate, N %% 4 == 0");
     if (d.a_colsum) TOIST_REQUIRE(d.a_kind == TOIST_A_KROW, "toist_gemm_bf16: a_colsum needs a k-major A operand");
+    if (d.flags & TOIST_GEMM_COLSUM_SLICES)
+        TOIST_REQUIRE(d.a_colsum != nullptr && d.group == nullptr && d.batch == 1 && d.split_k > 1 && !split_epi,
+                      "toist_gemm_bf16: TOIST_GEMM_COLSUM_SLICES needs a_colsum, split_k > 1, batch = 1, no group and no split epilogue");
     if (d.group) TOIST_REQUIRE((d.split_k <= 1 || (d.flags & TOIST_GEMM_DEFER_REDUCE)) && d.batch_inner == 1 && !d.epi.cmap && (d.tile & 255) != 131 &&
                                    d.a_kind != TOIST_A_CONVT,
                                "toist_gemm_bf16: a grouped launch takes batch_inner = 1, no cmap, a generic tile, and folds its k-slices through "
@@ -3352,6 +3363,8 @@ extern "C" int toist_gemm_bf16(const toist_gemm* desc, void* stream) {
     if (const int wt = wgrad_tile_replaced(d)) tile = wt;
     if (tile == 0) tile = auto_tile(d);
     d.split_k = clamp_split(d.split_k, d.K, tile);
+    if (d.flags & TOIST_GEMM_COLSUM_SLICES)      // the caller sized a_colsum (and its fold) by toist_gemm_effective_split: one row per slice
+        TOIST_REQUIRE(d.split_k > 1, "toist_gemm_bf16: TOIST_GEMM_COLSUM_SLICES with a split that clamps to 1 (see toist_gemm_effective_split)");
     // tile codes: 64 = 64x64x32, 65 = 64x64x64, 128 = 128x128x32, 129 = 128x128x64, 130 = 128x64x64, 132 = 128x32x64, 133 = 32x128x64
     const int bkt = (tile == 64 || tile == 128) ? 32 : 64;   // (134 = 64x128x64)
     if (d.b_kind == TOIST_B_KROW && d.b.kin > 0) TOIST_REQUIRE((d.b.kin % 8) == 0, "toist_gemm_bf16: kin %% 8 != 0");

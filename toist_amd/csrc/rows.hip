@@ -428,21 +428,56 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const long long* __restr
         *reinterpret_cast<unsigned*>(out + (size_t)t * D + c) = pack2bf(a, b);
     }
 }
-// scatter-add of the embedding gradient into the (dense, fp32) table gradients
+// the embedding gradient into the (dense, fp32) table gradients, the same sum in every run (no float atomics): the FIRST token that reads a
+// row of the word / position table owns it and adds the gradients of every token that reads it, in token order
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const bf16_t* __restrict__ g, const long long* __restrict__ ids,
                                                          const long long* __restrict__ pos_ids, int n, int D, long long pad_id,
-                                                         float* __restrict__ dword, float* __restrict__ dpos, float* __restrict__ dtype0) {
+                                                         float* __restrict__ dword, float* __restrict__ dpos) {
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= n) return;
-    // nn.Embedding(padding_idx=pad_id) never accumulates a gradient into the padding row
-    float* dw = (dword && ids[t] != pad_id) ? dword + ids[t] * (long long)D : nullptr;
-    float* dp = (dpos && pos_ids[t] != pad_id) ? dpos + pos_ids[t] * (long long)D : nullptr;
-    for (int c = lane; c < D; c += 64) {
-        const float v = bf2f(g[(size_t)t * D + c]);
-        if (dw) atomicAdd(dw + c, v);
-        if (dp) atomicAdd(dp + c, v);
-        if (dtype0) atomicAdd(dtype0 + c, v);
+    for (int which = 0; which < 2; ++which) {
+        const long long* key = which ? pos_ids : ids;
+        float* table = which ? dpos : dword;
+        if (table == nullptr) continue;
+        const long long id = key[t];
+        // nn.Embedding(padding_idx=pad_id) never accumulates a gradient into the padding row
+        if (id == pad_id) continue;
+        bool dup = false;
+        for (int u = lane; u < t; u += 64) dup |= (key[u] == id);
+        if (__any(dup)) continue;                       // an earlier token owns this row
+        float* row = table + id * (long long)D;
+        for (int c0 = 0; c0 < D; c0 += 64) {
+            const int c = c0 + lane;
+            float s = 0.f;
+            for (int base = t; base < n; base += 64) {
+                const int u = base + lane;
+                unsigned long long m = __ballot(u < n && key[u] == id);
+                while (m) {
+                    const int b = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    if (c < D) s += bf2f(g[(size_t)(base + b) * D + c]);
+                }
+            }
+            if (c < D) row[c] += s;
+        }
+    }
+}
+// the token-type row (every token reads it): 32 columns x 8 token lanes per workgroup, the lanes folded in a fixed order
+__global__ __launch_bounds__(256) void embed_type_bwd_kernel(const bf16_t* __restrict__ g, int n, int D, float* __restrict__ dtype0) {
+    __shared__ float red[8][32];
+    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cx;
+    float a = 0.f;
+    if (c < D)
+        for (int t = ry; t < n; t += 8) a += bf2f(g[(size_t)t * D + c]);
+    red[ry][cx] = a;
+    __syncthreads();
+    if (ry == 0 && c < D) {
+        float s = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) s += red[r][cx];
+        dtype0[c] += s;
     }
 }
 
@@ -546,7 +581,10 @@ extern "C" int toist_embed_fwd(const int64_t* ids, const int64_t* pos_ids, const
 extern "C" int toist_embed_bwd(const void* g, const int64_t* ids, const int64_t* pos_ids, int n, int D, int64_t pad_id, float* dword,
                                float* dpos, float* dtype0, void* stream) {
     TOIST_REQUIRE(n > 0 && D > 0, "toist_embed_bwd: bad shape");
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, (const long long*)ids,
-                       (const long long*)pos_ids, n, D, (long long)pad_id, dword, dpos, dtype0);
+    if (dword != nullptr || dpos != nullptr)
+        hipLaunchKernelGGL(embed_bwd_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, (const long long*)ids,
+                           (const long long*)pos_ids, n, D, (long long)pad_id, dword, dpos);
+    if (dtype0 != nullptr)
+        hipLaunchKernelGGL(embed_type_bwd_kernel, dim3((D + 31) / 32), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, n, D, dtype0);
     return check_launch("toist_embed_bwd");
 }

@@ -55,6 +55,7 @@ def _workspace(elems, device):
 # The queue must be flushed before anything reads those outputs: engine.Tape.backward() does it at program end.
 GEMM_DEFER_REDUCE = 2
 GEMM_SPLIT_EPILOGUE = 4
+GEMM_COLSUM_SLICES = 32768    # include/toist_hip.h: a_colsum = [k-slice][M] partials, folded in slice order
 _ARENA = {}     # (device, stream) -> [buffer, used elements]
 _PENDING = {}   # (device, stream) -> list of (ReduceDesc, keep-alive tensors)
 
@@ -85,6 +86,12 @@ def flush_reductions():
         ent = _ARENA.get(key)
         if ent is not None:
             ent[1] = 0
+
+
+def _fold_now(rd):
+    """Fold one split-K descriptor at once, on the current stream (not queued)."""
+    arr = (_lib.ReduceDesc * 1)(rd)
+    _lib.check(_lib.lib().toist_splitk_reduce_batch(ctypes.cast(arr, ctypes.c_void_p), 1, _stream()), "toist_splitk_reduce_batch")
 
 
 GROUP_MAX = 64
@@ -302,6 +309,24 @@ def gemm(M, N, K, a_kind, a, b_kind, b, c, ldc, *, batch=1, batch_inner=1, cs_ou
             deferred = (key, (rd, (c, rscale)))
         else:
             d.workspace = _p(_workspace(split_k * M * N, c.device), torch.float32)
+    colsum_now = None
+    if a_colsum is not None and split_k > 1 and group is None and not split_epilogue:
+        # the bias gradient of a split-K weight-gradient GEMM: each k-slice stores its column sums in a row of its own and one fold adds
+        # the rows in slice order -- float atomics would add them in whatever order the slices finish, a different sum in every run
+        eff_c = int(_lib.lib().toist_gemm_effective_split(ctypes.byref(d)))
+        if eff_c > 1 and M % 4 == 0 and a_colsum.data_ptr() % 16 == 0:      # (otherwise: one atomic add per slice, as before)
+            cs = torch.empty(eff_c * M, dtype=torch.float32, device=c.device)      # (not the arena: a take may flush / move it under this GEMM)
+            d.a_colsum = cs.data_ptr()
+            d.flags |= GEMM_COLSUM_SLICES
+            rd_c = _lib.ReduceDesc(cs.data_ptr(), a_colsum.data_ptr(), None, eff_c, 1, M, M, 1.0, 1)
+            key = (c.device, _raw_stream())
+            busy = any(it[0].out == a_colsum.data_ptr() for it in _PENDING.get(key, ()))
+            if (d.flags & GEMM_DEFER_REDUCE) and not busy:
+                _PENDING.setdefault(key, []).append((rd_c, (a_colsum, cs)))
+            else:
+                # folded on its own right after this GEMM: the GEMM is not deferred, or a queued fold already adds into the same bias
+                # (two folds of one output must not share a launch); the other queued folds stay batched
+                colsum_now = (rd_c, cs)
     if deferred is not None:
         _PENDING.setdefault(deferred[0], []).append(deferred[1])
     if DEBUG_WS is not None and split_k <= 1:
@@ -310,6 +335,8 @@ def gemm(M, N, K, a_kind, a, b_kind, b, c, ldc, *, batch=1, batch_inner=1, cs_ou
     prof = PROFILE
     if prof is None:
         _lib.check(_lib.lib().toist_gemm_bf16(ctypes.byref(d), _stream()), "toist_gemm_bf16")
+        if colsum_now is not None:
+            _fold_now(colsum_now[0])
         return
     if not flops:
         flops = 2 * M * N * K * max(batch, 1)
@@ -318,12 +345,16 @@ def gemm(M, N, K, a_kind, a, b_kind, b, c, ldc, *, batch=1, batch_inner=1, cs_ou
     want = prof["key"]
     if want is not None and not (want(key) if callable(want) else (key == want or (isinstance(want, (set, frozenset)) and key in want))):
         _lib.check(_lib.lib().toist_gemm_bf16(ctypes.byref(d), _stream()), "toist_gemm_bf16")
+        if colsum_now is not None:
+            _fold_now(colsum_now[0])
         prof["other"][key] = prof["other"].get(key, 0) + flops
         return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     _lib.check(_lib.lib().toist_gemm_bf16(ctypes.byref(d), _stream()), "toist_gemm_bf16")
     e1.record()
+    if colsum_now is not None:
+        _fold_now(colsum_now[0])
     ta = max(int(a.R) * int(a.S), 1) if a_kind in (A_CONV, A_CONVT) else 1
     tb = max(int(b.R) * int(b.S), 1) if b_kind == B_CONVX else 1
     nb = max(batch, 1)
@@ -510,10 +541,11 @@ def contrastive_fwd(pq, pt, tok_mask, tgt_off, match_off, src_idx, tgt_idx, num_
 
 def contrastive_bwd(pq, pt, tok_mask, tgt_off, match_off, src_idx, tgt_idx, num_boxes, temperature, upstream, dpq, dpt):
     L, B, Q, D = pq.shape
-    _lib.check(_lib.lib().toist_contrastive_bwd(_p(pq, torch.float32), _p(pt, torch.float32), _p(tok_mask, torch.int64), _p(tgt_off, torch.int32),
-                                                _p(match_off, torch.int32), _p(src_idx, torch.int64), _p(tgt_idx, torch.int64),
-                                                _p(num_boxes, torch.float32), L, B, Q, pt.shape[1], D, temperature, _p(upstream, torch.float32),
-                                                _p(dpq, torch.float32), _p(dpt, torch.float32), _stream()), "toist_contrastive_bwd")
+    ws = torch.empty(L * B * pt.shape[1] * D, dtype=torch.float32, device=pq.device)     # each layer's token gradient, folded in layer order
+    _lib.check(_lib.lib().toist_contrastive_bwd_ws(_p(pq, torch.float32), _p(pt, torch.float32), _p(tok_mask, torch.int64), _p(tgt_off, torch.int32),
+                                                   _p(match_off, torch.int32), _p(src_idx, torch.int64), _p(tgt_idx, torch.int64),
+                                                   _p(num_boxes, torch.float32), L, B, Q, pt.shape[1], D, temperature, _p(upstream, torch.float32),
+                                                   _p(dpq, torch.float32), _p(dpt, torch.float32), _p(ws, torch.float32), _stream()), "toist_contrastive_bwd_ws")
 
 
 def l2norm_fwd(x, y):

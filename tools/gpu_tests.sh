@@ -7,5 +7,5 @@ O=gpurun_out/$TAG
 mkdir -p $O
 ( time timeout 2400 python -m pytest tests -m gpu -q -p no:cacheprovider --durations=15 "$@" ) > $O/pytest.log 2>&1
 tail -60 $O/pytest.log | cut -c1-400
-( time timeout 900 python bench.py ) > $O/bench_default.log 2>&1
+( time timeout 900 python bench.py --full ) > $O/bench_default.log 2>&1
 tail -3 $O/bench_default.log | cut -c1-3000

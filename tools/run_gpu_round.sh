@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/$TAG
 mkdir -p $O
-( time timeout 900 python bench.py ) > $O/bench_default.log 2>&1
+( time timeout 900 python bench.py --full ) > $O/bench_default.log 2>&1
 tail -4 $O/bench_default.log | cut -c1-2500
 timeout 600 python bench.py --static-batch --no-cpu-baseline --no-roofline > $O/bench_static_batch.log 2>&1
 timeout 600 python bench.py --no-graph --no-cpu-baseline --no-roofline > $O/bench_eager.log 2>&1

@@ -695,6 +695,14 @@ TOIST_API int toist_opt_adamw_ema_blocks(const toist_opt_tensor* table, const in
  *                 (transitions + 1) run lengths, zeros first, to counts[first_run[m] ...]  (= rleEncode's cnts) */
 TOIST_API int toist_mask_resize_pack(const float* src, int n, int h0, int w0, int max_h, int max_w, int crop_h, int crop_w, int h, int w,
                            float threshold, uint64_t* bits, void* stream);
+/* resize_pack for a whole batch in one launch that takes every size from the device (the batched form of PostProcessSegm's loop over the images,
+ * models/postprocessors.py:86-107; nothing is read from the host, so the launch can sit in a captured hipGraph): src [batch, queries, h0, w0] fp32,
+ * one first-resize size [max_h, max_w] for all images, table int64 [batch, 4] = (crop_h, crop_w, h, w) per image.  Image i writes its `queries`
+ * planes [queries, w_i, ceil(h_i/64)] densely from word i * capacity_words of `bits`; the words behind them are left untouched.  The grid covers
+ * [cap_h, cap_w]; capacity_words >= queries * cap_w * ceil(cap_h/64).  A table row that does not fit (h_i > cap_h, w_i > cap_w, crop outside
+ * [max_h, max_w]) writes nothing: the caller checks its sizes on the host before the launch. */
+TOIST_API int toist_mask_resize_pack_batch(const float* src, int batch, int queries, int h0, int w0, int max_h, int max_w, const int64_t* table,
+                                 int cap_h, int cap_w, long long capacity_words, float threshold, uint64_t* bits, void* stream);
 TOIST_API int toist_mask_pack(const uint8_t* dense, int n, int h, int w, uint64_t* bits, void* stream);
 TOIST_API int toist_mask_unpack(const uint64_t* bits, int n, int h, int w, uint8_t* dense, void* stream);
 TOIST_API int toist_mask_area(const uint64_t* bits, int n, int h, int w, uint32_t* area, void* stream);
@@ -704,6 +712,14 @@ TOIST_API int toist_mask_rle_count(const uint64_t* bits, int n, int h, int w, in
 TOIST_API int toist_mask_rle_emit(const uint64_t* bits, int n, int h, int w, const int64_t* column_offset, uint32_t* positions, void* stream);
 TOIST_API int toist_mask_rle_counts(const uint32_t* positions, const int64_t* first_position, const int64_t* first_run, int n, int h, int w,
                           uint32_t* counts, void* stream);
+
+/* PostProcess for a whole batch in one launch (models/postprocessors.py:19-55): per (image, query) row
+ *   scores [B, Q] f32        = 1 - softmax(pred_logits [B, Q, C])[-1], fp32 with the row maximum subtracted
+ *   boxes  [B, Q, 4] f32     = pred_boxes (cx, cy, w, h) as (x0, y0, x1, y1), scaled by the image's (w, h, w, h)
+ *   scores_refexp [B, Q] f32 = scores * sigmoid(pred_isfinal [B, Q])        (both NULL without the referring-expression head)
+ * orig_sizes = DEVICE int64 [B, 2] rows (h, w).  *_bf16 != 0: that input holds bfloat16, else fp32.  The labels are the constant 1 (host side). */
+TOIST_API int toist_postprocess(const void* pred_logits, int logits_bf16, const void* pred_boxes, int boxes_bf16, const void* pred_isfinal, int isfinal_bf16,
+                      const int64_t* orig_sizes, int B, int Q, int C, float* scores, float* boxes, float* scores_refexp, void* stream);
 
 /* COCOeval.evaluateImg over a batch of images (pycocotools cocoeval.py; reached from datasets/coco_eval.py:368-399).  Image i owns
  * detections [dt_offset[i], dt_offset[i+1]) (score-descending, already cut to maxDets[-1]), ground truth [gt_offset[i], gt_offset[i+1])

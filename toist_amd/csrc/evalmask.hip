@@ -6,6 +6,7 @@
 //     bits[mask][x][yw]   (uint64; bit b of word yw is pixel (y = 64*yw + b, x); bits beyond H are 0)
 // which is 1/32 of an fp32 mask and already in RLE's pixel order (pixel index = x*H + y):
 //   * mask_resize_pack : both bilinear resizes + sigmoid + threshold fused, straight from the [h0, w0] mask logits
+//   * mask_resize_pack_batch : the same for every image of a batch in one launch, sizes read from a device table (captured evaluation)
 //   * mask_pack/unpack : dense bool <-> bit plane (ground truth in, reference-format results out)
 //   * mask_area / mask_iou : popcounts; IoU = i / (crowd ? area_d : area_d + area_g - i) in double, as rleIou does
 //   * mask_rle_count / emit / counts : run lengths (zeros first) = differences of the transition positions
@@ -41,15 +42,13 @@ __device__ __forceinline__ float bilerp(const float* __restrict__ p, int ld, con
            ty.l1 * (tx.l0 * p[(size_t)ty.i1 * ld + tx.i0] + tx.l1 * p[(size_t)ty.i1 * ld + tx.i1]);
 }
 
-// grid: (ceil(W/64) * YW / 4, n_masks); wave = one (x tile, y word)
-__global__ __launch_bounds__(EM_THREADS) void mask_resize_pack_kernel(const float* __restrict__ src, int h0, int w0, int max_h, int max_w, int crop_h,
-                                                                       int crop_w, int H, int W, float threshold, uint64_t* __restrict__ bits) {
+// One wave's share of mask_resize_pack: work unit `unit` = (x tile, y word) of ONE mask whose logits are `p` [h0, w0] and whose plane is `plane`
+// [W, ceil(H/64)].  Shared by the per-image and the batched kernel, so both produce the same bits.
+__device__ __forceinline__ void resize_pack_unit(const float* __restrict__ p, int h0, int w0, int max_h, int max_w, int crop_h, int crop_w, int H, int W,
+                                                 float threshold, uint64_t* __restrict__ plane, int unit) {
     const int yw_n = words_of(H), xt_n = (W + 63) >> 6;
-    const int unit = blockIdx.x * (EM_THREADS / 64) + (threadIdx.x >> 6);
     if (unit >= yw_n * xt_n) return;
     const int yw = unit % yw_n, x = (unit / yw_n) * 64 + (threadIdx.x & 63);
-    const int m = blockIdx.y;
-    const float* p = src + (size_t)m * h0 * w0;
     // stage 1: [h0, w0] -> [max_h, max_w]; stage 2: its [crop_h, crop_w] corner -> [H, W]
     const float s1y = (float)h0 / (float)max_h, s1x = (float)w0 / (float)max_w;
     const float s2y = (float)crop_h / (float)H, s2x = (float)crop_w / (float)W;
@@ -67,7 +66,33 @@ __global__ __launch_bounds__(EM_THREADS) void mask_resize_pack_kernel(const floa
         const float prob = 1.f / (1.f + expf(-v));
         word |= (uint64_t)(prob > threshold) << b;
     }
-    bits[((size_t)m * W + x) * yw_n + yw] = word;
+    plane[(size_t)x * yw_n + yw] = word;
+}
+
+// grid: (ceil(W/64) * YW / 4, n_masks); wave = one (x tile, y word)
+__global__ __launch_bounds__(EM_THREADS) void mask_resize_pack_kernel(const float* __restrict__ src, int h0, int w0, int max_h, int max_w, int crop_h,
+                                                                       int crop_w, int H, int W, float threshold, uint64_t* __restrict__ bits) {
+    const int unit = blockIdx.x * (EM_THREADS / 64) + (threadIdx.x >> 6);
+    const int m = blockIdx.y;
+    resize_pack_unit(src + (size_t)m * h0 * w0, h0, w0, max_h, max_w, crop_h, crop_w, H, W, threshold, bits + (size_t)m * W * words_of(H), unit);
+}
+
+// The same for a whole batch in ONE launch whose every size comes from the device: image i = blockIdx.z reads row i of `table` = (crop_h, crop_w, h, w)
+// and writes its Q planes [Q, w, ceil(h/64)] densely from word i * capacity_words.  grid: (units of the capacity [cap_h, cap_w] / 4, Q, B); the
+// workgroups beyond an image's own extent leave at once (no memory traffic), so the launch moves the bytes of the B per-image launches.  A row
+// that does not fit (h > cap_h, w > cap_w, more words than the capacity, crop outside the first resize) writes nothing: the host checks before it launches.
+__global__ __launch_bounds__(EM_THREADS) void mask_resize_pack_batch_kernel(const float* __restrict__ src, int Q, int h0, int w0, int max_h, int max_w,
+                                                                             const int64_t* __restrict__ table, int cap_h, int cap_w,
+                                                                             long long capacity_words, float threshold, uint64_t* __restrict__ bits) {
+    const int img = blockIdx.z, m = blockIdx.y;
+    const int64_t* row = table + (size_t)img * 4;
+    const long long crop_h = row[0], crop_w = row[1], H = row[2], W = row[3];
+    if (H <= 0 || W <= 0 || H > cap_h || W > cap_w || crop_h <= 0 || crop_w <= 0 || crop_h > max_h || crop_w > max_w) return;
+    const long long plane = W * (long long)words_of((int)H);
+    if (plane * Q > capacity_words) return;
+    const int unit = blockIdx.x * (EM_THREADS / 64) + (threadIdx.x >> 6);
+    resize_pack_unit(src + ((size_t)img * Q + m) * h0 * w0, h0, w0, max_h, max_w, (int)crop_h, (int)crop_w, (int)H, (int)W, threshold,
+                     bits + (size_t)img * capacity_words + (size_t)m * plane, unit);
 }
 
 __global__ __launch_bounds__(EM_THREADS) void mask_pack_kernel(const uint8_t* __restrict__ dense, int H, int W, uint64_t* __restrict__ bits) {
@@ -279,6 +304,22 @@ extern "C" int toist_mask_resize_pack(const float* src, int n, int h0, int w0, i
     hipLaunchKernelGGL(mask_resize_pack_kernel, tile_grid(n, h, w), dim3(EM_THREADS), 0, stream, src, h0, w0, max_h, max_w, crop_h, crop_w, h, w,
                        threshold, bits);
     return check_launch("toist_mask_resize_pack");
+}
+
+extern "C" int toist_mask_resize_pack_batch(const float* src, int batch, int queries, int h0, int w0, int max_h, int max_w, const int64_t* table, int cap_h,
+                                            int cap_w, long long capacity_words, float threshold, uint64_t* bits, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    TOIST_REQUIRE(batch >= 0 && queries >= 0 && batch <= 65535 && queries <= 65535 && cap_h > 0 && cap_w > 0 && (long long)cap_h * cap_w < (1ll << 32),
+                  "toist_mask_resize_pack_batch: bad geometry");
+    if (batch == 0 || queries == 0) return TOIST_OK;
+    TOIST_REQUIRE(src && table && bits, "toist_mask_resize_pack_batch: null pointer");
+    TOIST_REQUIRE(h0 > 0 && w0 > 0 && max_h > 0 && max_w > 0, "toist_mask_resize_pack_batch: bad source / first-resize size");
+    TOIST_REQUIRE(capacity_words >= (long long)queries * cap_w * ((cap_h + 63) / 64),
+                  "toist_mask_resize_pack_batch: capacity_words %lld cannot hold %d planes of [%d, %d]", capacity_words, queries, cap_h, cap_w);
+    const dim3 g = tile_grid(queries, cap_h, cap_w);
+    hipLaunchKernelGGL(mask_resize_pack_batch_kernel, dim3(g.x, g.y, batch), dim3(EM_THREADS), 0, stream, src, queries, h0, w0, max_h, max_w, table, cap_h, cap_w,
+                       capacity_words, threshold, bits);
+    return check_launch("toist_mask_resize_pack_batch");
 }
 
 extern "C" int toist_mask_pack(const uint8_t* dense, int n, int h, int w, uint64_t* bits, void* stream_) {

@@ -179,20 +179,46 @@ class DistillTables:
             if not empty[i]:
                 sub_span[span_positions(tokenized, i, [s_ for box in boxes for s_ in box], L).numpy(), i] = 1
         if self.pronoun_side:
-            for i in range(B):
-                beg = captions[i].find("something")
-                first, last = (tokenized.char_to_token(i, beg), tokenized.char_to_token(i, beg + len("something") - 1)) if beg >= 0 else (None, None)
-                if first is None or last is None:      # (the reference fails here too: mdetr.py:240-246 indexes with the None it gets back)
-                    raise ValueError(f"pronoun caption {i} ({captions[i]!r}) has no token for the word 'something'")
-                pos = np.arange(first, last + 1)
-                if len(pos) == 0:
-                    W_sth[i, :] = np.nan
-                else:
-                    W_sth[i, pos] = np.float32(1.0 / len(pos))
-                    sub_sth[pos, i] = 1
+            self._pack_something(tokenized, captions, W_sth, sub_sth)
             tasks = [task_index(t["dataset_name"]) for t in targets]               # the student clusters EVERY sample (mdetr.py:230-277)
         else:
             tasks = [-1 if empty[i] else task_index(t["dataset_name"]) for i, t in enumerate(targets)]
+        self._pack_groups(tasks, task, group_task, group_off, members)
+        return host
+
+    def pack_eval(self, tokenized, captions, dataset_names, out=None):
+        """Host image of one EVALUATION batch (pronoun side): what the prototype choice of inference reads (mdetr.py:282-312) -- W_sth, sub_sth, task and
+        the grouping by task -- from the tokenized captions (char_to_token), the caption strings and the dataset names alone.  No targets: W_span /
+        sub_span stay zero (only the teacher's bank update reads them)."""
+        B = self.B
+        if not self.pronoun_side:
+            raise ValueError("pack_eval fills the pronoun side's tables")
+        if len(captions) != B or len(dataset_names) != B:
+            raise ValueError(f"DistillTables holds {B} images; got {len(captions)} captions and {len(dataset_names)} dataset names")
+        host = out if out is not None else torch.zeros(self._host.numel(), dtype=torch.uint8)
+        if out is None and self._pin:
+            host = host.pin_memory()
+        host.zero_()
+        _, W_sth, _, sub_sth, task, group_task, group_off, members = (v.numpy() for v in self._views(host))
+        self._pack_something(tokenized, captions, W_sth, sub_sth)
+        self._pack_groups([task_index(n) for n in dataset_names], task, group_task, group_off, members)
+        return host
+
+    def _pack_something(self, tokenized, captions, W_sth, sub_sth):
+        for i in range(self.B):
+            beg = captions[i].find("something")
+            first, last = (tokenized.char_to_token(i, beg), tokenized.char_to_token(i, beg + len("something") - 1)) if beg >= 0 else (None, None)
+            if first is None or last is None:      # (the reference fails here too: mdetr.py:240-246 indexes with the None it gets back)
+                raise ValueError(f"pronoun caption {i} ({captions[i]!r}) has no token for the word 'something'")
+            pos = np.arange(first, last + 1)
+            if len(pos) == 0:
+                W_sth[i, :] = np.nan
+            else:
+                W_sth[i, pos] = np.float32(1.0 / len(pos))
+                sub_sth[pos, i] = 1
+
+    @staticmethod
+    def _pack_groups(tasks, task, group_task, group_off, members):
         task[:] = np.asarray(tasks, dtype=np.int32)
         live = [(i, t) for i, t in enumerate(tasks) if t >= 0]
         order = sorted(set(t for _, t in live))
@@ -204,7 +230,6 @@ class DistillTables:
         group_off[:len(off)] = off
         group_off[len(off):] = len(mem)
         members[:len(mem)] = mem
-        return host
 
     def load_packed(self, host):
         self._dev.copy_(host, non_blocking=True)
@@ -465,6 +490,21 @@ class ClusterCriterion(nn.Module):
         mod[-L:] = torch.where(tb.sub_sth.bool()[:, :, None], chosen[None].to(mod.dtype), mod[-L:])
         loss = ((features - chosen.to(features.dtype)) ** 2).mean(1).sum() / max(B, 1)
         return memory_cache_sth, {"loss_cluster_choice": torch.zeros((), device=loss.device), "loss_cluster_feature": loss}
+
+    @torch.no_grad()
+    def infer_choice_static(self, memory_cache_sth, tb):
+        """infer_choice (mdetr.py:279-312) on a DistillTables image filled by pack_eval: the word 'something' of every caption is replaced by the
+        prototype closest to its own feature, with no host value in any launch (harness.CapturedEvalStep records it into its graphs).  k-means moves
+        `cluster_centers` in place, as memory_cluster does."""
+        self._static_ok()
+        text = memory_cache_sth["text_memory"].permute(1, 0, 2)
+        L = text.shape[1]
+        memory_cache_sth["img_memory_mod"] = memory_cache_sth["img_memory"].clone()
+        features = (tb.W_sth.to(text.dtype).unsqueeze(-1) * text).sum(1)
+        _, chosen = self._cluster_static(features, tb)
+        mod = memory_cache_sth["img_memory_mod"]
+        mod[-L:] = torch.where(tb.sub_sth.bool()[:, :, None], chosen[None].to(mod.dtype), mod[-L:])
+        return memory_cache_sth
 
     def update_memory(self, memory_cache_noun, targets_noun, captions_noun):
         """Teacher side (mdetr.py:105-205): push this batch's noun features into the banks, then replace the noun

@@ -167,12 +167,29 @@ def synthetic_ground_truth(batches):
     return {"images": images, "annotations": anns, "categories": [{"id": 1, "name": "preferred"}]}
 
 
+def _captured_eval_batch(captured, batch):
+    """One batch of evaluate(captured=...): forward + post-processing from the CapturedEvalStep.  The sizes are taken from batch["orig_sizes"] /
+    batch["sizes"] (host lists of (h, w), what a loader has) when present, else read back from the targets' tensors."""
+    targets = batch["targets"]
+    text = batch["tokenized"] if "tokenized" in batch else [t["caption"] for t in targets]
+    orig = batch["orig_sizes"] if "orig_sizes" in batch else torch.stack([t["orig_size"] for t in targets], dim=0).tolist()
+    sizes = batch["sizes"] if "sizes" in batch else torch.stack([t["size"] for t in targets], dim=0).tolist()
+    names = captions = None
+    if captured.cluster_criterion is not None:
+        names, captions = [t["dataset_name"] for t in targets], [t["caption"] for t in targets]
+    return captured.step(batch["samples"], text, orig, sizes, dataset_names=names, captions=captions)
+
+
 @torch.no_grad()
-def evaluate(model, criterion, cluster_criterion, postprocessors, weight_dict, batches, evaluator_list, device, args):
+def evaluate(model, criterion, cluster_criterion, postprocessors, weight_dict, batches, evaluator_list, device, args, captured=None):
     """The reference's evaluation loop: per batch encode -> (prototype choice) -> decode -> losses for logging -> PostProcess
     (-> PostProcessSegm) -> evaluator.update; then gather across ranks, accumulate, summarize.  `batches` yields dicts with
     "samples", "tokenized" (or captions), "targets", "positive_map"; returns {"loss": ..., "coco_eval_bbox": [12 numbers],
-    "coco_eval_masks": [...]}."""
+    "coco_eval_masks": [...]}.
+    captured: a CapturedEvalStep built around `model` -- forward and post-processing of every batch then come from its hipGraphs (one upload + one
+    graph launch per batch).  The losses for logging still need an eager forward and are computed only when `criterion` is given; with
+    criterion=None the loop is graph replays + evaluator updates.  (With a cluster criterion AND a criterion the prototype choice runs twice per batch;
+    k-means restarted from converged centres leaves them where they are.)"""
     from . import dist as tdist
     from .mdetr import weighted_total
     model.eval()
@@ -184,6 +201,22 @@ def evaluate(model, criterion, cluster_criterion, postprocessors, weight_dict, b
     for batch in batches:
         samples, targets = batch["samples"], batch["targets"]
         text = batch["tokenized"] if "tokenized" in batch else [t["caption"] for t in targets]
+        if captured is not None:
+            if criterion is not None:                               # losses for logging: an eager forward, as below
+                memory_cache = model(samples, text, encode_and_save=True)
+                if getattr(args, "cluster", False):
+                    memory_cache = cluster_criterion.infer_choice(memory_cache, [t["dataset_name"] for t in targets], [t["caption"] for t in targets])
+                outputs = model(samples, text, encode_and_save=False, memory_cache=memory_cache)
+                loss_dict = tdist.reduce_dict(criterion(memory_cache, outputs, targets, batch.get("positive_map"), batch.get("example_rel")))
+                for name, v in loss_dict.items():
+                    sums[name] = sums.get(name, 0.0) + float(v)
+                sums["loss"] = sums.get("loss", 0.0) + float(weighted_total(loss_dict, weight_dict))
+            n += 1
+            results = _captured_eval_batch(captured, batch)         # (reads the XCD-resident decoder's status itself before it returns)
+            res = {int(t["image_id"]): r for t, r in zip(targets, results)}
+            for evaluator in evaluator_list:
+                evaluator.update(res)
+            continue
         memory_cache = model(samples, text, encode_and_save=True)
         if getattr(args, "cluster", False):
             memory_cache = cluster_criterion.infer_choice(memory_cache, [t["dataset_name"] for t in targets], [t["caption"] for t in targets])
@@ -373,6 +406,228 @@ class CapturedTrainStep:
                 self.captures += 1
         torch.cuda.current_stream().wait_stream(side)
         return total
+
+    __call__ = step
+
+
+class CapturedEvalStep:
+    """The reference's evaluation body (engine.py:253-342: encode -> optional prototype choice -> decode -> PostProcess -> optional PostProcessSegm) replayed
+    from hipGraphs, one per input-shape BUCKET (Hp, Wp, Lp) -- the padding rules and the LRU of `max_graphs` are CapturedTrainStep's; the batch size is
+    fixed; everything runs under torch.no_grad() with the model in eval().
+
+    step(samples, tokenized, orig_sizes, sizes, dataset_names=None, captions=None) -> results: a list of dicts with the keys, dtypes and shapes of
+    PostProcess and PostProcessSegm(packed=True): "scores" f32 [Q], "labels" int64 [Q], "boxes" f32 [Q, 4] (+ "scores_refexp" when the model emits
+    pred_isfinal), with a mask head "mask_bits" int64 [Q, w_i, ceil(h_i/64)] + "mask_size" (h_i, w_i) -- TDODCocoEvaluator.update takes them unchanged.
+    Every tensor is a view into the bucket's output buffers, valid until the next step of that bucket.  dense_masks=True replaces the packed planes by
+    the reference's "masks" bool [Q, 1, h_i, w_i] on the host.
+    orig_sizes / sizes: (h, w) per image as HOST values (lists, or host tensors): they travel to the device in one fixed-address int64 table per bucket
+    that the two post-processing kernels read (csrc/postproc.hip, csrc/evalmask.hip), so nothing is read back before the launch.
+
+    The FIRST batch of a bucket runs eagerly on the object's side stream and the graph is captured right after (inside kernels.tables_beside_graph());
+    later batches of that bucket are one upload of the inputs + one graph launch.
+    Masks: the planes of image i start at word i * capacity of one buffer per bucket, capacity = Q * max_orig_hw[1] * ceil(max_orig_hw[0] / 64); an
+    image larger than `max_orig_hw` raises ValueError before anything is launched.  In a padded bucket pred_masks cover (Hp, Wp), so the FIRST resize
+    target is the bucket's (Hp, Wp), not the batch's largest image, and the crop is each image's `size` -- what the reference computes on a batch
+    whose largest image is Hp x Wp (models/postprocessors.py:86-107).
+    Prototype choice: with a `cluster_criterion` it runs inside the graph (ClusterCriterion.infer_choice_static on a DistillTables image filled by
+    pack_eval from the tokenized captions -- which must answer char_to_token --, the caption strings and the dataset names); the preconditions are
+    ClusterCriterion._static_ok's.  k-means moves cluster_centers in place, as the reference's memory_cluster does.
+    XCD-resident decoder: when the captured graph holds that launch, its status word is read after every replay (kernels.xdec_check: the one
+    synchronisation of a step, at the point where the results are handed out); a failed launch drops every graph, and the same batch runs again on the
+    per-op launches and is captured again -- inference has no state a failed step could have poisoned.
+    Data parallelism: the forward holds no collective, every rank evaluates its own shard, so the step stays captured under torch.distributed."""
+
+    def __init__(self, model, cluster_criterion=None, *, batch, masks=None, max_orig_hw=None, pad_hw=64, pad_tokens=1, max_graphs=4, dense_masks=False,
+                 threshold=0.5, device=None):
+        from collections import OrderedDict
+        self.model, self.cluster_criterion = model, cluster_criterion
+        self.batch, self.pad_hw, self.pad_tokens, self.max_graphs = int(batch), int(pad_hw), int(pad_tokens), int(max_graphs)
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        det = getattr(model, "detr", model)
+        self.num_queries = det.query_embed.weight.shape[0]
+        self.masks = hasattr(model, "detr") if masks is None else bool(masks)
+        self.dense_masks, self.threshold = bool(dense_masks), float(threshold)
+        if self.masks and max_orig_hw is None:
+            raise ValueError("CapturedEvalStep with a mask head needs max_orig_hw = the largest original (h, w) it has to hold")
+        self.max_orig_hw = (int(max_orig_hw[0]), int(max_orig_hw[1])) if max_orig_hw is not None else None
+        self.capacity_words = self.num_queries * self.max_orig_hw[1] * ((self.max_orig_hw[0] + 63) // 64) if self.masks else 0
+        self._buckets = OrderedDict()          # (Hp, Wp, Lp) -> dict(graph, samples, tok, sizes, out, bits, tables, xdec)
+        self._side = None
+        self.captures = 0
+        self.replays = 0
+        self._xdec_off = False
+
+    # -- helpers ------------------------------------------------------------------------------------------------------------------
+    def bucket_of(self, samples, tokenized):
+        H, W = samples.tensors.shape[-2:]
+        L = tokenized["input_ids"].shape[1]
+        up = lambda v, m: (int(v) + m - 1) // m * m
+        return up(H, self.pad_hw), up(W, self.pad_hw), up(L, self.pad_tokens)
+
+    @staticmethod
+    def _pairs(v):
+        rows = v.tolist() if torch.is_tensor(v) else [(r.tolist() if torch.is_tensor(r) else r) for r in v]
+        return [(int(r[0]), int(r[1])) for r in rows]
+
+    def check_sizes(self, key, orig_sizes, sizes):
+        """Host check of a batch's sizes against the bucket and the mask capacity (ValueError; nothing has been launched).  -> (orig, sizes) as int pairs."""
+        orig, crop = self._pairs(orig_sizes), self._pairs(sizes)
+        if len(orig) != self.batch or len(crop) != self.batch:
+            raise ValueError(f"CapturedEvalStep was built for batches of {self.batch} images (got {len(orig)} original sizes, {len(crop)} sizes)")
+        for (h, w), (ch, cw) in zip(orig, crop):
+            if h <= 0 or w <= 0 or ch <= 0 or cw <= 0 or ch > key[0] or cw > key[1]:
+                raise ValueError(f"CapturedEvalStep: an image of size {ch} x {cw} (original {h} x {w}) does not fit the padded batch {key[0]} x {key[1]}")
+            if self.masks and (h > self.max_orig_hw[0] or w > self.max_orig_hw[1]):
+                raise ValueError(f"CapturedEvalStep: an original size of {h} x {w} exceeds max_orig_hw = {self.max_orig_hw[0]} x {self.max_orig_hw[1]} "
+                                 "(the capacity of the mask planes)")
+        return orig, crop
+
+    def _static_inputs(self, key):
+        from .misc import NestedTensor
+        from .transformer import TokenizedText
+        Hp, Wp, Lp = key
+        dev, B = self.device, self.batch
+        pad_id = getattr(getattr(self.model, "detr", self.model).transformer.text_encoder.config, "pad_token_id", 1)
+        ent = {"samples": NestedTensor(torch.zeros(B, 3, Hp, Wp, device=dev), torch.ones(B, Hp, Wp, dtype=torch.bool, device=dev)),
+               "tok": TokenizedText({"input_ids": torch.full((B, Lp), pad_id, dtype=torch.int64, device=dev),
+                                     "attention_mask": torch.zeros(B, Lp, dtype=torch.int64, device=dev)}),
+               # rows 0 .. 2B: (h, w) originals for toist_postprocess; rows 2B .. 6B: (crop_h, crop_w, h, w) for toist_mask_resize_pack_batch
+               "sizes_host": torch.ones(6 * B, dtype=torch.int64).pin_memory(), "sizes": torch.ones(6 * B, dtype=torch.int64, device=dev),
+               "sizes_event": None, "out": None, "graph": None, "xdec": False, "pad_id": pad_id, "tables": None,
+               "bits": torch.zeros(B * self.capacity_words, dtype=torch.int64, device=dev) if self.masks else None}
+        if self.cluster_criterion is not None:
+            from .distill import DistillTables
+            ent["tables"] = DistillTables(B, Lp, dev, pronoun_side=True)
+        return ent
+
+    def _fill(self, ent, samples, tokenized, orig, crop, dataset_names, captions):
+        img, msk = ent["samples"].tensors, ent["samples"].mask
+        B, _, H, W = samples.tensors.shape
+        if (H, W) != tuple(img.shape[-2:]):
+            img.zero_()
+            msk.fill_(True)
+        img[:, :, :H, :W].copy_(samples.tensors, non_blocking=True)
+        msk[:, :H, :W].copy_(samples.mask, non_blocking=True)
+        ids, att = ent["tok"]["input_ids"], ent["tok"]["attention_mask"]
+        L = tokenized["input_ids"].shape[1]
+        if L != ids.shape[1]:
+            ids.fill_(ent["pad_id"])
+            att.zero_()
+        ids[:, :L].copy_(tokenized["input_ids"], non_blocking=True)
+        att[:, :L].copy_(tokenized["attention_mask"], non_blocking=True)
+        if ent["sizes_event"] is not None:
+            ent["sizes_event"].synchronize()           # the previous upload has left the staging buffer
+        host = ent["sizes_host"]
+        host[:2 * B] = torch.tensor(orig, dtype=torch.int64).view(-1)
+        host[2 * B:] = torch.tensor([c + o for c, o in zip(crop, orig)], dtype=torch.int64).view(-1)
+        ent["sizes"].copy_(host, non_blocking=True)
+        ent["sizes_event"] = torch.cuda.Event()
+        ent["sizes_event"].record()
+        if ent["tables"] is not None:
+            tb = ent["tables"]
+            if tb._event is not None:
+                tb._event.synchronize()
+            tb.load_packed(tb.pack_eval(tokenized, captions, dataset_names, out=tb._host))
+            tb._event = torch.cuda.Event()
+            tb._event.record()
+
+    def _forward(self, ent, key):
+        """The launches of one batch on the bucket's static inputs (eagerly, and once more under capture)."""
+        from . import kernels
+        B = self.batch
+        mc = self.model(ent["samples"], ent["tok"], encode_and_save=True)
+        if self.cluster_criterion is not None:
+            mc = self.cluster_criterion.infer_choice_static(mc, ent["tables"])
+            if ent.get("img_memory_mod") is None:                # the memory with the chosen prototypes, copied to a fixed buffer: readable after any step
+                ent["img_memory_mod"] = torch.empty_like(mc["img_memory_mod"])
+            ent["img_memory_mod"].copy_(mc["img_memory_mod"])
+        outputs = self.model(ent["samples"], ent["tok"], encode_and_save=False, memory_cache=mc)
+        ent["out"] = kernels.postprocess(outputs["pred_logits"], outputs["pred_boxes"], ent["sizes"][:2 * B].view(B, 2), outputs.get("pred_isfinal"),
+                                         out=ent["out"])
+        if self.masks:
+            logits = outputs["pred_masks"].squeeze(2).float().contiguous()                # [B, Q, h0, w0]; they cover the padded (Hp, Wp)
+            kernels.mask_resize_pack_batch(logits, (key[0], key[1]), ent["sizes"][2 * B:].view(B, 4), self.max_orig_hw, self.capacity_words, ent["bits"],
+                                           self.threshold)
+
+    def _results(self, ent, orig):
+        from . import kernels
+        from .postprocessors import PostProcess
+        out, B, Q = ent["out"], self.batch, self.num_queries
+        lkey = (str(self.device), B, Q)
+        labels = PostProcess._LABELS.get(lkey)
+        if labels is None:
+            labels = PostProcess._LABELS[lkey] = torch.ones(B, Q, dtype=torch.int64, device=self.device)
+        results = []
+        for i, (h, w) in enumerate(orig):
+            r = {"scores": out["scores"][i], "labels": labels[i], "boxes": out["boxes"][i]}
+            if "scores_refexp" in out:
+                r["scores_refexp"] = out["scores_refexp"][i]
+            if self.masks:
+                words = kernels.mask_words(h)
+                bits = ent["bits"][i * self.capacity_words:i * self.capacity_words + Q * w * words].view(Q, w, words)
+                if self.dense_masks:
+                    r["masks"] = kernels.mask_unpack(bits, h, w).unsqueeze(1).cpu()
+                else:
+                    r["mask_bits"], r["mask_size"] = bits, (h, w)
+            results.append(r)
+        return results
+
+    # -- the step -------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, samples, tokenized, orig_sizes, sizes, dataset_names=None, captions=None):
+        from . import kernels
+        if isinstance(tokenized, (list, tuple)) and len(tokenized) and isinstance(tokenized[0], str):
+            if captions is None:
+                captions = list(tokenized)
+            tokenized = getattr(self.model, "detr", self.model).transformer._tokenize(list(tokenized), self.device)
+        if samples.tensors.shape[0] != self.batch:
+            raise ValueError(f"CapturedEvalStep was built for batches of {self.batch} images (got {samples.tensors.shape[0]})")
+        key = self.bucket_of(samples, tokenized)
+        orig, crop = self.check_sizes(key, orig_sizes, sizes)
+        if self.cluster_criterion is not None:
+            if dataset_names is None or captions is None:
+                raise ValueError("CapturedEvalStep with a cluster criterion needs the batch's dataset_names and captions")
+            self.cluster_criterion._static_ok()
+            self.cluster_criterion.eval()
+        if self.model.training:
+            self.model.eval()
+        ent = self._buckets.get(key)
+        if ent is None:
+            ent = self._buckets[key] = self._static_inputs(key)
+            while len(self._buckets) > self.max_graphs:
+                self._buckets.popitem(last=False)          # least recently used bucket: its graph, buffers and activation pool are released
+        if kernels.XDEC_FAILED and not self._xdec_off:
+            self._drop_xdec_graphs()
+        self._buckets.move_to_end(key)
+        self._fill(ent, samples, tokenized, orig, crop, dataset_names, captions)
+        if ent["graph"] is not None:
+            ent["graph"].replay()
+            self.replays += 1
+            # the results are handed out here: read the XCD-resident launch's status word first (one 4-byte read; it synchronises)
+            if not (ent["xdec"] and kernels.xdec_check(raise_on_failure=False)):
+                return self._results(ent, orig)
+            self._drop_xdec_graphs()                       # the launch's groups were not co-resident: per-op launches from now on, same batch again
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        side = self._side
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._forward(ent, key)                        # (the eval-mode decode checks, and if need be repeats, an XCD-resident launch by itself)
+            launches = kernels.XDEC_LAUNCHES
+            graph = torch.cuda.CUDAGraph()
+            with kernels.tables_beside_graph():
+                with torch.cuda.graph(graph, stream=side):
+                    self._forward(ent, key)
+            ent["graph"], ent["xdec"] = graph, kernels.XDEC_LAUNCHES != launches
+            self.captures += 1
+        torch.cuda.current_stream().wait_stream(side)
+        return self._results(ent, orig)
+
+    def _drop_xdec_graphs(self):
+        """kernels.XDEC_FAILED flipped: the graphs that hold an XCD-resident launch are void; every bucket captures again on its next step."""
+        self._xdec_off = True
+        for e in self._buckets.values():
+            e["graph"], e["xdec"] = None, False
 
     __call__ = step
 

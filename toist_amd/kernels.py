@@ -978,6 +978,50 @@ def mask_resize_pack(logits, max_size, crop, out_size, threshold=0.5):
     return bits
 
 
+def mask_resize_pack_batch(logits, max_size, table, cap_hw, capacity_words, out, threshold=0.5):
+    """mask_resize_pack for every image of a batch in one launch that reads its sizes from the device (include/toist_hip.h:
+    toist_mask_resize_pack_batch).  logits [B, Q, h0, w0] fp32 contiguous, table int64 [B, 4] = (crop_h, crop_w, h, w) on the device, out int64
+    [>= B * capacity_words]: image i's planes [Q, w_i, ceil(h_i/64)] start at word i * capacity_words.  No host read, no allocation: graph-capturable."""
+    B, Q, h0, w0 = logits.shape
+    if not logits.is_contiguous() or tuple(table.shape) != (B, 4) or not table.is_contiguous():
+        raise ValueError("mask_resize_pack_batch: contiguous [B, Q, h0, w0] logits and a contiguous int64 [B, 4] table")
+    if out.numel() < B * int(capacity_words):
+        raise ValueError(f"mask_resize_pack_batch: the output holds {out.numel()} words, {B} x {int(capacity_words)} are needed")
+    _lib.check(_lib.lib().toist_mask_resize_pack_batch(_p(logits, torch.float32), B, Q, h0, w0, int(max_size[0]), int(max_size[1]), _p(table, torch.int64),
+                                                       int(cap_hw[0]), int(cap_hw[1]), int(capacity_words), float(threshold), _p(out, torch.int64), _stream()),
+               "toist_mask_resize_pack_batch")
+    return out
+
+
+def postprocess(pred_logits, pred_boxes, sizes_dev, pred_isfinal=None, out=None):
+    """PostProcess in one launch (include/toist_hip.h: toist_postprocess).  pred_logits [B, Q, C] and pred_boxes [B, Q, 4] in bf16 or f32, pred_isfinal
+    [B, Q] (or [B, Q, 1]) optional, sizes_dev int64 [B, 2] = (h, w) ON THE DEVICE.  -> dict(scores f32 [B, Q], boxes f32 [B, Q, 4] (+ scores_refexp));
+    `out` = such a dict to write into (fixed addresses for a captured graph)."""
+    B, Q, C = pred_logits.shape
+    dev = pred_logits.device
+
+    def kind(t, what):
+        if t.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"postprocess: {what} must be bf16 or f32, got {t.dtype}")
+        return 1 if t.dtype == torch.bfloat16 else 0
+
+    if tuple(pred_boxes.shape) != (B, Q, 4) or tuple(sizes_dev.shape) != (B, 2):
+        raise ValueError("postprocess: pred_boxes [B, Q, 4] and sizes [B, 2] must match pred_logits [B, Q, C]")
+    if pred_isfinal is not None and pred_isfinal.numel() != B * Q:
+        raise ValueError("postprocess: pred_isfinal must hold one value per query")
+    if out is None:
+        out = {"scores": torch.empty(B, Q, dtype=torch.float32, device=dev), "boxes": torch.empty(B, Q, 4, dtype=torch.float32, device=dev)}
+        if pred_isfinal is not None:
+            out["scores_refexp"] = torch.empty(B, Q, dtype=torch.float32, device=dev)
+    logits, boxes = pred_logits.contiguous(), pred_boxes.contiguous()
+    final = pred_isfinal.contiguous() if pred_isfinal is not None else None
+    _lib.check(_lib.lib().toist_postprocess(_p(logits), kind(logits, "pred_logits"), _p(boxes), kind(boxes, "pred_boxes"), _p(final),
+                                            kind(final, "pred_isfinal") if final is not None else 0, _p(sizes_dev.contiguous(), torch.int64), B, Q, C,
+                                            _p(out["scores"], torch.float32), _p(out["boxes"], torch.float32),
+                                            _p(out["scores_refexp"], torch.float32) if final is not None else None, _stream()), "toist_postprocess")
+    return out
+
+
 def mask_pack(dense):
     """[n, h, w] bool / uint8 -> bit planes."""
     n, h, w = dense.shape

@@ -1,0 +1,492 @@
+"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedEvalStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
+core they share: bucket keys, the static image / text inputs of a bucket and the upload into them, the LRU of buckets, the eager pass followed by the
+capture, and the rule that voids captured graphs once the XCD-resident decoder launches have been turned off."""
+from collections import OrderedDict
+
+import torch
+
+from . import kernels
+from .misc import NestedTensor
+from .transformer import TokenizedText
+
+_NO_GRAPH = {"graph": None, "loss": None, "xdec": False}       # the capture state of a bucket entry: what _eager_then_capture sets and _void_graphs resets
+
+
+def _is_distributed():
+    return torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+
+
+def _pad_id(model):
+    return getattr(getattr(model, "detr", model).transformer.text_encoder.config, "pad_token_id", 1)
+
+
+def static_inputs(batch, Hp, Wp, Lp, pad_id, device, mask_fill=True):
+    """The fixed-address image and text inputs of one bucket: zero images under a mask of `mask_fill` (True = everything is padding until a batch is
+    uploaded), `pad_id` tokens under a zero attention mask."""
+    return {"samples": NestedTensor(torch.zeros(batch, 3, Hp, Wp, device=device), torch.full((batch, Hp, Wp), mask_fill, dtype=torch.bool, device=device)),
+            "tok": TokenizedText({"input_ids": torch.full((batch, Lp), pad_id, dtype=torch.int64, device=device),
+                                  "attention_mask": torch.zeros(batch, Lp, dtype=torch.int64, device=device)}),
+            "pad_id": pad_id, "mask_fill": mask_fill}
+
+
+def upload(ent, samples, tokenized):
+    """A batch's images and tokens into the static inputs of `ent` (on the current stream); a batch that does not fill the bucket finds the rest blank."""
+    img, msk = ent["samples"].tensors, ent["samples"].mask
+    H, W = samples.tensors.shape[-2:]
+    if (H, W) != tuple(img.shape[-2:]):
+        img.zero_()
+        msk.fill_(ent["mask_fill"])
+    img[:, :, :H, :W].copy_(samples.tensors, non_blocking=True)
+    msk[:, :H, :W].copy_(samples.mask, non_blocking=True)
+    ids, att = ent["tok"]["input_ids"], ent["tok"]["attention_mask"]
+    L = tokenized["input_ids"].shape[1]
+    if L != ids.shape[1]:
+        ids.fill_(ent["pad_id"])
+        att.zero_()
+    ids[:, :L].copy_(tokenized["input_ids"], non_blocking=True)
+    att[:, :L].copy_(tokenized["attention_mask"], non_blocking=True)
+
+
+class _CapturedStep:
+    """What the three steps share.  A subclass sets device (+ pad_hw, pad_tokens, max_graphs and _static_inputs(key) when it has more than one bucket)."""
+
+    def _init_capture_state(self, side=None, xdec_seen=False):
+        self._buckets = OrderedDict()          # (Hp, Wp, Lp) -> dict(static inputs and outputs of the bucket, **_NO_GRAPH), least recently used first
+        self._side = side                      # the stream of the eager-pass-then-capture; created on first use when None (no GPU is needed before)
+        self._xdec_seen = xdec_seen            # this object has already acted on kernels.XDEC_FAILED
+        self.captures = 0
+        self.replays = 0
+
+    def bucket_of(self, samples, tokenized):
+        H, W = samples.tensors.shape[-2:]
+        L = tokenized["input_ids"].shape[1]
+        up = lambda v, m: (int(v) + m - 1) // m * m
+        return up(H, self.pad_hw), up(W, self.pad_hw), up(L, self.pad_tokens)
+
+    def _void_graphs(self, force=False):
+        """Graphs captured before kernels.XDEC_FAILED flipped contain XCD-resident decoder launches, which are off from then on (kernels.xdec_check: an
+        expired spin, reached through harness.finite_or_exit on the NaN loss of that step or through CapturedEvalStep's own read): the first time this
+        object sees the flag, every graph it holds is dropped; the next step of each bucket runs eagerly on the per-op launches and is captured again."""
+        if force or (kernels.XDEC_FAILED and not self._xdec_seen):
+            self._xdec_seen = True
+            for e in self._buckets.values():
+                e.update(_NO_GRAPH)
+
+    def _entry(self, key):
+        """The bucket's entry, built on first use, as the most recently used of at most `max_graphs`."""
+        ent = self._buckets.get(key)
+        if ent is None:
+            ent = self._buckets[key] = self._static_inputs(key)
+            while len(self._buckets) > self.max_graphs:
+                self._buckets.popitem(last=False)          # least recently used bucket: its graph, buffers and activation pool are released
+        self._void_graphs()
+        self._buckets.move_to_end(key)
+        return ent
+
+    def _eager_then_capture(self, ent, body, reset=None, upload=None, capture=True):
+        """The first batch of a bucket: body() eagerly -- a real step -- on the object's own stream, the stream the graph is captured on right afterwards,
+        so that every per-stream cache of the launchers (split-K scratch, reduction arena) exists before the capture begins instead of being allocated
+        inside it; then the capture of the same call sequence on the static inputs (nothing executes during capture), with the pointer tables of grouped
+        launches beside the graph: filled once, not on every replay.  upload() runs first on that stream, reset() before each of the two passes.
+        -> what the eager body() returned; what the captured one returned stays in ent["loss"]."""
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        side = self._side
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            if upload is not None:
+                upload()
+            if reset is not None:
+                reset()
+            result = body()
+            if capture:
+                if reset is not None:
+                    reset()
+                launches = kernels.XDEC_LAUNCHES
+                graph = torch.cuda.CUDAGraph()
+                with kernels.tables_beside_graph():
+                    with torch.cuda.graph(graph, stream=side):
+                        ent["loss"] = body()
+                ent["graph"], ent["xdec"] = graph, kernels.XDEC_LAUNCHES != launches      # xdec: the graph holds an XCD-resident launch
+                self.captures += 1
+        torch.cuda.current_stream().wait_stream(side)
+        return result
+
+
+class CapturedTrainStep(_CapturedStep):
+    """The reference's training step (engine.py:54-101: encode -> decode -> SetCriterion -> weighted sum -> backward -> clip + AdamW + EMA)
+    replayed from hipGraphs, one per input-shape BUCKET, with real variable-size batches.
+
+    The reference resizes images to 480..800 x <= 1333 (datasets/tdod.py:305-319) and pads a batch to its largest image
+    (util/misc.py:185-209); captions are padded to the longest of the batch.  A captured graph has static shapes, so the IMAGES are padded a
+    little further -- height / width up to multiples of `pad_hw` -- with the padding masked out exactly as the reference masks its own
+    padding (NestedTensor.mask): extra masked pixels change no result.  Caption length is NOT rounded up by default (`pad_tokens=1`):
+    padded token positions are masked in every attention, but `loss_contrastive_align` takes its log-sum-exp over EVERY token column
+    without an attention mask (/root/reference/models/mdetr.py:646-663), so extra pad tokens would change that loss and its gradients.
+    `pad_tokens > 1` is an explicit trade: fewer graphs for captions of mixed lengths, and the contrastive term then equals the
+    reference's on a batch whose longest caption has the padded length (the detection losses are unaffected).
+    One graph is captured per bucket (Hp, Wp, Lp) on first use and kept in an LRU of `max_graphs`;
+    targets travel through matcher.StaticTargets (fixed-address device image, any number of targets per image up to
+    `max_targets_per_image`), dropout masks change per replay through the device seed word, learning rates are re-read from the
+    optimizer's device table (`optimizer.sync_hyperparams()` after changing them).
+
+    step(samples, tokenized, targets, positive_map) -> total loss (device scalar, valid until the next step of the same bucket).
+    The FIRST step of a new bucket runs eagerly (it is a real training step) and the graph is captured right after it, without
+    executing anything; later steps of that bucket are one host-to-device copy of the inputs + one graph launch.
+    Single process per GPU; with torch.distributed active the step falls back to the eager path (collectives are not captured).
+    Forward passes made between steps (validation) must run under torch.no_grad(): a grad-enabled forward that never sees backward()
+    leaves AccumulateGrad nodes bound to the stream it ran on, and torch's autograd engine would pull that stream into the next capture."""
+
+    def __init__(self, model, criterion, optimizer, weight_dict, *, batch, max_targets_per_image=16, pad_hw=64, pad_tokens=1, max_graphs=4,
+                 contrastive=None, device=None):
+        self.model, self.criterion, self.optimizer, self.weight_dict = model, criterion, optimizer, weight_dict
+        self.batch, self.max_t = int(batch), int(max_targets_per_image)
+        self.pad_hw, self.pad_tokens, self.max_graphs = int(pad_hw), int(pad_tokens), int(max_graphs)
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        det = getattr(model, "detr", model)
+        self.num_queries = det.query_embed.weight.shape[0]
+        self.contrastive = bool(getattr(det, "contrastive_align_loss", False)) if contrastive is None else bool(contrastive)
+        # configs[2]: the ground-truth masks travel in the bucket's StaticTargets, zero-padded to the bucket's (Hp, Wp).  The reference pads them to the
+        # batch's largest image (util/misc.py:185-209) and resizes the [ceil(H/4), ceil(W/4)] predictions to that size (mdetr.py:843):
+        # StaticTargets.valid_hw carries the batch's own sizes to the mask-loss kernels, which map that corner of the prediction onto that corner of
+        # the targets and normalise by H * W -- the same mask losses in any bucket (round 6).
+        self.masks = "masks" in getattr(criterion, "losses", ())
+        self._init_capture_state(side=torch.cuda.Stream(device=self.device), xdec_seen=kernels.XDEC_FAILED)
+        if kernels.SEED_DEV is None:
+            kernels.SEED_DEV = torch.zeros(1, dtype=torch.int64, device=self.device)
+        from . import engine
+        engine.REUSE_GRAD_BUFFERS = True       # the loop owns the gradients: one flat buffer per program, shared by every bucket's graph and the eager steps
+
+    # -- helpers ------------------------------------------------------------------------------------------------------------------
+    def _static_inputs(self, key):
+        from .matcher import StaticTargets
+        Hp, Wp, Lp = key
+        return {**static_inputs(self.batch, Hp, Wp, Lp, _pad_id(self.model), self.device), **_NO_GRAPH,
+                "targets": StaticTargets(self.batch, self.max_t, self.num_queries, 256, self.device, mask_hw=(Hp, Wp) if self.masks else None)}
+
+    def _fill(self, ent, samples, tokenized, targets, positive_map, packed):
+        B = samples.tensors.shape[0]
+        if B != self.batch:
+            raise ValueError(f"CapturedTrainStep was built for batches of {self.batch} images (got {B})")
+        upload(ent, samples, tokenized)
+        st = ent["targets"]
+        if packed is None:
+            host_t = [{k_: (v.cpu() if torch.is_tensor(v) else v) for k_, v in t.items()} for t in targets]
+            masks = self.criterion.token_masks_host(host_t, tokenized) if self.contrastive else None
+            st.load(host_t, positive_map.cpu() if torch.is_tensor(positive_map) else positive_map, masks)
+        else:
+            st.load_packed(packed)
+
+    def _fwd_bwd_opt(self, ent):
+        from .mdetr import weighted_total
+        kernels.SEED_DEV.add_(1000003)
+        mc = self.model(ent["samples"], ent["tok"], encode_and_save=True)
+        out = self.model(ent["samples"], ent["tok"], encode_and_save=False, memory_cache=mc)
+        losses = self.criterion(mc, out, ent["targets"], None, None)
+        total = weighted_total(losses, self.weight_dict)
+        total.backward()
+        self.optimizer.step()
+        return total
+
+    # -- the step -------------------------------------------------------------------------------------------------------------------
+    def step(self, samples, tokenized, targets=None, positive_map=None, packed=None):
+        ent = self._entry(self.bucket_of(samples, tokenized))
+        self._fill(ent, samples, tokenized, targets, positive_map, packed)
+        if ent["graph"] is not None:
+            ent["graph"].replay()
+            self.replays += 1
+            if hasattr(self.optimizer, "note_replayed_step"):
+                self.optimizer.note_replayed_step()      # copies of the weights that the captured tail does not rewrite are stale now
+            return ent["loss"]
+        return self._eager_then_capture(ent, lambda: self._fwd_bwd_opt(ent), reset=lambda: self.optimizer.zero_grad(set_to_none=True),
+                                        capture=not _is_distributed())       # (collectives are not captured)
+
+    __call__ = step
+
+
+class CapturedEvalStep(_CapturedStep):
+    """The reference's evaluation body (engine.py:253-342: encode -> optional prototype choice -> decode -> PostProcess -> optional PostProcessSegm) replayed
+    from hipGraphs, one per input-shape BUCKET (Hp, Wp, Lp) -- the padding rules and the LRU of `max_graphs` are CapturedTrainStep's; the batch size is
+    fixed; everything runs under torch.no_grad() with the model in eval().
+
+    step(samples, tokenized, orig_sizes, sizes, dataset_names=None, captions=None) -> results: a list of dicts with the keys, dtypes and shapes of
+    PostProcess and PostProcessSegm(packed=True): "scores" f32 [Q], "labels" int64 [Q], "boxes" f32 [Q, 4] (+ "scores_refexp" when the model emits
+    pred_isfinal), with a mask head "mask_bits" int64 [Q, w_i, ceil(h_i/64)] + "mask_size" (h_i, w_i) -- TDODCocoEvaluator.update takes them unchanged.
+    Every tensor is a view into the bucket's output buffers, valid until the next step of that bucket.  dense_masks=True replaces the packed planes by
+    the reference's "masks" bool [Q, 1, h_i, w_i] on the host.
+    orig_sizes / sizes: (h, w) per image as HOST values (lists, or host tensors): they travel to the device in one fixed-address int64 table per bucket
+    that the two post-processing kernels read (csrc/postproc.hip, csrc/evalmask.hip), so nothing is read back before the launch.
+
+    The FIRST batch of a bucket runs eagerly on the object's side stream and the graph is captured right after (inside kernels.tables_beside_graph());
+    later batches of that bucket are one upload of the inputs + one graph launch.
+    Masks: the planes of image i start at word i * capacity of one buffer per bucket, capacity = Q * max_orig_hw[1] * ceil(max_orig_hw[0] / 64); an
+    image larger than `max_orig_hw` raises ValueError before anything is launched.  In a padded bucket pred_masks cover (Hp, Wp), so the FIRST resize
+    target is the bucket's (Hp, Wp), not the batch's largest image, and the crop is each image's `size` -- what the reference computes on a batch
+    whose largest image is Hp x Wp (models/postprocessors.py:86-107).
+    Prototype choice: with a `cluster_criterion` it runs inside the graph (ClusterCriterion.infer_choice_static on a DistillTables image filled by
+    pack_eval from the tokenized captions -- which must answer char_to_token --, the caption strings and the dataset names); the preconditions are
+    ClusterCriterion._static_ok's.  k-means moves cluster_centers in place, as the reference's memory_cluster does.
+    XCD-resident decoder: when the captured graph holds that launch, its status word is read after every replay (kernels.xdec_check: the one
+    synchronisation of a step, at the point where the results are handed out); a failed launch drops every graph, and the same batch runs again on the
+    per-op launches and is captured again -- inference has no state a failed step could have poisoned.
+    Data parallelism: the forward holds no collective, every rank evaluates its own shard, so the step stays captured under torch.distributed."""
+
+    def __init__(self, model, cluster_criterion=None, *, batch, masks=None, max_orig_hw=None, pad_hw=64, pad_tokens=1, max_graphs=4, dense_masks=False,
+                 threshold=0.5, device=None):
+        self.model, self.cluster_criterion = model, cluster_criterion
+        self.batch, self.pad_hw, self.pad_tokens, self.max_graphs = int(batch), int(pad_hw), int(pad_tokens), int(max_graphs)
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        det = getattr(model, "detr", model)
+        self.num_queries = det.query_embed.weight.shape[0]
+        self.masks = hasattr(model, "detr") if masks is None else bool(masks)
+        self.dense_masks, self.threshold = bool(dense_masks), float(threshold)
+        if self.masks and max_orig_hw is None:
+            raise ValueError("CapturedEvalStep with a mask head needs max_orig_hw = the largest original (h, w) it has to hold")
+        self.max_orig_hw = (int(max_orig_hw[0]), int(max_orig_hw[1])) if max_orig_hw is not None else None
+        self.capacity_words = self.num_queries * self.max_orig_hw[1] * ((self.max_orig_hw[0] + 63) // 64) if self.masks else 0
+        self._init_capture_state()
+
+    # -- helpers ------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _pairs(v):
+        rows = v.tolist() if torch.is_tensor(v) else [(r.tolist() if torch.is_tensor(r) else r) for r in v]
+        return [(int(r[0]), int(r[1])) for r in rows]
+
+    def check_sizes(self, key, orig_sizes, sizes):
+        """Host check of a batch's sizes against the bucket and the mask capacity (ValueError; nothing has been launched).  -> (orig, sizes) as int pairs."""
+        orig, crop = self._pairs(orig_sizes), self._pairs(sizes)
+        if len(orig) != self.batch or len(crop) != self.batch:
+            raise ValueError(f"CapturedEvalStep was built for batches of {self.batch} images (got {len(orig)} original sizes, {len(crop)} sizes)")
+        for (h, w), (ch, cw) in zip(orig, crop):
+            if h <= 0 or w <= 0 or ch <= 0 or cw <= 0 or ch > key[0] or cw > key[1]:
+                raise ValueError(f"CapturedEvalStep: an image of size {ch} x {cw} (original {h} x {w}) does not fit the padded batch {key[0]} x {key[1]}")
+            if self.masks and (h > self.max_orig_hw[0] or w > self.max_orig_hw[1]):
+                raise ValueError(f"CapturedEvalStep: an original size of {h} x {w} exceeds max_orig_hw = {self.max_orig_hw[0]} x {self.max_orig_hw[1]} "
+                                 "(the capacity of the mask planes)")
+        return orig, crop
+
+    def _static_inputs(self, key):
+        Hp, Wp, Lp = key
+        dev, B = self.device, self.batch
+        ent = {**static_inputs(B, Hp, Wp, Lp, _pad_id(self.model), dev), **_NO_GRAPH,
+               # rows 0 .. 2B: (h, w) originals for toist_postprocess; rows 2B .. 6B: (crop_h, crop_w, h, w) for toist_mask_resize_pack_batch
+               "sizes_host": torch.ones(6 * B, dtype=torch.int64).pin_memory(), "sizes": torch.ones(6 * B, dtype=torch.int64, device=dev),
+               "sizes_event": None, "out": None, "tables": None,
+               "bits": torch.zeros(B * self.capacity_words, dtype=torch.int64, device=dev) if self.masks else None}
+        if self.cluster_criterion is not None:
+            from .distill import DistillTables
+            ent["tables"] = DistillTables(B, Lp, dev, pronoun_side=True)
+        return ent
+
+    def _fill(self, ent, samples, tokenized, orig, crop, dataset_names, captions):
+        B = self.batch
+        upload(ent, samples, tokenized)
+        if ent["sizes_event"] is not None:
+            ent["sizes_event"].synchronize()           # the previous upload has left the staging buffer
+        host = ent["sizes_host"]
+        host[:2 * B] = torch.tensor(orig, dtype=torch.int64).view(-1)
+        host[2 * B:] = torch.tensor([c + o for c, o in zip(crop, orig)], dtype=torch.int64).view(-1)
+        ent["sizes"].copy_(host, non_blocking=True)
+        ent["sizes_event"] = torch.cuda.Event()
+        ent["sizes_event"].record()
+        if ent["tables"] is not None:
+            tb = ent["tables"]
+            if tb._event is not None:
+                tb._event.synchronize()
+            tb.load_packed(tb.pack_eval(tokenized, captions, dataset_names, out=tb._host))
+            tb._event = torch.cuda.Event()
+            tb._event.record()
+
+    def _forward(self, ent, key):
+        """The launches of one batch on the bucket's static inputs (eagerly, and once more under capture)."""
+        B = self.batch
+        mc = self.model(ent["samples"], ent["tok"], encode_and_save=True)
+        if self.cluster_criterion is not None:
+            mc = self.cluster_criterion.infer_choice_static(mc, ent["tables"])
+            if ent.get("img_memory_mod") is None:                # the memory with the chosen prototypes, copied to a fixed buffer: readable after any step
+                ent["img_memory_mod"] = torch.empty_like(mc["img_memory_mod"])
+            ent["img_memory_mod"].copy_(mc["img_memory_mod"])
+        outputs = self.model(ent["samples"], ent["tok"], encode_and_save=False, memory_cache=mc)
+        ent["out"] = kernels.postprocess(outputs["pred_logits"], outputs["pred_boxes"], ent["sizes"][:2 * B].view(B, 2), outputs.get("pred_isfinal"),
+                                         out=ent["out"])
+        if self.masks:
+            logits = outputs["pred_masks"].squeeze(2).float().contiguous()                # [B, Q, h0, w0]; they cover the padded (Hp, Wp)
+            kernels.mask_resize_pack_batch(logits, (key[0], key[1]), ent["sizes"][2 * B:].view(B, 4), self.max_orig_hw, self.capacity_words, ent["bits"],
+                                           self.threshold)
+
+    def _results(self, ent, orig):
+        from .postprocessors import PostProcess
+        out, B, Q = ent["out"], self.batch, self.num_queries
+        lkey = (str(self.device), B, Q)
+        labels = PostProcess._LABELS.get(lkey)
+        if labels is None:
+            labels = PostProcess._LABELS[lkey] = torch.ones(B, Q, dtype=torch.int64, device=self.device)
+        results = []
+        for i, (h, w) in enumerate(orig):
+            r = {"scores": out["scores"][i], "labels": labels[i], "boxes": out["boxes"][i]}
+            if "scores_refexp" in out:
+                r["scores_refexp"] = out["scores_refexp"][i]
+            if self.masks:
+                words = kernels.mask_words(h)
+                bits = ent["bits"][i * self.capacity_words:i * self.capacity_words + Q * w * words].view(Q, w, words)
+                if self.dense_masks:
+                    r["masks"] = kernels.mask_unpack(bits, h, w).unsqueeze(1).cpu()
+                else:
+                    r["mask_bits"], r["mask_size"] = bits, (h, w)
+            results.append(r)
+        return results
+
+    # -- the step -------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, samples, tokenized, orig_sizes, sizes, dataset_names=None, captions=None):
+        if isinstance(tokenized, (list, tuple)) and len(tokenized) and isinstance(tokenized[0], str):
+            if captions is None:
+                captions = list(tokenized)
+            tokenized = getattr(self.model, "detr", self.model).transformer._tokenize(list(tokenized), self.device)
+        if samples.tensors.shape[0] != self.batch:
+            raise ValueError(f"CapturedEvalStep was built for batches of {self.batch} images (got {samples.tensors.shape[0]})")
+        key = self.bucket_of(samples, tokenized)
+        orig, crop = self.check_sizes(key, orig_sizes, sizes)
+        if self.cluster_criterion is not None:
+            if dataset_names is None or captions is None:
+                raise ValueError("CapturedEvalStep with a cluster criterion needs the batch's dataset_names and captions")
+            self.cluster_criterion._static_ok()
+            self.cluster_criterion.eval()
+        if self.model.training:
+            self.model.eval()
+        ent = self._entry(key)
+        self._fill(ent, samples, tokenized, orig, crop, dataset_names, captions)
+        if ent["graph"] is not None:
+            ent["graph"].replay()
+            self.replays += 1
+            # the results are handed out here: read the XCD-resident launch's status word first (one 4-byte read; it synchronises)
+            if not (ent["xdec"] and kernels.xdec_check(raise_on_failure=False)):
+                return self._results(ent, orig)
+            self._void_graphs(force=True)                  # the launch's groups were not co-resident: per-op launches from now on, same batch again
+        # (the eval-mode decode checks, and if need be repeats, an XCD-resident launch of the eager pass by itself)
+        self._eager_then_capture(ent, lambda: self._forward(ent, key))
+        return self._results(ent, orig)
+
+    __call__ = step
+
+
+class CapturedDistillStep(_CapturedStep):
+    """The reference's distillation step (engine.py:152-204: teacher encode -> memory-bank update + prototypes -> teacher decode -> student encode ->
+    prototype of 'something' -> student decode -> paired SetCriterion with softkd / nsthl2 + cluster losses -> backward -> clip + AdamW + EMA of both
+    models) replayed from ONE hipGraph for ANY batch of a fixed shape (round 6).
+
+    What used to tie a captured graph to its batch -- per-image target counts (LSAP problem sizes (Q - c)^2, pair tables), the grouping of the images by
+    task (k-means groups, one memory-bank LSAP per task), the token tables of the captions (noun spans, the word 'something') -- now lives in
+    fixed-address device images that `step()` refills before every replay: matcher.StaticTargets (one per side) and distill.DistillTables (one per
+    side, attached as StaticTargets.distill); the criterion and the cluster criterion dispatch on them (SetCriterion._forward_pair_static,
+    ClusterCriterion.update_memory_static / forward_static).
+
+    step(batch) with batch = what util/misc.collate_fn delivers for (noun, pronoun) pairs (harness.synthetic_distill_batch): dict(samples=[..] * 2,
+    tokenized=[..] * 2 (BatchEncodings with char_to_token), targets=[..] * 2, captions=[..] * 2, positive_map=[..] * 2) -> total loss (device scalar).
+    The first step runs eagerly (a real training step) and is captured right after; later steps = the H2D copies of the inputs + one graph launch.
+    Requirements (checked): one process, every memory bank full, nearest-replacement bank updates, both sides with the same number of targets per
+    image (the reference's pairs share their boxes), images / captions of the constructor's shape."""
+
+    def __init__(self, model, model_noun, criterion, cluster_criterion, optimizers, weight_dict, *, batch, image_hw, tokens, max_targets_per_image=16, device=None,
+                 stream=None):
+        """stream: the HIP stream the steps run (and the graph is captured) on; pass the stream earlier eager steps of the same models ran on, if any -- the programs'
+        reused gradient buffers and the launchers' per-stream scratch must not change streams between eager steps and the capture."""
+        from . import engine
+        from .distill import DistillTables
+        from .matcher import StaticTargets
+        self.model, self.model_noun, self.criterion, self.cluster_criterion = model, model_noun, criterion, cluster_criterion
+        self.optimizers, self.weight_dict = list(optimizers), weight_dict
+        self.B, self.hw, self.L = int(batch), (int(image_hw[0]), int(image_hw[1])), int(tokens)
+        dev = self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        det = getattr(model, "detr", model)
+        Q = det.query_embed.weight.shape[0]
+        self.contrastive = bool(getattr(det, "contrastive_align_loss", False))
+        self.sides = []
+        for pronoun in (False, True):
+            st = StaticTargets(self.B, int(max_targets_per_image), Q, 256, dev)
+            st.distill = DistillTables(self.B, self.L, dev, pronoun_side=pronoun)
+            # (every batch has exactly this shape and overwrites the whole mask)
+            self.sides.append({**static_inputs(self.B, *self.hw, self.L, _pad_id(model), dev, mask_fill=False), "targets": st})
+        self._init_capture_state(side=stream if stream is not None else torch.cuda.Stream(device=dev))
+        self._ent = self._buckets[(*self.hw, self.L)] = dict(_NO_GRAPH)        # the one bucket
+        if kernels.SEED_DEV is None:
+            kernels.SEED_DEV = torch.zeros(1, dtype=torch.int64, device=dev)
+        engine.REUSE_GRAD_BUFFERS = True
+
+    def pack(self, batch):
+        """Host half of a step (no device work, no synchronisation when the batch's targets are host tensors: run it in the loader): the pinned images of both
+        sides' StaticTargets and DistillTables, next to the batch's image / token tensors.  step(packed=...) consumes it."""
+        if [len(t["boxes"]) for t in batch["targets"][0]] != [len(t["boxes"]) for t in batch["targets"][1]]:
+            raise ValueError("softkd needs the same number of targets on the noun and the pronoun side of every pair")
+        out = []
+        for i, side in enumerate(self.sides):
+            samples, tok, targets = batch["samples"][i], batch["tokenized"][i], batch["targets"][i]
+            if tuple(samples.tensors.shape) != (self.B, 3, *self.hw) or tuple(tok["input_ids"].shape) != (self.B, self.L):
+                raise ValueError(f"CapturedDistillStep was built for {self.B} x 3 x {self.hw[0]} x {self.hw[1]} images and {self.L}-token captions")
+            host_t = [{k_: (v.cpu() if torch.is_tensor(v) else v) for k_, v in t.items()} for t in targets]
+            pm = batch["positive_map"][i]
+            masks = self.criterion.token_masks_host(host_t, tok) if self.contrastive else None
+            out.append({"samples": samples, "tok": tok, "targets": side["targets"].pack(host_t, pm.cpu() if torch.is_tensor(pm) else pm, masks),
+                        "tables": side["targets"].distill.pack(tok, host_t, batch["captions"][i])})
+        return out
+
+    def _fill(self, packed):
+        for side, pk in zip(self.sides, packed):
+            upload(side, pk["samples"], pk["tok"])
+            side["targets"].load_packed(pk["targets"])
+            side["targets"].distill.load_packed(pk["tables"])
+
+    def _fwd_bwd_opt(self):
+        """One step.  The backward pass is issued in TWO calls -- the teacher's total (the noun_ keys) first, then everything else (sth_, softkd, nsthl2, cluster:
+        the student's) -- which changes no gradient (the two models' graphs are disjoint: the teacher enters the cross losses detached, mdetr.py:520-599, 668-781)
+        but lets a captured step run the teacher's backward beside the softkd assignment problems, which occupy 24 CUs for ~3.6 ms on a side stream
+        (SetCriterion._forward_pair_static)."""
+        from .harness import distillation_losses
+        from .mdetr import weighted_total
+        kernels.SEED_DEV.add_(1000003)
+        noun, sth = self.sides
+        static = {"samples": [noun["samples"], sth["samples"]], "targets": [noun["targets"], sth["targets"]], "captions": [None, None],
+                  "tokenized": [noun["tok"], sth["tok"]], "positive_map": [None, None]}
+        self.criterion.defer_pair_join = True          # the softkd block may go to a side stream: this method joins it (below) before the student's total
+        try:
+            losses = distillation_losses(self.model, self.model_noun, self.criterion, self.cluster_criterion, static)
+        finally:
+            self.criterion.defer_pair_join = False
+        w_noun = {k_: v for k_, v in self.weight_dict.items() if k_.startswith("noun_")}
+        w_rest = {k_: v for k_, v in self.weight_dict.items() if not k_.startswith("noun_")}
+        total_noun = weighted_total(losses, w_noun)
+        total_noun.backward()
+        join = getattr(losses, "join", None)
+        if join is not None:
+            torch.cuda.current_stream().wait_stream(join)
+        total_rest = weighted_total(losses, w_rest)
+        total_rest.backward()
+        for o in self.optimizers:
+            o.step()
+        return (total_noun + total_rest).detach()
+
+    def _zero_grad(self):
+        for o in self.optimizers:
+            o.zero_grad(set_to_none=True)
+
+    def step(self, batch=None, packed=None):
+        batch = packed if packed is not None else self.pack(batch)
+        if _is_distributed():
+            raise RuntimeError("CapturedDistillStep is single-process (the memory-bank queue all_gathers rows across ranks: collectives are not captured)")
+        self._void_graphs()
+        ent = self._ent
+        if ent["graph"] is None:
+            return self._eager_then_capture(ent, self._fwd_bwd_opt, reset=self._zero_grad, upload=lambda: self._fill(batch))
+        side = self._side                                  # (unlike the bucketed steps, upload and replay stay on the stream of the capture)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._fill(batch)
+            ent["graph"].replay()
+        torch.cuda.current_stream().wait_stream(side)
+        self.replays += 1
+        for o in self.optimizers:
+            if hasattr(o, "note_replayed_step"):
+                o.note_replayed_step()
+        return ent["loss"]
+
+    __call__ = step

@@ -364,7 +364,13 @@ TOIST_API int toist_mask_loss_bwd_compact(const float* pred, const int32_t* pred
  * address of tensor i's fp32 gradient (0 = no gradient this step: the tensor is only EMA-averaged).
  * Work is cut into chunks of toist_opt_chunk_elems() elements: chunks[2*b] = tensor index, chunks[2*b+1] = chunk
  * index inside that tensor.  State (step count, clip coefficient, bias corrections) stays on the device so a
- * captured hipGraph replays the tail unchanged; learning rates are read from `groups` at run time. */
+ * captured hipGraph replays the tail unchanged; learning rates are read from `groups` at run time.
+ * Guard (opt-in): toist_opt_finish_norm_guarded SKIPS a step whose gradient norm is not finite (NaN / inf gradients, or an fp32
+ * sum of squares that overflows: finite gradients of ~1e19 and above) or that a veto word objects to -- device words read at run
+ * time through two pointer tables: int32 words veto when non-zero (a kernel's failure status), fp32 words when not finite (the
+ * loss).  A skipped step sets state.skipped, does not advance state.step, and every toist_opt_adamw_ema[_blocks] launch that reads
+ * that state returns without writing: parameters, moments, averages and bf16 copies stay bit for bit as they were.  The plain
+ * toist_opt_finish_norm never skips (it clears state.skipped): a non-finite norm then reaches the parameters, as in torch. */
 typedef struct toist_opt_tensor {
     float* p;                 /* fp32 master parameter (or the EMA source for buffers / frozen parameters)            */
     float* m;                 /* exp_avg     (NULL: never updated by the optimizer)                                   */
@@ -387,9 +393,13 @@ typedef struct toist_opt_state {
     float grad_norm;          /* total 2-norm of all gradients before clipping                                        */
     float bias1;              /* 1 - beta1^step                                                                       */
     float bias2_sqrt;         /* sqrt(1 - beta2^step)                                                                 */
-    int32_t step;             /* optimizer steps taken (incremented by toist_opt_finish_norm)                         */
-    int32_t reserved[3];
+    int32_t step;             /* optimizer steps APPLIED (incremented by toist_opt_finish_norm[_guarded]; not by a skipped step) */
+    int32_t skipped;          /* 1: the last finish-norm launch vetoed the step (toist_opt_adamw_ema then returns at once), else 0 */
+    int32_t skipped_total;    /* vetoed steps since the state was zeroed                                              */
+    int32_t veto_mask;        /* why the last step was vetoed: bit 0 = grad_norm not finite, bit 1+i = integer veto word i
+                                 non-zero, bit 9+j = float veto word j not finite; 0 after an applied guarded step   */
 } toist_opt_state;            /* 32 bytes */
+#define TOIST_OPT_MAX_VETO 8  /* veto words of each kind a guarded finish-norm launch reads                           */
 
 /* ---- attention cores (head dim 32; csrc/attn2.hip; the first-generation toist_attn_fwd / toist_attn_bwd of rounds 1-4 were removed in round 5).  Operands: per-head column
  * slices of [B*S, ld*] bf16 buffers), flash-style only: nothing score-shaped is stored, the key count is unbounded.
@@ -669,6 +679,9 @@ TOIST_API int toist_splitk_reduce_batch(const toist_reduce_desc* descs, int n, v
 TOIST_API int toist_opt_chunk_elems(void);
 TOIST_API int toist_opt_sqnorm(const toist_opt_tensor* table, const int64_t* grads, const int32_t* chunks, int n_chunks, float* partial, void* stream);
 TOIST_API int toist_opt_finish_norm(const float* partial, int n_chunks, float max_norm, float beta1, float beta2, toist_opt_state* state, void* stream);
+/* veto_i32 / veto_f32: DEVICE tables of n_veto_i32 / n_veto_f32 (each 0 .. TOIST_OPT_MAX_VETO) device addresses; NULL only with a count of 0 */
+TOIST_API int toist_opt_finish_norm_guarded(const float* partial, int n_chunks, float max_norm, float beta1, float beta2, toist_opt_state* state,
+                        const int32_t* const* veto_i32, int n_veto_i32, const float* const* veto_f32, int n_veto_f32, void* stream);
 TOIST_API int toist_opt_adamw_ema(const toist_opt_tensor* table, const int64_t* grads, const int32_t* chunks, int n_chunks,
                         const toist_opt_group* groups, const toist_opt_state* state, float beta1, float beta2, float eps,
                         float ema_decay, void* stream);

@@ -170,6 +170,7 @@ _SIGNATURES = {
     "toist_opt_chunk_elems": ([], ctypes.c_int),
     "toist_opt_sqnorm": ([c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "toist_opt_finish_norm": ([c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p], ctypes.c_int),
+    "toist_opt_finish_norm_guarded": ([c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p], ctypes.c_int),
     "toist_opt_adamw_ema": ([c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_void_p], ctypes.c_int),
     "toist_opt_adamw_ema_blocks": ([c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int32, c_void_p], ctypes.c_int),
     "toist_mask_resize_pack": ([c_void_p] + [c_int32] * 9 + [c_float, c_void_p, c_void_p], ctypes.c_int),

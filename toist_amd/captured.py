@@ -56,6 +56,47 @@ class _CapturedStep:
         self._xdec_seen = xdec_seen            # this object has already acted on kernels.XDEC_FAILED
         self.captures = 0
         self.replays = 0
+        self.skipped = 0                       # steps that resolve_skipped() found vetoed
+        self._guard_opts, self._loss_word, self._xdec_bit = [], None, {}
+
+    def _init_guard(self, optimizers):
+        """The device-side finite-loss guard: when EVERY optimizer of the step is a FusedClipAdamWEMA(skip_nonfinite=True), the step owns a one-element
+        fp32 loss word (the subclass copies the total loss into it before the optimizers' step(): the reference's math.isfinite(loss_value),
+        engine.py:82-85, on the device -- the gradient norm alone is not enough, some analytic backward kernels turn a NaN loss into finite gradients,
+        sign(NaN) for one) registered as a float veto, and the sticky status word of the device's XCD-resident decoder launches registered as an integer
+        veto.  The status word is rank-local: under torch.distributed only the norm and the loss can veto, which are the same on every rank after the
+        all-reduce -- a rank that skipped alone would leave the replicas with different weights."""
+        opts = list(optimizers)
+        if not opts or not all(getattr(o, "skip_nonfinite", False) for o in opts):
+            return
+        self._guard_opts = opts
+        self._loss_word = torch.zeros(1, dtype=torch.float32, device=self.device)
+        for o in opts:
+            o.add_veto(self._loss_word)
+        if not _is_distributed():
+            index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+            ctl = kernels._xdec_ctl(torch.device("cuda", index))          # allocated here, eagerly: never from a capturing graph's pool
+            if ctl is not None:
+                for o in opts:
+                    self._xdec_bit[id(o)] = o.add_veto(ctl[-1:])                   # the sticky status word
+
+    def resolve_skipped(self):
+        """Was the last step applied?  Reads the optimizers' device state (synchronises) -> None: it was; "xdec": it was skipped because an XCD-resident
+        decoder launch had reported failure -- kernels.xdec_check has been called (the status word is cleared, the launches are off for the process),
+        the next step() drops the graphs and runs the SAME batch, which the caller passes again, on the per-op launches; "nonfinite": it was skipped
+        because the loss or the gradient norm was not finite (or a veto word of the caller's objected) -- go on with the next batch.  A skipped step
+        has changed no parameter, moment, average or step count; `self.skipped` counts them.  Always None without the guard (an optimizer built
+        without skip_nonfinite=True): then a bad step has already been applied."""
+        why = None
+        for o in self._guard_opts:
+            st = o.device_state()
+            if st["skipped"]:
+                why = "xdec" if st["veto_mask"] & self._xdec_bit.get(id(o), 0) or why == "xdec" else "nonfinite"
+        if why is not None:
+            self.skipped += 1
+        if why == "xdec":
+            kernels.xdec_check(raise_on_failure=False)
+        return why
 
     def bucket_of(self, samples, tokenized):
         H, W = samples.tensors.shape[-2:]
@@ -135,7 +176,13 @@ class CapturedTrainStep(_CapturedStep):
     executing anything; later steps of that bucket are one host-to-device copy of the inputs + one graph launch.
     Single process per GPU; with torch.distributed active the step falls back to the eager path (collectives are not captured).
     Forward passes made between steps (validation) must run under torch.no_grad(): a grad-enabled forward that never sees backward()
-    leaves AccumulateGrad nodes bound to the stream it ran on, and torch's autograd engine would pull that stream into the next capture."""
+    leaves AccumulateGrad nodes bound to the stream it ran on, and torch's autograd engine would pull that stream into the next capture.
+
+    A bad step: backward and optimizer.step() are inside the graph, so by the time the host can read the loss the update has run.  With a plain
+    optimizer a non-finite loss or gradient, or a failed XCD-resident decoder launch (whose results are NaN), has then been written into the weights,
+    both moments and the EMA: that is fatal, restore from a checkpoint.  With FusedClipAdamWEMA(skip_nonfinite=True) the tail skips such a step on
+    the device and leaves all training state as it was; the loop asks afterwards:
+        loss = cap.step(...); why = cap.resolve_skipped()      # None | "nonfinite" (go on) | "xdec" (cap.step(the same batch) once more)"""
 
     def __init__(self, model, criterion, optimizer, weight_dict, *, batch, max_targets_per_image=16, pad_hw=64, pad_tokens=1, max_graphs=4,
                  contrastive=None, device=None):
@@ -156,6 +203,7 @@ class CapturedTrainStep(_CapturedStep):
             kernels.SEED_DEV = torch.zeros(1, dtype=torch.int64, device=self.device)
         from . import engine
         engine.REUSE_GRAD_BUFFERS = True       # the loop owns the gradients: one flat buffer per program, shared by every bucket's graph and the eager steps
+        self._init_guard([optimizer])
 
     # -- helpers ------------------------------------------------------------------------------------------------------------------
     def _static_inputs(self, key):
@@ -185,6 +233,8 @@ class CapturedTrainStep(_CapturedStep):
         losses = self.criterion(mc, out, ent["targets"], None, None)
         total = weighted_total(losses, self.weight_dict)
         total.backward()
+        if self._loss_word is not None:
+            self._loss_word.copy_(total.detach())      # (device to device, captured like any other launch: every replay hands its own loss to the guard)
         self.optimizer.step()
         return total
 
@@ -385,7 +435,11 @@ class CapturedDistillStep(_CapturedStep):
     tokenized=[..] * 2 (BatchEncodings with char_to_token), targets=[..] * 2, captions=[..] * 2, positive_map=[..] * 2) -> total loss (device scalar).
     The first step runs eagerly (a real training step) and is captured right after; later steps = the H2D copies of the inputs + one graph launch.
     Requirements (checked): one process, every memory bank full, nearest-replacement bank updates, both sides with the same number of targets per
-    image (the reference's pairs share their boxes), images / captions of the constructor's shape."""
+    image (the reference's pairs share their boxes), images / captions of the constructor's shape.
+
+    A bad step is handled as in CapturedTrainStep: fatal for both models' training state unless BOTH optimizers were built with skip_nonfinite=True;
+    then the step is skipped on the device and resolve_skipped() reports it (the loss word and the decoder status word are shared by the two tails, so
+    they skip together; a gradient norm that is not finite in one model only skips that model's update)."""
 
     def __init__(self, model, model_noun, criterion, cluster_criterion, optimizers, weight_dict, *, batch, image_hw, tokens, max_targets_per_image=16, device=None,
                  stream=None):
@@ -412,6 +466,7 @@ class CapturedDistillStep(_CapturedStep):
         if kernels.SEED_DEV is None:
             kernels.SEED_DEV = torch.zeros(1, dtype=torch.int64, device=dev)
         engine.REUSE_GRAD_BUFFERS = True
+        self._init_guard(self.optimizers)
 
     def pack(self, batch):
         """Host half of a step (no device work, no synchronisation when the batch's targets are host tensors: run it in the loader): the pinned images of both
@@ -461,9 +516,12 @@ class CapturedDistillStep(_CapturedStep):
             torch.cuda.current_stream().wait_stream(join)
         total_rest = weighted_total(losses, w_rest)
         total_rest.backward()
+        total = (total_noun + total_rest).detach()
+        if self._loss_word is not None:
+            self._loss_word.copy_(total)               # the guard's finite-loss check, as in CapturedTrainStep
         for o in self.optimizers:
             o.step()
-        return (total_noun + total_rest).detach()
+        return total
 
     def _zero_grad(self):
         for o in self.optimizers:

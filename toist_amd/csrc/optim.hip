@@ -2,6 +2,8 @@
 // clip_grad_norm_(max_norm) -> AdamW.step() -> update_ema(); util/optim.py:9-26; main.py:351-392 parameter groups):
 //   sqnorm_kernel      sum of squares of every gradient chunk                (reads g once)
 //   finish_norm_kernel total norm, clip coefficient, step count, bias corrections (one block, device-side state)
+//   finish_norm_guarded_kernel  the same, unless the norm is not finite or a veto word objects: then the step is SKIPPED (state.skipped = 1)
+//                      and adamw_ema_kernel returns without touching anything
 //   adamw_ema_kernel   g*clip -> decoupled weight decay -> Adam moments -> parameter -> EMA -> bf16 compute copy
 //                      (reads p,g,m,v,ema; writes p,m,v,ema,w_bf16: 38 B/parameter instead of three library sweeps
 //                      plus one cast kernel per weight tensor)
@@ -50,9 +52,8 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const toist_opt_tensor* __r
 
 // (one block on the step's critical path between the gradient norm and the update: 1024 threads, four independent loads in flight per thread --
 // 22 600 partial sums took 30 us with 256 threads walking them one load at a time)
-__global__ __launch_bounds__(1024) void finish_norm_kernel(const float* __restrict__ partial, int n, float max_norm, float beta1,
-                                                           float beta2, toist_opt_state* __restrict__ st) {
-    __shared__ double red[1024];
+// -> the sum of the n partial sums; valid in thread 0 only
+__device__ __forceinline__ double sum_partials_1024(const float* __restrict__ partial, int n, double* red) {
     double acc = 0.0;
     int i = threadIdx.x;
     for (; i + 3 * 1024 < n; i += 4 * 1024) {
@@ -66,19 +67,68 @@ __global__ __launch_bounds__(1024) void finish_norm_kernel(const float* __restri
         if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        const float norm = (float)sqrt(red[0]);
-        float coef = 1.f;
-        if (max_norm > 0.f) {  // torch.nn.utils.clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max=1)
-            coef = max_norm / (norm + 1e-6f);
-            if (coef > 1.f) coef = 1.f;  // NaN stays NaN, as in torch
+    return red[0];
+}
+
+// the state of an APPLIED step (one thread)
+__device__ __forceinline__ void take_step(toist_opt_state* __restrict__ st, float norm, float max_norm, float beta1, float beta2) {
+    float coef = 1.f;
+    if (max_norm > 0.f) {  // torch.nn.utils.clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max=1)
+        coef = max_norm / (norm + 1e-6f);
+        if (coef > 1.f) coef = 1.f;  // NaN stays NaN, as in torch
+    }
+    const int step = st->step + 1;
+    st->step = step;
+    st->grad_norm = norm;
+    st->clip_coef = coef;
+    st->bias1 = 1.f - powf(beta1, (float)step);
+    st->bias2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+    st->skipped = 0;
+}
+
+__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }  // inf or NaN
+
+__global__ __launch_bounds__(1024) void finish_norm_kernel(const float* __restrict__ partial, int n, float max_norm, float beta1,
+                                                           float beta2, toist_opt_state* __restrict__ st) {
+    __shared__ double red[1024];
+    const double sq = sum_partials_1024(partial, n, red);
+    if (threadIdx.x == 0) take_step(st, (float)sqrt(sq), max_norm, beta1, beta2);
+}
+
+// finish_norm with a veto: the step is applied only when the norm is finite and no veto word objects.  Threads 0..7 read the integer words and
+// threads 8..15 the float words BEFORE the reduction (two dependent loads each, hidden behind it); the words are read on every launch, so a
+// replayed hipGraph sees their current values.  A vetoed step leaves step / bias1 / bias2_sqrt alone and sets skipped, which makes every
+// adamw_ema launch that reads this state return at once.
+__global__ __launch_bounds__(1024) void finish_norm_guarded_kernel(const float* __restrict__ partial, int n, float max_norm, float beta1,
+                                                                   float beta2, toist_opt_state* __restrict__ st,
+                                                                   const int32_t* const* __restrict__ veto_i32, int n_i32,
+                                                                   const float* const* __restrict__ veto_f32, int n_f32) {
+    __shared__ double red[1024];
+    __shared__ int veto[2 * TOIST_OPT_MAX_VETO];
+    const int t = threadIdx.x;
+    if (t < 2 * TOIST_OPT_MAX_VETO) {
+        int bit = 0;
+        if (t < TOIST_OPT_MAX_VETO) {
+            if (t < n_i32 && *veto_i32[t] != 0) bit = 1 << (1 + t);
+        } else if (t - TOIST_OPT_MAX_VETO < n_f32 && nonfinite(*veto_f32[t - TOIST_OPT_MAX_VETO])) {
+            bit = 1 << (1 + t);
         }
-        const int step = st->step + 1;
-        st->step = step;
-        st->grad_norm = norm;
-        st->clip_coef = coef;
-        st->bias1 = 1.f - powf(beta1, (float)step);
-        st->bias2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+        veto[t] = bit;  // (the barriers of the reduction order these stores before thread 0 reads them)
+    }
+    const double sq = sum_partials_1024(partial, n, red);
+    if (t == 0) {
+        const float norm = (float)sqrt(sq);
+        int mask = nonfinite(norm) ? 1 : 0;
+        for (int i = 0; i < 2 * TOIST_OPT_MAX_VETO; ++i) mask |= veto[i];
+        st->veto_mask = mask;
+        if (mask == 0) {
+            take_step(st, norm, max_norm, beta1, beta2);
+        } else {  // a skipped step does not count as a step
+            st->skipped = 1;
+            st->skipped_total = st->skipped_total + 1;
+            st->grad_norm = norm;
+            st->clip_coef = 0.f;
+        }
     }
 }
 
@@ -95,6 +145,9 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const toist_opt_tensor* 
                                                         const int2* __restrict__ chunks, const toist_opt_group* __restrict__ groups,
                                                         const toist_opt_state* __restrict__ st, float b1, float b2, float eps,
                                                         float decay, int n_chunks) {
+  // a vetoed step (toist_opt_finish_norm_guarded) changes nothing: parameters, moments, averages and compute copies stay as they are.  Uniform
+  // across the launch; the word shares the cache line of clip_coef.
+  if (st->skipped != 0) return;
   // gridDim.x < n_chunks: a slim launch (the late groups' update beside the next forward pass) walks the chunks with few workgroups
   for (int cb = blockIdx.x; cb < n_chunks; cb += gridDim.x) {
     const int2 ch = chunks[cb];
@@ -188,6 +241,19 @@ extern "C" int toist_opt_finish_norm(const float* partial, int n_chunks, float m
     TOIST_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "toist_opt_finish_norm: betas must be in [0, 1)");
     hipLaunchKernelGGL(finish_norm_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partial, n_chunks, max_norm, beta1, beta2, state);
     return check_launch("toist_opt_finish_norm");
+}
+
+extern "C" int toist_opt_finish_norm_guarded(const float* partial, int n_chunks, float max_norm, float beta1, float beta2, toist_opt_state* state,
+                                             const int32_t* const* veto_i32, int n_veto_i32, const float* const* veto_f32, int n_veto_f32,
+                                             void* stream) {
+    TOIST_REQUIRE(partial && state && n_chunks > 0, "toist_opt_finish_norm_guarded: bad args");
+    TOIST_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "toist_opt_finish_norm_guarded: betas must be in [0, 1)");
+    TOIST_REQUIRE(n_veto_i32 >= 0 && n_veto_i32 <= TOIST_OPT_MAX_VETO && n_veto_f32 >= 0 && n_veto_f32 <= TOIST_OPT_MAX_VETO,
+                  "toist_opt_finish_norm_guarded: at most 8 veto words of each kind");
+    TOIST_REQUIRE((veto_i32 || n_veto_i32 == 0) && (veto_f32 || n_veto_f32 == 0), "toist_opt_finish_norm_guarded: NULL veto table with a positive count");
+    hipLaunchKernelGGL(finish_norm_guarded_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partial, n_chunks, max_norm, beta1, beta2, state,
+                       veto_i32, n_veto_i32, veto_f32, n_veto_f32);
+    return check_launch("toist_opt_finish_norm_guarded");
 }
 
 extern "C" int toist_opt_adamw_ema_blocks(const toist_opt_tensor* table, const int64_t* grads, const int32_t* chunks, int n_chunks,

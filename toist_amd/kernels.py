@@ -660,6 +660,14 @@ def opt_finish_norm(partial, n_chunks, max_norm, beta1, beta2, state):
                                                 _stream()), "toist_opt_finish_norm")
 
 
+def opt_finish_norm_guarded(partial, n_chunks, max_norm, beta1, beta2, state, veto_i32, n_veto_i32, veto_f32, n_veto_f32):
+    """finish_norm that skips the step when the norm is not finite or a veto word objects; veto_i32 / veto_f32: int64 device tensors holding the
+    device addresses of the words (include/toist_hip.h: toist_opt_finish_norm_guarded)"""
+    _lib.check(_lib.lib().toist_opt_finish_norm_guarded(_p(partial, torch.float32), n_chunks, max_norm, beta1, beta2, _p(state, torch.uint8),
+                                                        _p(veto_i32, torch.int64), n_veto_i32, _p(veto_f32, torch.int64), n_veto_f32, _stream()),
+               "toist_opt_finish_norm_guarded")
+
+
 def opt_adamw_ema(table, grads, chunks, n_chunks, groups, state, beta1, beta2, eps, ema_decay, max_blocks=0):
     _lib.check(_lib.lib().toist_opt_adamw_ema_blocks(_p(table, torch.uint8), _p(grads, torch.int64), _p(chunks, torch.int32), n_chunks,
                                                      _p(groups, torch.float32), _p(state, torch.uint8), beta1, beta2, eps, ema_decay, max_blocks, _stream()),
@@ -908,6 +916,9 @@ def xdec_check(raise_on_failure=True):
     results are invalid (the launch also turned them into NaN, so the losses of that step are NaN).  The word is cleared, XDEC_FAILED is set so that
     every later decoder forward / backward runs on the per-op launches (graphs captured with the launches inside must be re-captured:
     harness.CapturedTrainStep does), and RuntimeError is raised unless raise_on_failure is False (then the return value says whether a launch failed).
+    What the failed step did to TRAINING state depends on the optimizer: a FusedClipAdamWEMA(skip_nonfinite=True) inside a captured step has this word
+    as a veto and skipped the update (captured._CapturedStep.resolve_skipped calls this function: repeat the step); without the guard the NaN
+    gradients of that launch have already been applied to the weights, the moments and the EMA, and only a checkpoint helps.
     Called by harness.finite_or_exit, CapturedTrainStep when a replayed loss is not finite, harness.evaluate, Transformer's eval-mode decode, bench.py,
     smoke()."""
     global XDEC_FAILED
@@ -920,8 +931,10 @@ def xdec_check(raise_on_failure=True):
         XDEC_FAILED = True
         if raise_on_failure:
             raise RuntimeError("toist_xdec: a workgroup gave up waiting for its XCD group (the 32 workgroups of an image were not co-resident); the results of "
-                               "that step are invalid (NaN).  The XCD-resident decoder launches are now off for this process: repeat the step (per-op launches), "
-                               "or start with TOIST_XDEC=0 when the GPU is shared")
+                               "that step are invalid (NaN).  The XCD-resident decoder launches are now off for this process.  Inference, and training "
+                               "under FusedClipAdamWEMA(skip_nonfinite=True) (the update of that step was skipped): repeat the step (per-op launches).  "
+                               "Training without that guard: the step's NaN gradients are already in the weights, restore from a checkpoint.  Start "
+                               "with TOIST_XDEC=0 when the GPU is shared")
     return failed
 
 

@@ -75,10 +75,23 @@ class FusedClipAdamWEMA:
     defer_ema=True takes the moving average out of step(): it only needs the updated parameters, so the loop may run it as
     `ema_update()` on a side stream beside the next forward pass (12 of the tail's 38 bytes per parameter leave the critical path).
     The average is the same sequence of values; step() applies a still-pending update itself before it changes the parameters
-    again, and `ema_update()` after the last step completes it."""
+    again, and `ema_update()` after the last step completes it.
+
+    skip_nonfinite=True is the reference's finite-loss guard (engine.py:82-85: it leaves the loop before backward() when the loss is not
+    finite) moved to the device, for steps whose backward pass and tail sit in one hipGraph and cannot be stopped from the host.  The
+    finish-norm launch vetoes the step when the gradient norm is not finite or when a word registered with `add_veto` objects (an int32
+    word that is non-zero: a kernel's failure status; an fp32 word that is not finite: the loss).  A skipped step is as if step() had
+    not been called: parameters, both moments, every average (EMA-only rows and the deferred `ema_update()` included), the bf16 compute
+    copies, the late groups' launch, the step count and the bias corrections stay bit for bit as they were.  `device_state()` then
+    reports `skipped`, the running `skipped_total` and `veto_mask` (bit 0: the norm; bit 1 + i: integer word i; bit 9 + j: float word
+    j).  The norm is taken from an fp32 sum of squares: finite gradients large enough to overflow it (around 1e19 and above) count as
+    non-finite and are skipped too.  With the option off (the default) nothing is ever skipped: NaN gradients reach the weights, as
+    with torch.optim.AdamW."""
+
+    MAX_VETO = 8        # words of each kind (include/toist_hip.h: TOIST_OPT_MAX_VETO)
 
     def __init__(self, param_groups, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4, max_norm=0.1, ema=None, ema_decay=0.9998,
-                 defer_ema=False):
+                 defer_ema=False, skip_nonfinite=False):
         if isinstance(param_groups, (list, tuple)) and param_groups and torch.is_tensor(param_groups[0]):
             param_groups = [{"params": list(param_groups)}]
         self.param_groups = []
@@ -140,6 +153,10 @@ class FusedClipAdamWEMA:
             if e is not None and (e.shape != p.shape or e.stride() != p.stride()):
                 raise ValueError("FusedClipAdamWEMA: an EMA tensor must share its source's shape and strides")
         self.state = torch.zeros(32, dtype=torch.uint8, device=self.device)          # toist_opt_state
+        self.skip_nonfinite = bool(skip_nonfinite)
+        # the veto words' addresses: fixed-address device tables (a captured finish-norm launch holds the tables, not the words), rewritten by add_veto
+        self._veto_words = ([], [])                                                    # (int32 words, fp32 words): kept alive here
+        self._veto_dev = tuple(torch.zeros(self.MAX_VETO, dtype=torch.int64, device=self.device) for _ in range(2)) if self.skip_nonfinite else None
         self._groups_host = None
         self._groups_dev = torch.zeros(len(self.param_groups), 2, dtype=torch.float32, device=self.device)
         self._chunk = k.opt_chunk_elems()
@@ -240,6 +257,26 @@ class FusedClipAdamWEMA:
         keep("_partial", torch.empty(self._n_chunks, dtype=torch.float32, device=self.device))
         self._copy_gen = engine.COPY_GEN
 
+    def add_veto(self, word):
+        """Register a one-element device tensor that can veto a step (skip_nonfinite=True only): int32 -- the step is skipped while the word is
+        non-zero; fp32 -- while it is not finite.  The word is read by the finish-norm launch of every step, replays included; register it BEFORE
+        a capture (the tables sit at fixed addresses, but a word added later is only seen by launches issued after this call has completed).
+        At most 8 words of each kind.  -> the word's bit in device_state()["veto_mask"]."""
+        if not self.skip_nonfinite:
+            raise ValueError("FusedClipAdamWEMA.add_veto needs skip_nonfinite=True")
+        if not torch.is_tensor(word) or word.numel() != 1 or word.device != self.device or word.dtype not in (torch.int32, torch.float32):
+            raise TypeError("FusedClipAdamWEMA.add_veto: a one-element int32 or fp32 tensor on the optimizer's device")
+        kind = 0 if word.dtype == torch.int32 else 1
+        words = self._veto_words[kind]
+        for j, w in enumerate(words):
+            if w.data_ptr() == word.data_ptr():
+                return 1 << (1 + self.MAX_VETO * kind + j)
+        if len(words) >= self.MAX_VETO:
+            raise ValueError(f"FusedClipAdamWEMA.add_veto: at most {self.MAX_VETO} {'fp32' if kind else 'int32'} veto words")
+        words.append(word)
+        self._veto_dev[kind].copy_(torch.tensor([w.data_ptr() for w in words] + [0] * (self.MAX_VETO - len(words)), dtype=torch.int64))
+        return 1 << (1 + self.MAX_VETO * kind + len(words) - 1)
+
     # ---- torch.optim-like surface ---------------------------------------------------------------------------
     def zero_grad(self, set_to_none=True):
         # a pending late-group launch reads the gradient VALUES through the pointers kept in _late_grads: it must run before they are zeroed
@@ -294,7 +331,11 @@ class FusedClipAdamWEMA:
         else:
             k.opt_sqnorm(self._table, self._grads_dev, self._chunks, self._n_chunks, self._partial)
         self._early_done = False
-        k.opt_finish_norm(self._partial, self._n_chunks, self.max_norm, self.betas[0], self.betas[1], self.state)
+        if self.skip_nonfinite:
+            k.opt_finish_norm_guarded(self._partial, self._n_chunks, self.max_norm, self.betas[0], self.betas[1], self.state,
+                                      self._veto_dev[0], len(self._veto_words[0]), self._veto_dev[1], len(self._veto_words[1]))
+        else:
+            k.opt_finish_norm(self._partial, self._n_chunks, self.max_norm, self.betas[0], self.betas[1], self.state)
         if self._n_now:
             k.opt_adamw_ema(self._table, self._grads_dev, self._chunks, self._n_now, self._groups_dev, self.state, self.betas[0],
                             self.betas[1], self.eps, self.ema_decay)
@@ -385,11 +426,13 @@ class FusedClipAdamWEMA:
 
     # ---- introspection / checkpointing ----------------------------------------------------------------------
     def device_state(self):
-        """{'clip_coef', 'grad_norm', 'bias1', 'bias2_sqrt', 'step'} read back from the device (synchronises)."""
+        """{'clip_coef', 'grad_norm', 'bias1', 'bias2_sqrt', 'step', 'skipped', 'skipped_total', 'veto_mask'} read back from the device
+        (synchronises).  step counts APPLIED steps; skipped: the last step() was vetoed (skip_nonfinite=True), veto_mask says why."""
         raw = self.state.cpu().numpy()
         f = raw[:16].view(np.float32)
+        i = raw[16:32].view(np.int32)
         return {"clip_coef": float(f[0]), "grad_norm": float(f[1]), "bias1": float(f[2]), "bias2_sqrt": float(f[3]),
-                "step": int(raw[16:20].view(np.int32)[0])}
+                "step": int(i[0]), "skipped": bool(i[1]), "skipped_total": int(i[2]), "veto_mask": int(i[3])}
 
     def state_dict(self):
         """torch.optim.AdamW's layout ({"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [{..., "params": [i, ...]}]}),
@@ -421,7 +464,7 @@ class FusedClipAdamWEMA:
             steps.append(int(float(st["step"])))
         if steps and min(steps) != max(steps):
             raise ValueError("FusedClipAdamWEMA.load_state_dict: parameters with different step counts (the fused tail keeps one counter)")
-        raw = np.zeros(32, dtype=np.uint8)
+        raw = np.zeros(32, dtype=np.uint8)          # (skipped / skipped_total / veto_mask are not part of a checkpoint: zero)
         raw[16:20] = np.array([steps[0] if steps else 0], dtype=np.int32).view(np.uint8)
         self.state.copy_(torch.from_numpy(raw))
         for g, src in zip(self.param_groups, sd.get("param_groups", [])):

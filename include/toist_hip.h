@@ -746,6 +746,26 @@ TOIST_API int toist_coco_match(const double* iou, const int64_t* iou_offset, con
                      int n_ranges, const double* iou_thresholds, int n_thresholds, int32_t* dt_match, uint8_t* dt_ignore,
                      uint8_t* gt_range_ignore, uint8_t* gt_taken, void* stream);
 
+/* ---- image preparation on the device (replaces the host pipeline between the decoded uint8 image and the model's input: datasets/tdod.py:301-335,
+ * datasets/transforms.py:18-59 crop, 62-80 hflip, 83-138 resize = PIL Image.resize(BILINEAR), 244-273 ToTensor / Normalize, and the padding + mask of
+ * util/misc.py:185-209 NestedTensor.from_tensor_list).  One launch per batch; every size comes from the device, so the launch can sit in a captured
+ * hipGraph.  `desc` = int32 [batch_cap, TOIST_PREP_DESC_WORDS], one row per image:
+ *    0 src_off (bytes from `src`)   1 src_h   2 src_w   3 src_stride (bytes per row; uint8 HWC RGB)      4 flip (horizontal, applied first)
+ *    5 crop_y  6 crop_x  7 crop_h  8 crop_w   (in the coordinates of the flipped source; the whole image when there is no crop)
+ *    9 out_h  10 out_w  11 ksize_h  12 ksize_v   (`_h` = the horizontal pass crop_w -> out_w, `_v` = the vertical pass crop_h -> out_h)
+ *   13 bounds_h  14 coef_h  15 bounds_v  16 coef_v   (int32 word offsets into `arena`)      17 dst_off (bytes from `dst_u8`)      18, 19 reserved
+ * bounds = (first tap, tap count) per output index; coef = ksize int32 coefficients per output index with 22 fractional bits (Pillow's 8-bit
+ * resampler: out = clip((2^21 + sum_j pixel[first + j] * k_j) >> 22, 0, 255), horizontal pass first, its uint8 result the vertical pass's input).
+ * The grid covers [batch_cap, cap_h, cap_w].  A row with out_h = 0 is an empty slot; a row that does not fit the capacities (src_bytes, arena_words,
+ * dst_bytes, cap_h, cap_w) is treated as one: the caller checks its sizes on the host before the launch.  Exactly one output mode:
+ *   final        (out != NULL): out fp32 [batch_cap, 3, cap_h, cap_w] = lut[c][pixel] inside (out_h, out_w), 0 outside; mask bytes [batch_cap, cap_h,
+ *                cap_w] = 0 inside, 1 outside.  The WHOLE capacity is written.  lut = fp32 [3, 256] = (v / 255 - mean[c]) / std[c].  cap_w % 4 == 0.
+ *   intermediate (dst_u8 != NULL): image i as uint8 HWC [out_h, out_w, 3] at dst_u8 + dst_off; nothing else is written.  dst_u8 may be another part
+ *                of the buffer `src` points into, as long as no image's output overlaps any image's source. */
+#define TOIST_PREP_DESC_WORDS 20
+TOIST_API int toist_image_prep(const uint8_t* src, long long src_bytes, const int32_t* desc, const int32_t* arena, long long arena_words, const float* lut,
+                     int batch_cap, int cap_h, int cap_w, float* out, uint8_t* mask, uint8_t* dst_u8, long long dst_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

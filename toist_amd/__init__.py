@@ -22,6 +22,9 @@ def __getattr__(name):
         "PostProcessSegm": ("postprocessors", "PostProcessSegm"), "build_postprocessors": ("postprocessors", "build_postprocessors"),
         "NestedTensor": ("misc", "NestedTensor"), "targets_to": ("misc", "targets_to"),
         "TDODCocoEvaluator": ("coco_eval", "TDODCocoEvaluator"), "CocoGroundTruth": ("coco_eval", "CocoGroundTruth"),
+        "DevicePreprocessor": ("preprocess", "DevicePreprocessor"), "PrepPlan": ("preprocess", "PrepPlan"), "val_plan": ("preprocess", "val_plan"),
+        "sample_train_plan": ("preprocess", "sample_train_plan"), "transform_target": ("preprocess", "transform_target"),
+        "resized_size": ("preprocess", "resized_size"), "resample_tables": ("preprocess", "resample_tables"),
     }
     if name in table:
         mod, attr = table[name]

@@ -1006,6 +1006,33 @@ def mask_resize_pack_batch(logits, max_size, table, cap_hw, capacity_words, out,
     return out
 
 
+def image_prep(src, desc, arena, lut=None, out=None, mask=None, dst_u8=None, cap_hw=None):
+    """Resize (Pillow-exact bilinear) + normalise + pad + mask of a batch of uint8 images in one launch that reads every size from the device
+    (include/toist_hip.h: toist_image_prep).  src uint8 [bytes], desc int32 [batch capacity, PREP_DESC_WORDS], arena int32 [words]: fixed-address
+    device buffers that toist_amd.preprocess.DevicePreprocessor fills.  Final mode: out fp32 [B, 3, Hp, Wp] + mask bool [B, Hp, Wp] + lut fp32 [3, 256];
+    intermediate mode: dst_u8 uint8 [bytes] + cap_hw = the largest (h, w) the grid has to cover.  No host read, no allocation: graph-capturable."""
+    if desc.dim() != 2 or desc.shape[1] != _lib.PREP_DESC_WORDS or not desc.is_contiguous() or not src.is_contiguous() or not arena.is_contiguous():
+        raise ValueError(f"image_prep: contiguous buffers and an int32 [B, {_lib.PREP_DESC_WORDS}] descriptor table")
+    B = desc.shape[0]
+    if (out is None) == (dst_u8 is None):
+        raise ValueError("image_prep: exactly one of `out` (final mode) and `dst_u8` (intermediate mode)")
+    if out is not None:
+        if mask is None or lut is None or tuple(lut.shape) != (3, 256) or not lut.is_contiguous():
+            raise ValueError("image_prep: the final mode needs the mask and a contiguous fp32 [3, 256] normalisation table")
+        Hp, Wp = int(out.shape[-2]), int(out.shape[-1])
+        if tuple(out.shape) != (B, 3, Hp, Wp) or tuple(mask.shape) != (B, Hp, Wp) or not out.is_contiguous() or not mask.is_contiguous() or Wp % 4:
+            raise ValueError(f"image_prep: contiguous out [{B}, 3, Hp, Wp] and mask [{B}, Hp, Wp] with Wp % 4 == 0 (got {tuple(out.shape)}, {tuple(mask.shape)})")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"image_prep: the mask holds bytes (bool or uint8), got {mask.dtype}")
+        args = (_p(lut, torch.float32), B, Hp, Wp, _p(out, torch.float32), _p(mask), None, 0)
+    else:
+        if not dst_u8.is_contiguous() or cap_hw is None:
+            raise ValueError("image_prep: the intermediate mode needs a contiguous uint8 destination and cap_hw")
+        args = (None, B, int(cap_hw[0]), int(cap_hw[1]), None, None, _p(dst_u8, torch.uint8), dst_u8.numel())
+    _lib.check(_lib.lib().toist_image_prep(_p(src, torch.uint8), src.numel(), _p(desc, torch.int32), _p(arena, torch.int32), arena.numel(), *args, _stream()),
+               "toist_image_prep")
+
+
 def postprocess(pred_logits, pred_boxes, sizes_dev, pred_isfinal=None, out=None):
     """PostProcess in one launch (include/toist_hip.h: toist_postprocess).  pred_logits [B, Q, C] and pred_boxes [B, Q, 4] in bf16 or f32, pred_isfinal
     [B, Q] (or [B, Q, 1]) optional, sizes_dev int64 [B, 2] = (h, w) ON THE DEVICE.  -> dict(scores f32 [B, Q], boxes f32 [B, Q, 4] (+ scores_refexp));

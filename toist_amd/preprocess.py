@@ -1,0 +1,470 @@
+"""Image preparation on the device: the reference's host pipeline between a decoded uint8 image and the model's input (datasets/tdod.py:301-335
+make_coco_transforms, datasets/transforms.py, util/misc.py:185-209 NestedTensor.from_tensor_list) with the pixels done by ONE HIP launch per batch
+(csrc/prep.hip: toist_image_prep) -- the host link carries the original uint8 pixels, not fp32 planes at the resized size.
+
+The host keeps what is cheap and per image: the size rule, the random decisions of the training recipe (a PrepPlan), the targets
+(transform_target) and the resampling tables.  torchvision's F.resize on a PIL image is Image.resize((w, h), BILINEAR), and Pillow's 8-bit
+resampler is integer arithmetic on coefficients computed in double precision: resample_tables restates that computation in numpy float64,
+the kernel does the integer passes, so the prepared pixels EQUAL the reference's (tests/golden/preprocess.npz is Pillow's own output).
+
+There is no CPU path: DevicePreprocessor on a CPU device raises, like misc.DeviceStager."""
+import functools
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .box_ops import box_xyxy_to_cxcywh
+from .misc import NestedTensor, interpolate
+
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)                      # tdod.py:303
+SCALES = (480, 512, 544, 576, 608, 640, 672, 704, 736, 768, 800)            # tdod.py:305
+MAX_SIZE = 1333
+PRECISION_BITS = 22
+
+
+# ---- sizes and tables ----------------------------------------------------------------------------------------------------------------------
+def resized_size(w, h, size, max_size=None):
+    """The reference's get_size_with_aspect_ratio (transforms.py:86-104): short side to `size`, long side capped at `max_size`.  -> (h, w)."""
+    w, h = int(w), int(h)
+    if max_size is not None:
+        lo, hi = float(min(w, h)), float(max(w, h))
+        if hi / lo * size > max_size:
+            size = int(round(max_size * lo / hi))
+    if (w <= h and w == size) or (h <= w and h == size):
+        return h, w
+    if w < h:
+        return int(size * h / w), size
+    return size, int(size * w / h)
+
+
+def _tables(n_in, n_out):
+    scale = np.float64(n_in) / np.float64(n_out)
+    fs = max(scale, np.float64(1.0))
+    support = fs                                                   # the bilinear filter's support is 1
+    ksize = 2 * int(np.ceil(support)) + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    hi = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), n_in)
+    n = hi - lo
+    j = np.arange(ksize, dtype=np.int64)[None, :]
+    ss = np.float64(1.0) / fs
+    w = np.maximum(0.0, 1.0 - np.abs(((j + lo[:, None]) - center[:, None] + 0.5) * ss))
+    w = np.where(j < n[:, None], w, 0.0)
+    total = np.zeros(n_out, dtype=np.float64)
+    for c in range(ksize):                                         # left to right, as the resampler sums them
+        total = total + w[:, c]
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    coef = np.trunc(w * float(1 << PRECISION_BITS) + 0.5).astype(np.int32)
+    bounds = np.stack([lo, n], axis=1).astype(np.int32)
+    return bounds, coef
+
+
+@functools.lru_cache(maxsize=512)
+def _cached_tables(n_in, n_out):
+    bounds, coef = _tables(n_in, n_out)
+    bounds.setflags(write=False)
+    coef.setflags(write=False)
+    return bounds, coef
+
+
+def resample_tables(n_in, n_out):
+    """Pillow's bilinear resampling of one axis from extent n_in to n_out for 8-bit images.  -> (bounds int32 [n_out, 2] = (first tap, tap count),
+    coef int32 [n_out, ksize], 22 fractional bits, zero behind the tap count); ksize = 2 * ceil(max(n_in / n_out, 1)) + 1.  One pass is
+    out[i] = clip((2^21 + sum_j pixel[first_i + j] * coef[i, j]) >> 22, 0, 255).  Everything before the final integer rounding is float64."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"resample_tables: extents must be positive (got {n_in} -> {n_out})")
+    return _cached_tables(n_in, n_out)
+
+
+@functools.lru_cache(maxsize=64)
+def _identity_tables(n):
+    bounds = np.stack([np.arange(n), np.ones(n, dtype=np.int64)], axis=1).astype(np.int32)
+    return bounds, np.full((n, 1), 1 << PRECISION_BITS, dtype=np.int32)
+
+
+def _pass_tables(n_in, n_out):
+    """The tables the kernel gets: a pass whose extents are equal is the identity (Pillow skips it) -- one tap of weight 1."""
+    return _identity_tables(n_in) if n_in == n_out else resample_tables(n_in, n_out)
+
+
+# ---- the decisions for one image -----------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class PrepPlan:
+    """What happens to one image, in the reference's order: horizontal flip -> optional first resize -> optional crop -> final resize (-> ToTensor,
+    Normalize).  width / height: the source; first: (h, w) of the first resize or None; crop: (top, left, h, w) in the coordinates of the image
+    it is applied to (the first resize's output, or the flipped source without one) or None; final: (h, w) of the prepared image."""
+    width: int
+    height: int
+    flip: bool = False
+    first: Optional[Tuple[int, int]] = None
+    crop: Optional[Tuple[int, int, int, int]] = None
+    final: Tuple[int, int] = (0, 0)
+
+    def __post_init__(self):
+        if self.width <= 0 or self.height <= 0 or self.final[0] <= 0 or self.final[1] <= 0:
+            raise ValueError(f"PrepPlan: bad sizes {self}")
+        if self.first is not None and (self.first[0] <= 0 or self.first[1] <= 0):
+            raise ValueError(f"PrepPlan: bad first resize {self.first}")
+        if self.crop is not None:
+            t, l, h, w = self.crop
+            H, W = self.first if self.first is not None else (self.height, self.width)
+            if t < 0 or l < 0 or h <= 0 or w <= 0 or t + h > H or l + w > W:
+                raise ValueError(f"PrepPlan: the crop {self.crop} leaves the {H} x {W} image it is applied to")
+
+
+def val_plan(w, h):
+    """The validation recipe (tdod.py:327-333): resize 800 / 1333."""
+    return PrepPlan(int(w), int(h), final=resized_size(w, h, 800, MAX_SIZE))
+
+
+def _boxes_survive(boxes, plan_flip, w, h, first, region):
+    t = {"boxes": torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4)}
+    n = len(t["boxes"])
+    if plan_flip:
+        t = _t_hflip(t, w)
+    t = _t_resize(t, (h, w), first)
+    return len(_t_crop(t, region)["boxes"]) == n
+
+
+def sample_train_plan(rng, w, h, boxes=None, cautious=False):
+    """A plan with the STRUCTURE of the reference's training recipe (tdod.py:308-325): flip with probability 1/2 (never when `cautious`), then with
+    probability 1/2 one resize to a random scale / 1333, else resize to one of 400 / 500 / 600, a random crop of 384 .. 1333 per side and the resize
+    to a random scale / 1333.  With `cautious` the crop is drawn again (150 times at most, RandomSizeCrop's respect_boxes, transforms.py:163-181)
+    until no box of `boxes` (xyxy, source coordinates) is cropped out; when none is found the image stays un-cropped, as in the reference.
+    `rng` is a random.Random (random(), randint(a, b), choice(seq)).  It does NOT reproduce the reference's random stream: the reference draws from the
+    global `random` module and torch.randint in an order this function does not follow, so the same seed gives other decisions."""
+    w, h = int(w), int(h)
+    flip = (not cautious) and rng.random() < 0.5
+    if rng.random() < 0.5:
+        return PrepPlan(w, h, flip, None, None, resized_size(w, h, rng.choice(SCALES), MAX_SIZE))
+    first = resized_size(w, h, rng.choice((400, 500, 600)), None)
+    fh, fw = first
+    crop = None
+    for _ in range(150):
+        cw = rng.randint(min(384, fw), min(fw, MAX_SIZE))
+        ch = rng.randint(min(384, fh), min(fh, MAX_SIZE))
+        region = (rng.randint(0, fh - ch), rng.randint(0, fw - cw), ch, cw)
+        if not cautious or boxes is None or _boxes_survive(boxes, flip, w, h, first, region):
+            crop = region
+            break
+    ch, cw = (crop[2], crop[3]) if crop is not None else first
+    return PrepPlan(w, h, flip, first, crop, resized_size(cw, ch, rng.choice(SCALES), MAX_SIZE))
+
+
+# ---- targets (host) ------------------------------------------------------------------------------------------------------------------------
+def _t_hflip(t, w):
+    t = dict(t)
+    if "boxes" in t:
+        t["boxes"] = t["boxes"][:, [2, 1, 0, 3]] * torch.as_tensor([-1, 1, -1, 1]) + torch.as_tensor([w, 0, w, 0])
+    if "masks" in t:
+        t["masks"] = t["masks"].flip(-1)
+    if "caption" in t:
+        t["caption"] = t["caption"].replace("left", "[TMP]").replace("right", "left").replace("[TMP]", "right")
+    return t
+
+
+def _t_resize(t, old_hw, new_hw):
+    t = dict(t)
+    rh, rw = float(new_hw[0]) / float(old_hw[0]), float(new_hw[1]) / float(old_hw[1])
+    if "boxes" in t:
+        t["boxes"] = t["boxes"] * torch.as_tensor([rw, rh, rw, rh])
+    if "area" in t:
+        t["area"] = t["area"] * (rw * rh)
+    t["size"] = torch.tensor([int(new_hw[0]), int(new_hw[1])])
+    if "masks" in t:
+        t["masks"] = interpolate(t["masks"][:, None].float(), tuple(int(v) for v in new_hw), mode="nearest")[:, 0] > 0.5
+    return t
+
+
+def _t_crop(t, region):
+    t = dict(t)
+    i, j, h, w = region
+    t["size"] = torch.tensor([h, w])
+    fields = ["labels", "area", "iscrowd", "positive_map", "isfinal"]
+    if "boxes" in t:
+        b = t["boxes"] - torch.as_tensor([j, i, j, i])
+        b = torch.min(b.reshape(-1, 2, 2), torch.as_tensor([w, h], dtype=torch.float32)).clamp(min=0)
+        t["area"] = (b[:, 1, :] - b[:, 0, :]).prod(dim=1)
+        t["boxes"] = b.reshape(-1, 4)
+        fields.append("boxes")
+    if "masks" in t:
+        t["masks"] = t["masks"][:, i:i + h, j:j + w]
+        fields.append("masks")
+    if "boxes" in t or "masks" in t:
+        if "boxes" in t:
+            b = t["boxes"].reshape(-1, 2, 2)
+            keep = torch.all(b[:, 1, :] > b[:, 0, :], dim=1)
+        else:
+            keep = t["masks"].flatten(1).any(1)
+        for f in fields:
+            if f in t:
+                t[f] = t[f][keep]
+    return t
+
+
+def transform_target(target, plan):
+    """What the reference's transforms do to a target dict along `plan` (transforms.py hflip 62-80, resize 118-138, crop 18-59, Normalize 262-273), on
+    the host: boxes (xyxy in, cxcywh / (w, h, w, h) out), area, size, masks (flip, nearest resize, slice: torch ops) and caption (left <-> right on a
+    flip); after a crop the boxes of zero area go, with their rows of labels, area, iscrowd, positive_map, isfinal and masks.  The input is not changed."""
+    t = dict(target)
+    hw = (plan.height, plan.width)
+    if plan.flip:
+        t = _t_hflip(t, plan.width)
+    if plan.first is not None:
+        t = _t_resize(t, hw, plan.first)
+        hw = plan.first
+    if plan.crop is not None:
+        t = _t_crop(t, plan.crop)
+        hw = (plan.crop[2], plan.crop[3])
+    t = _t_resize(t, hw, plan.final)
+    if "boxes" in t:
+        h, w = plan.final
+        t["boxes"] = box_xyxy_to_cxcywh(t["boxes"]) / torch.tensor([w, h, w, h], dtype=torch.float32)
+    return t
+
+
+# ---- the packed descriptor -------------------------------------------------------------------------------------------------------------------
+DESC_FIELDS = ("src_off", "src_h", "src_w", "src_stride", "flip", "crop_y", "crop_x", "crop_h", "crop_w", "out_h", "out_w", "ksize_h", "ksize_v",
+               "bounds_h", "coef_h", "bounds_v", "coef_v", "dst_off", "reserved0", "reserved1")
+assert len(DESC_FIELDS) == _lib.PREP_DESC_WORDS
+
+
+def pack_descriptor(**fields):
+    """One row of toist_image_prep's descriptor table (include/toist_hip.h) as int32 [PREP_DESC_WORDS]; fields left out are 0."""
+    unknown = set(fields) - set(DESC_FIELDS)
+    if unknown:
+        raise KeyError(f"pack_descriptor: unknown fields {sorted(unknown)}")
+    row = np.zeros(len(DESC_FIELDS), dtype=np.int32)
+    for name, v in fields.items():
+        if not -2 ** 31 <= int(v) < 2 ** 31:
+            raise OverflowError(f"pack_descriptor: {name} = {v} does not fit int32")
+        row[DESC_FIELDS.index(name)] = int(v)
+    return row
+
+
+def unpack_descriptor(row):
+    return {name: int(v) for name, v in zip(DESC_FIELDS, np.asarray(row).reshape(-1))}
+
+
+def normalisation_table():
+    """fp32 [3, 256]: ToTensor + Normalize of every byte value, (v / 255 - mean[c]) / std[c], computed by torch as the reference computes it."""
+    v = torch.arange(256, dtype=torch.float32).div(255)
+    return (v[None, :] - torch.tensor(MEAN, dtype=torch.float32)[:, None]) / torch.tensor(STD, dtype=torch.float32)[:, None]
+
+
+@dataclass(frozen=True)
+class PackedBatch:
+    """What pack() placed in the arenas: image count, the batch extent (largest output rounded up to pad_hw) and whether any image has a first resize."""
+    batch: int
+    height: int
+    width: int
+    two_stage: bool
+    sizes: tuple          # (h, w) of every prepared image
+
+
+def _up(v, m):
+    return (int(v) + m - 1) // m * m
+
+
+def _as_hwc(img):
+    a = img.detach().cpu().numpy() if torch.is_tensor(img) else np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError(f"DevicePreprocessor: images are uint8 [h, w, 3] (got {a.dtype} {a.shape})")
+    return a
+
+
+class DevicePreprocessor:
+    """Decoded uint8 images + PrepPlans -> the padded fp32 batch and its mask, on the device.
+
+    Owns fixed-address device memory -- one blob holding the two descriptor tables, the resampling tables and the source pixels of a batch,
+    followed by the intermediate uint8 images of two-resize plans; the normalisation table; the output [max_batch, 3, Hc, Wc] + mask at the capacity
+    (max_out_hw rounded up to pad_hw, the width to a multiple of 4) -- and one pinned host image of the blob's head.
+      pack(images, plans)   : fills the pinned buffer and issues ONE asynchronous host-to-device copy on the current stream -> PackedBatch
+      launch(out=None)      : one launch (two when an image has a first resize: that stage writes the uint8 image between the resizes), sizes
+                              read from the device, nothing else: the launches can be captured once and replayed after every pack()
+      prepare(images, plans, out=None) = pack + launch -> NestedTensor of the batch extent (views into the capacity-sized output, which is
+                              written completely: zeros and mask True outside each image, whatever it held before)
+    The batch extent is the largest prepared image rounded up to pad_hw: with pad_hw = 64 it is a captured step's bucket shape, and captured.upload
+    takes its existing path.  `out` = a NestedTensor [Bc <= max_batch, 3, Hp, Wp % 4 == 0] / [Bc, Hp, Wp] of the caller's to write instead.
+    Every capacity (max_batch, max_src_pixels over the batch, max_out_hw, max_mid_hw for the image between two resizes, the table words) is
+    checked on the host and raises ValueError before anything is copied or launched."""
+
+    def __init__(self, device, max_batch, max_src_pixels, max_out_hw, pad_hw=1, max_mid_hw=None, max_table_words=None):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DevicePreprocessor prepares images in GPU memory: there is no CPU path")
+        self.max_batch, self.max_src_pixels, self.pad_hw = int(max_batch), int(max_src_pixels), int(pad_hw)
+        self.max_out_hw = (int(max_out_hw[0]), int(max_out_hw[1]))
+        self.max_mid_hw = (int(max_mid_hw[0]), int(max_mid_hw[1])) if max_mid_hw is not None else self.max_out_hw
+        if self.max_batch <= 0 or self.max_src_pixels <= 0 or self.pad_hw <= 0 or min(self.max_out_hw) <= 0 or min(self.max_mid_hw) <= 0:
+            raise ValueError("DevicePreprocessor: capacities must be positive")
+        self.cap_hw = (_up(self.max_out_hw[0], self.pad_hw), _up(_up(self.max_out_hw[1], self.pad_hw), 4))
+        # two axes x two stages per image, ksize 3 (bounds + coefficients = 5 words per output index) with room for reductions up to ksize 16
+        self.max_table_words = int(max_table_words) if max_table_words is not None else \
+            self.max_batch * 2 * 18 * (sum(self.max_out_hw) + sum(self.max_mid_hw))
+        B = self.max_batch
+        self._desc_bytes = 2 * B * _lib.PREP_DESC_WORDS * 4
+        self._head_bytes = _up(self._desc_bytes + 4 * self.max_table_words + 3 * self.max_src_pixels + 16 * (B + 1), 16)     # what pack() may fill
+        self._mid_bytes = _up(3 * B * self.max_mid_hw[0] * self.max_mid_hw[1] + 16 * B, 16)
+        if self._head_bytes + self._mid_bytes >= 2 ** 31:
+            raise ValueError("DevicePreprocessor: the arenas address bytes with 31 bits")
+        self.blob = torch.zeros(self._head_bytes + self._mid_bytes, dtype=torch.uint8, device=self.device)
+        self.desc = self.blob[:self._desc_bytes].view(torch.int32).view(2, B, _lib.PREP_DESC_WORDS)      # [0]: first-resize stage, [1]: final stage
+        self.arena = self.blob.view(torch.int32)          # table offsets are int32 words from the blob's start
+        self.mid = self.blob[self._head_bytes:]
+        self.lut = normalisation_table().to(self.device)
+        self.out = NestedTensor(torch.zeros(B, 3, *self.cap_hw, device=self.device), torch.ones(B, *self.cap_hw, dtype=torch.bool, device=self.device))
+        self._host = torch.zeros(self._head_bytes, dtype=torch.uint8).pin_memory()
+        self._host_np = self._host.numpy()
+        self._event = None
+        self._last = None
+
+    # -- host side ----------------------------------------------------------------------------------------------------------------------
+    def _layout(self, images, plans, u8):
+        """Host check + placement of a batch: -> (PackedBatch, rows [2, B] of descriptor dicts, table list, pixel list, used bytes).  Raises ValueError on
+        any capacity overrun; touches no buffer."""
+        if len(images) != len(plans) or not images:
+            raise ValueError(f"DevicePreprocessor: {len(images)} images for {len(plans)} plans (at least one)")
+        if len(images) > self.max_batch:
+            raise ValueError(f"DevicePreprocessor: a batch of {len(images)} exceeds max_batch = {self.max_batch}")
+        imgs = [_as_hwc(im) for im in images]
+        for a, p in zip(imgs, plans):
+            if a.shape[:2] != (p.height, p.width):
+                raise ValueError(f"DevicePreprocessor: a {a.shape[0]} x {a.shape[1]} image with a plan for {p.height} x {p.width}")
+            limit = self.max_mid_hw if u8 else self.max_out_hw
+            if p.final[0] > limit[0] or p.final[1] > limit[1]:
+                raise ValueError(f"DevicePreprocessor: a prepared size of {p.final[0]} x {p.final[1]} exceeds the capacity {limit[0]} x {limit[1]}")
+            if p.first is not None and u8:
+                raise ValueError("DevicePreprocessor: resize_u8 takes single-resize plans")
+            if p.first is not None and (p.first[0] > self.max_mid_hw[0] or p.first[1] > self.max_mid_hw[1]):
+                raise ValueError(f"DevicePreprocessor: a first resize to {p.first[0]} x {p.first[1]} exceeds max_mid_hw = {self.max_mid_hw[0]} x {self.max_mid_hw[1]}")
+        if sum(a.shape[0] * a.shape[1] for a in imgs) > self.max_src_pixels:
+            raise ValueError(f"DevicePreprocessor: {sum(a.shape[0] * a.shape[1] for a in imgs)} source pixels exceed max_src_pixels = {self.max_src_pixels}")
+        word = self._desc_bytes // 4
+        tables, where = [], {}
+
+        def place(n_in, n_out):
+            nonlocal word
+            key = (n_in, n_out)
+            if key not in where:
+                bounds, coef = _pass_tables(n_in, n_out)
+                where[key] = (word, word + bounds.size, coef.shape[1])
+                tables.append((word, bounds, coef))
+                word += bounds.size + coef.size
+            return where[key]
+
+        def stage(src_off, src_hw, stride, flip, crop, out_hw, dst_off=0):
+            t, l, ch, cw = crop if crop is not None else (0, 0, src_hw[0], src_hw[1])
+            bh, ck, kh = place(cw, out_hw[1])
+            bv, cv, kv = place(ch, out_hw[0])
+            return dict(src_off=src_off, src_h=src_hw[0], src_w=src_hw[1], src_stride=stride, flip=int(bool(flip)), crop_y=t, crop_x=l, crop_h=ch, crop_w=cw,
+                        out_h=out_hw[0], out_w=out_hw[1], ksize_h=kh, ksize_v=kv, bounds_h=bh, coef_h=ck, bounds_v=bv, coef_v=cv, dst_off=dst_off)
+
+        rows = [[{} for _ in imgs], [{} for _ in imgs]]
+        pending, mid_at = [], 0
+        for i, (a, p) in enumerate(zip(imgs, plans)):
+            hw = (p.height, p.width)
+            if u8:
+                pending.append((0, i, (hw, p.width * 3, p.flip, p.crop, p.final, mid_at)))
+                mid_at += _up(3 * p.final[0] * p.final[1], 16)
+            elif p.first is None:
+                pending.append((1, i, (hw, p.width * 3, p.flip, p.crop, p.final)))
+            else:
+                pending.append((0, i, (hw, p.width * 3, p.flip, None, p.first, mid_at)))
+                rows[1][i] = stage(self._head_bytes + mid_at, p.first, p.first[1] * 3, False, p.crop, p.final)
+                mid_at += _up(3 * p.first[0] * p.first[1], 16)
+        if mid_at > self._mid_bytes:
+            raise ValueError(f"DevicePreprocessor: {mid_at} bytes of intermediate images exceed the capacity of {self._mid_bytes} (max_mid_hw)")
+        # the tables are placed first, the pixels behind them: every offset is known once the table words are
+        for s, i, args in pending:
+            rows[s][i] = stage(0, *args)
+        if word - self._desc_bytes // 4 > self.max_table_words:
+            raise ValueError(f"DevicePreprocessor: {word - self._desc_bytes // 4} table words exceed max_table_words = {self.max_table_words}")
+        at = _up(word * 4, 16)
+        pixels = []
+        for s, i, _ in pending:
+            rows[s][i]["src_off"] = at
+            pixels.append((at, imgs[i]))
+            at += _up(imgs[i].size, 16)
+        H = _up(max(p.final[0] for p in plans), self.pad_hw)
+        W = _up(max(p.final[1] for p in plans), self.pad_hw)
+        packed = PackedBatch(len(imgs), H, W, any(rows[0][i] for i in range(len(imgs))), tuple(tuple(p.final) for p in plans))
+        return packed, rows, tables, pixels, at
+
+    def pack(self, images, plans, _u8=False, _layout=None):
+        """The batch into the arenas: pixels, descriptors and tables into the pinned buffer, then one asynchronous copy of its used head on the current
+        stream (the previous copy out of the pinned buffer is waited for first).  -> PackedBatch."""
+        packed, rows, tables, pixels, used = _layout if _layout is not None else self._layout(images, plans, _u8)
+        assert used <= self._head_bytes
+        if self._event is not None:
+            self._event.synchronize()
+        host = self._host_np
+        desc = host[:self._desc_bytes].view(np.int32).reshape(2, self.max_batch, _lib.PREP_DESC_WORDS)
+        desc[:] = 0                                             # unused slots: out_h = 0 = an empty image (padding only)
+        for s in (0, 1):
+            for i, r in enumerate(rows[s]):
+                if r:
+                    desc[s, i] = pack_descriptor(**r)
+        words = host.view(np.int32)
+        for at, bounds, coef in tables:
+            words[at:at + bounds.size] = bounds.reshape(-1)
+            words[at + bounds.size:at + bounds.size + coef.size] = coef.reshape(-1)
+        for at, a in pixels:
+            host[at:at + a.size].reshape(a.shape)[...] = a
+        self.blob[:used].copy_(self._host[:used], non_blocking=True)
+        self._event = torch.cuda.Event()
+        self._event.record()
+        self._last = packed
+        return packed
+
+    # -- device side --------------------------------------------------------------------------------------------------------------------
+    def launch(self, out=None, first_stage=None):
+        """The launches of the batch that pack() placed: the first-resize stage (when `first_stage`; None = the last pack() needs it -- pass True in
+        a captured loop whose batches may) and the final stage into `out` (default: the object's own output).  -> the capacity-sized NestedTensor."""
+        from . import kernels
+        out = self.out if out is None else out
+        Bc = int(out.tensors.shape[0])
+        if Bc > self.max_batch or (self._last is not None and Bc < self._last.batch):
+            raise ValueError(f"DevicePreprocessor: an output of {Bc} images for a batch of {self._last.batch if self._last else 0} (max_batch {self.max_batch})")
+        if first_stage is None:
+            first_stage = self._last is not None and self._last.two_stage
+        if first_stage:
+            kernels.image_prep(self.blob, self.desc[0, :Bc], self.arena, dst_u8=self.mid, cap_hw=self.max_mid_hw)
+        kernels.image_prep(self.blob, self.desc[1, :Bc], self.arena, lut=self.lut, out=out.tensors, mask=out.mask)
+        return out
+
+    def _check_out(self, out, packed):
+        if out is None:
+            return
+        t, m = out.tensors, out.mask
+        if t.dim() != 4 or t.shape[1] != 3 or m is None or tuple(m.shape) != (t.shape[0], t.shape[2], t.shape[3]) or t.dtype != torch.float32:
+            raise ValueError("DevicePreprocessor: `out` is a NestedTensor of fp32 [B, 3, Hp, Wp] with its [B, Hp, Wp] mask")
+        if t.shape[0] < packed.batch or t.shape[0] > self.max_batch or t.shape[2] < packed.height or t.shape[3] < packed.width:
+            raise ValueError(f"DevicePreprocessor: `out` {tuple(t.shape)} cannot hold {packed.batch} images of extent {packed.height} x {packed.width}")
+
+    def view(self, packed, out=None):
+        """The batch extent of a capacity-sized output as a NestedTensor of views."""
+        out = self.out if out is None else out
+        return NestedTensor(out.tensors[:packed.batch, :, :packed.height, :packed.width], out.mask[:packed.batch, :packed.height, :packed.width])
+
+    def prepare(self, images, plans, out=None):
+        layout = self._layout(images, plans, False)            # every capacity is checked before anything is copied or launched
+        self._check_out(out, layout[0])
+        packed = self.pack(images, plans, _layout=layout)
+        return self.view(packed, self.launch(out))
+
+    def resize_u8(self, images, plans):
+        """The intermediate mode on its own: flip / crop / resize of single-resize plans -> a list of uint8 [h, w, 3] device tensors (views into the
+        intermediate arena, valid until the next call), what the reference holds as a PIL image before ToTensor."""
+        packed = self.pack(images, plans, _u8=True)
+        from . import kernels
+        kernels.image_prep(self.blob, self.desc[0], self.arena, dst_u8=self.mid, cap_hw=self.max_mid_hw)
+        res, at = [], 0
+        for h, w in packed.sizes:
+            res.append(self.mid[at:at + 3 * h * w].view(h, w, 3))
+            at += _up(3 * h * w, 16)
+        return res

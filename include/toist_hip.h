@@ -766,6 +766,23 @@ TOIST_API int toist_coco_match(const double* iou, const int64_t* iou_offset, con
 TOIST_API int toist_image_prep(const uint8_t* src, long long src_bytes, const int32_t* desc, const int32_t* arena, long long arena_words, const float* lut,
                      int batch_cap, int cap_h, int cap_w, float* out, uint8_t* mask, uint8_t* dst_u8, long long dst_bytes, void* stream);
 
+/* ---- target masks on the device (replaces what the host does to a target's masks: datasets/transforms.py:62-80 hflip, 118-138 resize =
+ * F.interpolate(mode="nearest"), 18-59 crop, and the zero padding of util/misc.py:185-209).  Flip, nearest resize and crop are index maps: the host
+ * composes an image's plan into one table of source rows and one of source columns; the launch gathers single bits of the ORIGINAL-size masks into
+ * the bytes the mask losses read.  One launch per batch; every size comes from the device, so the launch can sit in a captured hipGraph.
+ * `src` = the source masks, one bit per pixel: pixel x of a row is bit (x & 31) of 32-bit word (x >> 5) (numpy packbits, bitorder "little"), rows padded
+ * to whole words, every mask 4-byte aligned.  `desc` = int32 [slots, TOIST_TMASK_DESC_WORDS], one row per slot:
+ *    0 src_off (bytes from `src`, a multiple of 4)   1 src_h   2 src_w   3 src_stride_words (32-bit words per source row)
+ *    4 out_h   5 out_w   (the prepared mask)      6 tab_y   7 tab_x   (int32 word offsets into `arena`)
+ * tab_y[out_h] = the source row of every output row, tab_x[out_w] = the source column of every output column (the flip folded in); the targets of
+ * an image share one pair.  An entry outside the source reads as 0.
+ * dst = uint8 [slots, cap_h, cap_w], values 0 / 1.  The grid covers it.  A row with out_h = 0 is a DEAD slot: nothing of it is written.  Any other
+ * slot is written completely: the gathered bit inside (out_h, out_w), 0 outside.  A row that does not fit the capacities (src_bytes, arena_words, cap_h,
+ * cap_w) gives an all-zero slot: the caller checks its sizes on the host before the launch.  Any cap_w; 16-byte stores where a row's address allows. */
+#define TOIST_TMASK_DESC_WORDS 8
+TOIST_API int toist_target_masks(const uint8_t* src, long long src_bytes, const int32_t* desc, const int32_t* arena, long long arena_words, int slots,
+                     int cap_h, int cap_w, uint8_t* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

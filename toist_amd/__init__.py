@@ -25,6 +25,9 @@ def __getattr__(name):
         "DevicePreprocessor": ("preprocess", "DevicePreprocessor"), "PrepPlan": ("preprocess", "PrepPlan"), "val_plan": ("preprocess", "val_plan"),
         "sample_train_plan": ("preprocess", "sample_train_plan"), "transform_target": ("preprocess", "transform_target"),
         "resized_size": ("preprocess", "resized_size"), "resample_tables": ("preprocess", "resample_tables"),
+        "DeviceTargetMasks": ("preprocess", "DeviceTargetMasks"), "PackedTargetMasks": ("preprocess", "PackedTargetMasks"),
+        "nearest_table": ("preprocess", "nearest_table"), "mask_index_tables": ("preprocess", "mask_index_tables"),
+        "pack_mask_bits": ("preprocess", "pack_mask_bits"), "unpack_mask_bits": ("preprocess", "unpack_mask_bits"),
     }
     if name in table:
         mod, attr = table[name]

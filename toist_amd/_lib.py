@@ -61,6 +61,7 @@ class RowGemm(Structure):
 
 XDEC_MAX_LAYERS, XDEC_CTL_WORDS = 8, 1024
 PREP_DESC_WORDS = 20          # TOIST_PREP_DESC_WORDS: int32 words of one image's row in toist_image_prep's descriptor table
+TMASK_DESC_WORDS = 8          # TOIST_TMASK_DESC_WORDS: int32 words of one slot's row in toist_target_masks' descriptor table
 
 
 class XdecLayer(Structure):
@@ -187,6 +188,7 @@ _SIGNATURES = {
     "toist_mask_rle_counts": ([c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "toist_image_prep": ([c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                          ctypes.c_longlong, c_void_p], ctypes.c_int),
+    "toist_target_masks": ([c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
 }
 
 _lib = None

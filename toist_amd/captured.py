@@ -172,6 +172,9 @@ class CapturedTrainStep(_CapturedStep):
     optimizer's device table (`optimizer.sync_hyperparams()` after changing them).
 
     step(samples, tokenized, targets, positive_map) -> total loss (device scalar, valid until the next step of the same bucket).
+    step(..., target_masks=a preprocess.DeviceTargetMasks whose pack() has run): configs[2] with the ground-truth masks prepared on the device -- the
+    targets carry "mask_size" instead of "masks" (preprocess.transform_target(masks=False)), and write_into() fills the bucket's StaticTargets.masks
+    on the step's stream after the targets' upload, outside the graph.
     The FIRST step of a new bucket runs eagerly (it is a real training step) and the graph is captured right after it, without
     executing anything; later steps of that bucket are one host-to-device copy of the inputs + one graph launch.
     Single process per GPU; with torch.distributed active the step falls back to the eager path (collectives are not captured).
@@ -212,7 +215,7 @@ class CapturedTrainStep(_CapturedStep):
         return {**static_inputs(self.batch, Hp, Wp, Lp, _pad_id(self.model), self.device), **_NO_GRAPH,
                 "targets": StaticTargets(self.batch, self.max_t, self.num_queries, 256, self.device, mask_hw=(Hp, Wp) if self.masks else None)}
 
-    def _fill(self, ent, samples, tokenized, targets, positive_map, packed):
+    def _fill(self, ent, samples, tokenized, targets, positive_map, packed, target_masks=None):
         B = samples.tensors.shape[0]
         if B != self.batch:
             raise ValueError(f"CapturedTrainStep was built for batches of {self.batch} images (got {B})")
@@ -224,6 +227,12 @@ class CapturedTrainStep(_CapturedStep):
             st.load(host_t, positive_map.cpu() if torch.is_tensor(positive_map) else positive_map, masks)
         else:
             st.load_packed(packed)
+        if target_masks is not None:
+            last = target_masks.last
+            if last is None or list(last.counts) != list(st.sizes):          # (boxes give st.sizes, "mask_rows" the counts: slot i must be target i)
+                raise ValueError(f"CapturedTrainStep: target_masks holds masks for {None if last is None else list(last.counts)} targets per image, "
+                                 f"the batch has {list(st.sizes)}: pack() the masks of THIS batch, with its \"mask_rows\"")
+            target_masks.write_into(st)        # outside the graph, like upload(): the ground-truth masks of the batch, gathered on the device
 
     def _fwd_bwd_opt(self, ent):
         from .mdetr import weighted_total
@@ -239,9 +248,14 @@ class CapturedTrainStep(_CapturedStep):
         return total
 
     # -- the step -------------------------------------------------------------------------------------------------------------------
-    def step(self, samples, tokenized, targets=None, positive_map=None, packed=None):
+    def step(self, samples, tokenized, targets=None, positive_map=None, packed=None, target_masks=None):
+        if self.masks and target_masks is None:
+            by_size = packed[2] is None if packed is not None else any("masks" not in t and "mask_size" in t for t in targets or ())
+            if by_size:
+                raise ValueError("CapturedTrainStep: the targets carry \"mask_size\" instead of \"masks\": pass target_masks= the DeviceTargetMasks "
+                                 "whose pack() holds this batch's masks")
         ent = self._entry(self.bucket_of(samples, tokenized))
-        self._fill(ent, samples, tokenized, targets, positive_map, packed)
+        self._fill(ent, samples, tokenized, targets, positive_map, packed, target_masks)
         if ent["graph"] is not None:
             ent["graph"].replay()
             self.replays += 1

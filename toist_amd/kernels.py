@@ -1033,6 +1033,23 @@ def image_prep(src, desc, arena, lut=None, out=None, mask=None, dst_u8=None, cap
                "toist_image_prep")
 
 
+def target_masks(src, desc, arena, out):
+    """The prepared masks of a batch's targets in one launch that reads every size from the device (include/toist_hip.h: toist_target_masks): a gather
+    of single bits of the original-size masks through one row table and one column table per image.  src uint8 [bytes], desc int32 [slots,
+    TMASK_DESC_WORDS], arena int32 [words]: fixed-address device buffers that toist_amd.preprocess.DeviceTargetMasks fills; out uint8 (or bool)
+    [slots, cap_h, cap_w].  A slot whose row has out_h = 0 is left as it is.  No host read, no allocation: graph-capturable."""
+    if desc.dim() != 2 or desc.shape[1] != _lib.TMASK_DESC_WORDS or not desc.is_contiguous() or not src.is_contiguous() or not arena.is_contiguous():
+        raise ValueError(f"target_masks: contiguous buffers and an int32 [slots, {_lib.TMASK_DESC_WORDS}] descriptor table")
+    S = desc.shape[0]
+    if out.dim() != 3 or out.shape[0] != S or not out.is_contiguous():
+        raise ValueError(f"target_masks: a contiguous output [{S}, cap_h, cap_w] (got {tuple(out.shape)})")
+    if out.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"target_masks: the output holds bytes (uint8 or bool), got {out.dtype}")
+    _lib.check(_lib.lib().toist_target_masks(_p(src, torch.uint8), src.numel(), _p(desc, torch.int32), _p(arena, torch.int32), arena.numel(), S,
+                                             int(out.shape[1]), int(out.shape[2]), _p(out), _stream()), "toist_target_masks")
+    return out
+
+
 def postprocess(pred_logits, pred_boxes, sizes_dev, pred_isfinal=None, out=None):
     """PostProcess in one launch (include/toist_hip.h: toist_postprocess).  pred_logits [B, Q, C] and pred_boxes [B, Q, 4] in bf16 or f32, pred_isfinal
     [B, Q] (or [B, Q, 1]) optional, sizes_dev int64 [B, 2] = (h, w) ON THE DEVICE.  -> dict(scores f32 [B, Q], boxes f32 [B, Q, 4] (+ scores_refexp));

@@ -64,21 +64,10 @@ class StaticTargets:
             self._mask_host = torch.zeros(batch * max_per_image, *self.mask_hw, dtype=torch.uint8).pin_memory()
         self.cap = cap = batch * max_per_image
         self.device = torch.device(device)
-        sizes = [cap * 4 * 4, cap * K * 4, cap * TOKEN_MASK_WORDS * 8, (batch + 1) * 4, (batch + 1) * 4, 4, 16]
-        offs, total = [], 0
-        for n in sizes:
-            offs.append(total)
-            total += (n + 15) // 16 * 16
+        self._views, total = self.arena_views(batch, cap, K)
         self._host = torch.zeros(total, dtype=torch.uint8).pin_memory()
         self._dev = torch.zeros(total, dtype=torch.uint8, device=self.device)
-
-        def views(buf):
-            cut = lambda i, dt, shape: buf[offs[i]:offs[i] + sizes[i]].view(dt).view(shape)
-            return (cut(0, torch.float32, (cap, 4)), cut(1, torch.float32, (cap, K)), cut(2, torch.int64, (cap, TOKEN_MASK_WORDS)), cut(3, torch.int32, (batch + 1,)),
-                    cut(4, torch.int32, (batch + 1,)), cut(5, torch.float32, (1,)), cut(6, torch.int32, (4,)))
-
-        self._views = views
-        self.boxes, self.positive_map, self.tok_mask, self.tgt_off, self.match_off, self._nb_local, self.valid_hw = views(self._dev)
+        self.boxes, self.positive_map, self.tok_mask, self.tgt_off, self.match_off, self._nb_local, self.valid_hw = self._views(self._dev)
         if self.mask_hw is None:
             self.valid_hw = None
         self.num_boxes = torch.ones(1, dtype=torch.float32, device=self.device)
@@ -87,10 +76,29 @@ class StaticTargets:
         self._event = None
         self.distill = None   # distill.DistillTables of this side of a (noun, pronoun) pair: the captured distillation step (harness.CapturedDistillStep)
 
+    @staticmethod
+    def arena_views(batch, cap, K):
+        """The arena layout (class docstring) as host code: -> (views(buf) = the seven typed views of a uint8 buffer of `total` bytes, total)."""
+        sizes = [cap * 4 * 4, cap * K * 4, cap * TOKEN_MASK_WORDS * 8, (batch + 1) * 4, (batch + 1) * 4, 4, 16]
+        offs, total = [], 0
+        for n in sizes:
+            offs.append(total)
+            total += (n + 15) // 16 * 16
+
+        def views(buf):
+            cut = lambda i, dt, shape: buf[offs[i]:offs[i] + sizes[i]].view(dt).view(shape)
+            return (cut(0, torch.float32, (cap, 4)), cut(1, torch.float32, (cap, K)), cut(2, torch.int64, (cap, TOKEN_MASK_WORDS)), cut(3, torch.int32, (batch + 1,)),
+                    cut(4, torch.int32, (batch + 1,)), cut(5, torch.float32, (1,)), cut(6, torch.int32, (4,)))
+
+        return views, total
+
     def pack(self, targets, positive_map, token_masks=None, out=None):
         """Host image of one batch (pinned uint8 tensor in the arena layout, + the per-image target counts): build it ahead of time -- in a
         loader worker -- and hand it to load_packed().  targets: list of dicts with HOST tensors `boxes` [T_i, 4]; positive_map: host
-        [sum T_i, K]; token_masks: host int64 [sum T_i, TOKEN_MASK_WORDS] (SetCriterion.token_masks_host) when the contrastive-alignment loss is on."""
+        [sum T_i, K]; token_masks: host int64 [sum T_i, TOKEN_MASK_WORDS] (SetCriterion.token_masks_host) when the contrastive-alignment loss is on.
+        With mask_hw the targets carry `masks` [T_i, h, w] -- or, all of them, `mask_size` (h, w) INSTEAD (preprocess.transform_target(masks=False)):
+        valid_hw is fed from that size, no mask bytes are staged (the third entry of the result is None) and load_packed() copies none:
+        preprocess.DeviceTargetMasks.write_into fills `masks` on the device."""
         sizes = [int(t["boxes"].shape[0]) for t in targets]
         if len(sizes) != self.B or max(sizes, default=0) > self.max_per_image:
             raise ValueError(f"StaticTargets holds {self.B} images x <= {self.max_per_image} targets; got sizes {sizes}")
@@ -112,6 +120,19 @@ class StaticTargets:
         if self.mask_hw is None:
             return host, sizes
         TH, TW = self.mask_hw
+        by_size = ["masks" not in t and "mask_size" in t for t in targets]
+        if any(by_size):
+            # the masks are written on the device (preprocess.DeviceTargetMasks.write_into): the targets carry their prepared size only
+            if not all(by_size):
+                raise ValueError("StaticTargets: some targets of the batch carry \"masks\" and others \"mask_size\"")
+            vh, vw = 0, 0
+            for t in targets:
+                h, w = (int(v) for v in t["mask_size"])
+                if h > TH or w > TW:
+                    raise ValueError(f"StaticTargets(mask_hw={self.mask_hw}) got a mask_size of {h} x {w}")
+                vh, vw = max(vh, h), max(vw, w)
+            hvalid[0], hvalid[1], hvalid[2], hvalid[3] = vh, vw, self.mask_pred_of(vh), self.mask_pred_of(vw)
+            return host, sizes, None
         mh = self._mask_host if out is not None else torch.zeros(self.cap, TH, TW, dtype=torch.uint8).pin_memory()
         row, vh, vw = 0, 0, 0
         for t in targets:
@@ -135,7 +156,7 @@ class StaticTargets:
         self._dev.copy_(host, non_blocking=True)
         if self.mask_hw is not None:
             tot = sum(sizes)
-            if tot:
+            if tot and packed[2] is not None:          # (None: "mask_size" targets, the masks are written on the device)
                 self.masks[:tot].copy_(packed[2][:tot], non_blocking=True)
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             self.num_boxes.copy_(self._nb_local)

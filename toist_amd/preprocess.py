@@ -7,7 +7,11 @@ The host keeps what is cheap and per image: the size rule, the random decisions 
 resampler is integer arithmetic on coefficients computed in double precision: resample_tables restates that computation in numpy float64,
 the kernel does the integer passes, so the prepared pixels EQUAL the reference's (tests/golden/preprocess.npz is Pillow's own output).
 
-There is no CPU path: DevicePreprocessor on a CPU device raises, like misc.DeviceStager."""
+The masks of the targets (configs[2]) go the same way: flip, nearest resize and crop are index maps that compose into one row table and one column
+table per image (mask_index_tables); DeviceTargetMasks sends the masks at their original size with one bit per pixel and ONE launch
+(csrc/tmask.hip: toist_target_masks) gathers them into the bytes the mask losses read -- the bytes transform_target's torch ops produce.
+
+There is no CPU path: DevicePreprocessor and DeviceTargetMasks on a CPU device raise, like misc.DeviceStager."""
 import functools
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -184,7 +188,7 @@ def _t_crop(t, region):
     t = dict(t)
     i, j, h, w = region
     t["size"] = torch.tensor([h, w])
-    fields = ["labels", "area", "iscrowd", "positive_map", "isfinal"]
+    fields = ["labels", "area", "iscrowd", "positive_map", "isfinal", "mask_rows"]
     if "boxes" in t:
         b = t["boxes"] - torch.as_tensor([j, i, j, i])
         b = torch.min(b.reshape(-1, 2, 2), torch.as_tensor([w, h], dtype=torch.float32)).clamp(min=0)
@@ -206,11 +210,23 @@ def _t_crop(t, region):
     return t
 
 
-def transform_target(target, plan):
+def transform_target(target, plan, masks=True):
     """What the reference's transforms do to a target dict along `plan` (transforms.py hflip 62-80, resize 118-138, crop 18-59, Normalize 262-273), on
     the host: boxes (xyxy in, cxcywh / (w, h, w, h) out), area, size, masks (flip, nearest resize, slice: torch ops) and caption (left <-> right on a
-    flip); after a crop the boxes of zero area go, with their rows of labels, area, iscrowd, positive_map, isfinal and masks.  The input is not changed."""
+    flip); after a crop the boxes of zero area go, with their rows of labels, area, iscrowd, positive_map, isfinal and masks.  The input is not changed.
+    masks=False leaves the pixels of "masks" to the device (DeviceTargetMasks): the entry is neither read nor produced; the result carries "mask_rows"
+    (int64: the source rows of "masks" that survive the crop's keep rule, all of them without a crop) and "mask_size" (plan.final as (h, w)) instead.
+    The keep rule of a target with masks but no boxes reads the pixels (transforms.py crop: masks.flatten(1).any(1)): that stays a host job, and
+    masks=False raises ValueError for a crop on such a target."""
     t = dict(target)
+    by_size = not masks and "masks" in t
+    if by_size:
+        if plan.crop is not None and "boxes" not in t:
+            raise ValueError("transform_target(masks=False): a crop on a target with masks but no boxes keeps the targets whose CROPPED mask is "
+                             "not empty -- that rule reads the pixels, transform it with masks=True")
+        n = len(t["boxes"]) if "boxes" in t else int(t["masks"].shape[0])
+        del t["masks"]
+        t["mask_rows"] = torch.arange(n, dtype=torch.int64)
     hw = (plan.height, plan.width)
     if plan.flip:
         t = _t_hflip(t, plan.width)
@@ -224,7 +240,76 @@ def transform_target(target, plan):
     if "boxes" in t:
         h, w = plan.final
         t["boxes"] = box_xyxy_to_cxcywh(t["boxes"]) / torch.tensor([w, h, w, h], dtype=torch.float32)
+    if by_size:
+        t["mask_size"] = (int(plan.final[0]), int(plan.final[1]))
     return t
+
+
+# ---- target masks: index tables and packed bits (host) ---------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=512)
+def _cached_nearest(n_in, n_out):
+    scale = np.float32(n_in) / np.float32(n_out)
+    t = np.minimum(np.floor(np.arange(n_out, dtype=np.float32) * scale), np.float32(n_in - 1)).astype(np.int32)
+    t.setflags(write=False)
+    return t
+
+
+def nearest_table(n_in, n_out):
+    """The source index F.interpolate(mode="nearest") picks for every output index of an axis resized from n_in to n_out: int32 [n_out] =
+    min(floor(float32(i) * (float32(n_in) / float32(n_out))), n_in - 1), the product formed in float32 as torch forms it.  (Read-only: cached.)"""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"nearest_table: extents must be positive (got {n_in} -> {n_out})")
+    return _cached_nearest(n_in, n_out)
+
+
+def mask_index_tables(plan):
+    """flip -> first resize -> crop -> final resize of a mask as ONE gather: -> (ty int32 [final_h], tx int32 [final_w]), the source row of every
+    prepared row and the source column of every prepared column, so that prepared = source[:, ty][:, :, tx] equals transform_target's masks bit for
+    bit.  Each step is an index map; they compose by indexing one table with the next, the flip last (on source columns: width - 1 - x)."""
+    h, w = (plan.crop[2], plan.crop[3]) if plan.crop is not None else plan.first if plan.first is not None else (plan.height, plan.width)
+    ty, tx = nearest_table(h, plan.final[0]), nearest_table(w, plan.final[1])
+    if plan.crop is not None:
+        ty, tx = ty + np.int32(plan.crop[0]), tx + np.int32(plan.crop[1])
+    if plan.first is not None:
+        ty, tx = nearest_table(plan.height, plan.first[0])[ty], nearest_table(plan.width, plan.first[1])[tx]
+    if plan.flip:
+        tx = np.int32(plan.width - 1) - tx
+    return np.ascontiguousarray(ty, dtype=np.int32), np.ascontiguousarray(tx, dtype=np.int32)
+
+
+def _mask_array(masks):
+    a = masks.detach().cpu().numpy() if torch.is_tensor(masks) else np.asarray(masks)
+    if a.dtype not in (np.bool_, np.uint8) or a.ndim != 3:
+        raise ValueError(f"target masks are bool or uint8 [n, h, w] (got {a.dtype} {a.shape})")
+    return a
+
+
+def _pack_bits(a):
+    n, h, w = a.shape
+    b = a if a.dtype == np.bool_ else a != 0
+    if w % 32:
+        padded = np.zeros((n, h, 32 * ((w + 31) // 32)), dtype=np.bool_)
+        padded[:, :, :w] = b
+        b = padded
+    return np.packbits(b, axis=-1, bitorder="little")
+
+
+def pack_mask_bits(masks):
+    """bool or uint8 [n, h, w] (a host tensor or an ndarray; non-zero = set) -> uint8 [n, h, 4 * ceil(w / 32)] of the same kind: one bit per pixel, pixel
+    x of a row = bit (x & 31) of its 32-bit little-endian word (x >> 5), rows padded with zero bits to whole words: the source format of toist_target_masks."""
+    bits = _pack_bits(_mask_array(masks))
+    return torch.from_numpy(bits) if torch.is_tensor(masks) else bits
+
+
+def unpack_mask_bits(bits, width):
+    """The inverse of pack_mask_bits: uint8 [n, h, 4 * ceil(width / 32)] -> bool [n, h, width] of the same kind."""
+    a = bits.detach().cpu().numpy() if torch.is_tensor(bits) else np.asarray(bits)
+    width = int(width)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 * ((width + 31) // 32):
+        raise ValueError(f"unpack_mask_bits: uint8 [n, h, {4 * ((width + 31) // 32)}] for a width of {width} (got {a.dtype} {a.shape})")
+    m = np.unpackbits(a, axis=-1, bitorder="little")[:, :, :width].astype(np.bool_)
+    return torch.from_numpy(m) if torch.is_tensor(bits) else m
 
 
 # ---- the packed descriptor -------------------------------------------------------------------------------------------------------------------
@@ -467,4 +552,179 @@ class DevicePreprocessor:
         for h, w in packed.sizes:
             res.append(self.mid[at:at + 3 * h * w].view(h, w, 3))
             at += _up(3 * h * w, 16)
+        return res
+
+
+# ---- target masks on the device ----------------------------------------------------------------------------------------------------------------
+TMASK_DESC_FIELDS = ("src_off", "src_h", "src_w", "src_stride_words", "out_h", "out_w", "tab_y", "tab_x")
+assert len(TMASK_DESC_FIELDS) == _lib.TMASK_DESC_WORDS
+
+
+@dataclass(frozen=True)
+class PackedTargetMasks:
+    """What DeviceTargetMasks.pack() placed: the live slots (surviving targets of the batch, in target order), the surviving targets and the prepared
+    (h, w) of every image, and the bytes of the one host-to-device copy."""
+    slots: int
+    counts: tuple
+    sizes: tuple
+    link_bytes: int
+
+
+class DeviceTargetMasks:
+    """The masks of a batch's targets at their ORIGINAL size + PrepPlans -> the prepared masks (flip, nearest resize, crop, zero padding), on the device.
+
+    The host link carries one bit per source pixel; one launch (csrc/tmask.hip: toist_target_masks) gathers the bits through one row table and one
+    column table per image (mask_index_tables) into the uint8 [slots, Hp, Wp] image that the mask losses read (matcher.StaticTargets.masks).  The
+    loader side transforms its targets with transform_target(target, plan, masks=False) and keeps the source masks.
+    Owns fixed-address device memory -- one blob: the descriptor table [max_batch * max_targets_per_image, TMASK_DESC_WORDS], the index tables, the
+    packed bits -- and its pinned host image.
+      pack(masks_per_image, plans, rows_per_image=None) : fills the pinned image and issues ONE asynchronous host-to-device copy of its used head on
+                              the current stream -> PackedTargetMasks.  masks_per_image[i] = bool / uint8 [n_i, plans[i].height, plans[i].width];
+                              rows_per_image[i] = the "mask_rows" of transform_target(masks=False): only those masks are uploaded, in that order.
+                              Slots are the surviving targets in target order across the batch (StaticTargets' order); an image without targets
+                              takes none.
+      write_into(static_targets) : one launch into static_targets.masks; sizes come from the device only, so it can be captured once and replayed
+                              after every pack().  Slots behind the batch's targets are not written.
+      dense(packed)         : list of bool [n_i, h_i, w_i] device tensors (the list-of-dicts criterion's "masks").
+    Every capacity (max_batch, max_targets_per_image, max_src_pixels = source pixels summed over the surviving masks with every row counted in whole
+    32-pixel words, max_out_hw, the table words) is checked on the host and raises ValueError before anything is copied or launched."""
+
+    def __init__(self, device, max_batch, max_targets_per_image, max_src_pixels, max_out_hw, max_table_words=None):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceTargetMasks prepares masks in GPU memory: there is no CPU path")
+        self._set_capacities(max_batch, max_targets_per_image, max_src_pixels, max_out_hw, max_table_words)
+        self.blob = torch.zeros(self._blob_bytes, dtype=torch.uint8, device=self.device)
+        self.desc = self.blob[:self._desc_bytes].view(torch.int32).view(self.max_slots, _lib.TMASK_DESC_WORDS)
+        self.arena = self.blob.view(torch.int32)              # table offsets are int32 words from the blob's start
+        self._host = torch.zeros(self._blob_bytes, dtype=torch.uint8).pin_memory()
+        self._host_np = self._host.numpy()
+        self._dense = None                                    # uint8 [max_slots, *max_out_hw], on the first dense()
+        self._event = None
+        self.last = None                                      # the PackedTargetMasks of the last pack()
+
+    def _set_capacities(self, max_batch, max_targets_per_image, max_src_pixels, max_out_hw, max_table_words=None):
+        """The capacities and the byte layout they imply (host only)."""
+        self.max_batch, self.max_targets_per_image, self.max_src_pixels = int(max_batch), int(max_targets_per_image), int(max_src_pixels)
+        self.max_out_hw = (int(max_out_hw[0]), int(max_out_hw[1]))
+        if self.max_batch <= 0 or self.max_targets_per_image <= 0 or self.max_src_pixels <= 0 or min(self.max_out_hw) <= 0:
+            raise ValueError("DeviceTargetMasks: capacities must be positive")
+        self.max_slots = self.max_batch * self.max_targets_per_image
+        self.max_table_words = int(max_table_words) if max_table_words is not None else self.max_batch * sum(self.max_out_hw)    # one pair per image
+        self._desc_bytes = self.max_slots * _lib.TMASK_DESC_WORDS * 4
+        self._blob_bytes = _up(self._desc_bytes + 4 * self.max_table_words + (self.max_src_pixels + 7) // 8, 16)
+        if self.max_slots > 65535 or self._blob_bytes >= 2 ** 31:
+            raise ValueError("DeviceTargetMasks: at most 65535 slots, and the blob is addressed with 31 bits")
+
+    # -- host side ----------------------------------------------------------------------------------------------------------------------
+    def _layout(self, masks_per_image, plans, rows_per_image=None):
+        """Host check + placement of a batch: -> (PackedTargetMasks, descriptor dicts of the live slots, [(word, table)], [(byte, source masks)], used
+        bytes).  Raises ValueError on any capacity overrun; touches no buffer."""
+        if len(masks_per_image) != len(plans) or not plans:
+            raise ValueError(f"DeviceTargetMasks: {len(masks_per_image)} mask stacks for {len(plans)} plans (at least one)")
+        if len(plans) > self.max_batch:
+            raise ValueError(f"DeviceTargetMasks: a batch of {len(plans)} exceeds max_batch = {self.max_batch}")
+        if rows_per_image is not None and len(rows_per_image) != len(plans):
+            raise ValueError(f"DeviceTargetMasks: {len(rows_per_image)} row lists for {len(plans)} plans")
+        stacks = []
+        for i, (m, p) in enumerate(zip(masks_per_image, plans)):
+            a = _mask_array(m)
+            if a.shape[0] and a.shape[1:] != (p.height, p.width):
+                raise ValueError(f"DeviceTargetMasks: {a.shape[1]} x {a.shape[2]} masks with a plan for {p.height} x {p.width}")
+            if rows_per_image is not None:
+                rows = np.asarray(rows_per_image[i].cpu() if torch.is_tensor(rows_per_image[i]) else rows_per_image[i], dtype=np.int64).reshape(-1)
+                if rows.size and (rows.min() < 0 or rows.max() >= a.shape[0]):
+                    raise ValueError(f"DeviceTargetMasks: mask rows {rows.tolist()} of an image with {a.shape[0]} masks")
+                a = a[rows]
+            if a.shape[0] > self.max_targets_per_image:
+                raise ValueError(f"DeviceTargetMasks: {a.shape[0]} targets of one image exceed max_targets_per_image = {self.max_targets_per_image}")
+            if p.final[0] > self.max_out_hw[0] or p.final[1] > self.max_out_hw[1]:
+                raise ValueError(f"DeviceTargetMasks: a prepared size of {p.final[0]} x {p.final[1]} exceeds the capacity {self.max_out_hw[0]} x {self.max_out_hw[1]}")
+            stacks.append(a)
+        stride = lambda p: (p.width + 31) // 32
+        pixels = sum(a.shape[0] * p.height * stride(p) * 32 for a, p in zip(stacks, plans))
+        if pixels > self.max_src_pixels:
+            raise ValueError(f"DeviceTargetMasks: {pixels} source pixels (rows in whole 32-pixel words) exceed max_src_pixels = {self.max_src_pixels}")
+        word = self._desc_bytes // 4
+        tables, where = [], []
+        for a, p in zip(stacks, plans):
+            if not a.shape[0]:
+                where.append(None)
+                continue
+            ty, tx = mask_index_tables(p)
+            where.append((word, word + ty.size))
+            tables.append((word, ty))
+            tables.append((word + ty.size, tx))
+            word += ty.size + tx.size
+        if word - self._desc_bytes // 4 > self.max_table_words:
+            raise ValueError(f"DeviceTargetMasks: {word - self._desc_bytes // 4} table words exceed max_table_words = {self.max_table_words}")
+        at = word * 4
+        rows, bits = [], []
+        for a, p, tab in zip(stacks, plans, where):
+            if tab is None:
+                continue
+            bits.append((at, a))
+            for _ in range(a.shape[0]):
+                rows.append(dict(src_off=at, src_h=p.height, src_w=p.width, src_stride_words=stride(p), out_h=p.final[0], out_w=p.final[1],
+                                 tab_y=tab[0], tab_x=tab[1]))
+                at += p.height * stride(p) * 4
+        packed = PackedTargetMasks(len(rows), tuple(a.shape[0] for a in stacks), tuple((int(p.final[0]), int(p.final[1])) for p in plans), at)
+        return packed, rows, tables, bits, at
+
+    def pack(self, masks_per_image, plans, rows_per_image=None):
+        """The batch into the blob: descriptors, tables and packed bits into the pinned image, then one asynchronous copy of its used head on the
+        current stream (the previous copy out of the pinned image is waited for first).  -> PackedTargetMasks."""
+        packed, rows, tables, bits, used = self._layout(masks_per_image, plans, rows_per_image)
+        assert used <= self._blob_bytes and packed.slots <= self.max_slots
+        if self._event is not None:
+            self._event.synchronize()
+        host = self._host_np
+        desc = host[:self._desc_bytes].view(np.int32).reshape(self.max_slots, _lib.TMASK_DESC_WORDS)
+        desc[:] = 0                                             # slots behind the batch's targets: out_h = 0 = dead, not written
+        for i, r in enumerate(rows):
+            desc[i] = [r[name] for name in TMASK_DESC_FIELDS]
+        words = host.view(np.int32)
+        for at, table in tables:
+            words[at:at + table.size] = table
+        for at, a in bits:
+            b = _pack_bits(a)
+            host[at:at + b.size] = b.reshape(-1)
+        self.blob[:used].copy_(self._host[:used], non_blocking=True)
+        self._event = torch.cuda.Event()
+        self._event.record()
+        self.last = packed
+        return packed
+
+    # -- device side --------------------------------------------------------------------------------------------------------------------
+    def write_into(self, static_targets):
+        """One launch of the batch that pack() placed into static_targets.masks (matcher.StaticTargets(mask_hw=...)): its first PackedTargetMasks.slots
+        slots are written completely (zeros outside each mask), the others are left alone."""
+        from . import kernels
+        out = static_targets.masks
+        if out is None:
+            raise ValueError("DeviceTargetMasks: the StaticTargets was built without mask_hw")
+        slots, Hp, Wp = (int(v) for v in out.shape)
+        if slots > self.max_slots:
+            raise ValueError(f"DeviceTargetMasks: a StaticTargets of {slots} slots exceeds max_batch * max_targets_per_image = {self.max_slots}")
+        if self.last is not None:
+            if self.last.slots > slots:
+                raise ValueError(f"DeviceTargetMasks: the packed batch has {self.last.slots} targets, the StaticTargets holds {slots}")
+            if self.last.slots and any(h > Hp or w > Wp for (h, w), n in zip(self.last.sizes, self.last.counts) if n):
+                raise ValueError(f"DeviceTargetMasks: prepared masks of {self.last.sizes} do not fit mask_hw = {Hp} x {Wp}")
+        kernels.target_masks(self.blob, self.desc[:slots], self.arena, out)
+        return static_targets
+
+    def dense(self, packed):
+        """The prepared masks of the batch that pack() returned `packed` for, per image: bool [n_i, h_i, w_i] device tensors, copies cut from an internal
+        [max_slots, *max_out_hw] output that the next call overwrites."""
+        from . import kernels
+        if packed is not self.last:
+            raise ValueError("DeviceTargetMasks.dense: `packed` is not the batch of the last pack()")
+        if self._dense is None:
+            self._dense = torch.zeros(self.max_slots, *self.max_out_hw, dtype=torch.uint8, device=self.device)
+        kernels.target_masks(self.blob, self.desc, self.arena, self._dense)
+        res, at = [], 0
+        for n, (h, w) in zip(packed.counts, packed.sizes):
+            res.append(self._dense[at:at + n, :h, :w].to(torch.bool))
+            at += n
         return res

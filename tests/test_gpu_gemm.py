@@ -224,6 +224,30 @@ def test_small_channel_conv_direct_kernel(dev, C, Co):
         _close(dx, _nhwc(xr.grad + prev.float()), Co * 9, "small conv dgrad")
 
 
+@pytest.mark.parametrize("C,Co", [(16, 8), (32, 16)])
+def test_small_channel_wgrad_twice_into_one_output_before_the_flush(dev, C, Co):
+    """Four deferred kernels.wgrad3x3_small calls into the outputs A, A, B, C and one flush: the second call into A makes the queue fold the first
+    ahead of it, and no later call may be handed partials space whose fold is still queued.  Each fold is a complete sum over the per-workgroup
+    partials added to the output with factor 1.0, so the result EQUALS the calls folded alone into zeros and added in call order."""
+    from toist_amd import kernels as k
+    g = torch.Generator().manual_seed(C * 100 + Co)
+    calls = [(_rand((2, 12, 10, Co), g).to(dev), _rand((2, 12, 10, C), g).to(dev)) for _ in range(4)]
+    alone = []
+    for dy, x in calls:
+        s = torch.zeros(Co, 3, 3, C, device=dev)
+        k.wgrad3x3_small(dy, x, s, defer=False, accumulate=True)
+        assert float(s.abs().max()) > 0
+        alone.append(s)
+    base = [torch.randn(Co, 3, 3, C, generator=g).to(dev) for _ in range(3)]
+    A, B, C_ = (b.clone() for b in base)
+    for (dy, x), out in zip(calls, (A, A, B, C_)):
+        k.wgrad3x3_small(dy, x, out, defer=True, accumulate=True)
+    k.flush_reductions()
+    assert torch.equal(A, (base[0] + alone[0]) + alone[1])
+    assert torch.equal(B, base[1] + alone[2])
+    assert torch.equal(C_, base[2] + alone[3])
+
+
 def test_attention_products(dev):
     from toist_amd import kernels as k, ops
     g = torch.Generator().manual_seed(5)

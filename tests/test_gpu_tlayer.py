@@ -115,6 +115,55 @@ def test_rowgemm_layernorm_backward(dev, M, K, parts):
     _close(dzd, want, "masked dz", rtol=8e-3, atol=1e-5)
 
 
+def _added_in_call_order(run, dev):
+    """run(i, dgamma, dbeta) queues call i's LayerNorm parameter-gradient folds.  Both calls into one pair of outputs and one flush must EQUAL each call
+    folded alone into zeros, added to the outputs' contents in call order (a fold is a complete sum over the per-block partials, added with factor 1.0)."""
+    from toist_amd import kernels as k
+    alone = []
+    for i in range(2):
+        dg, db = torch.zeros(256, device=dev), torch.zeros(256, device=dev)
+        run(i, dg, db)
+        k.flush_reductions()
+        assert float(dg.abs().max()) > 0 and float(db.abs().max()) > 0
+        alone.append((dg, db))
+    dgamma, dbeta = torch.full((256,), 0.25, device=dev), torch.full((256,), -0.5, device=dev)
+    run(0, dgamma, dbeta)
+    run(1, dgamma, dbeta)        # the outputs have queued folds: those are folded ahead of this call's
+    k.flush_reductions()
+    assert torch.equal(dgamma, (0.25 + alone[0][0]) + alone[1][0])
+    assert torch.equal(dbeta, (-0.5 + alone[0][1]) + alone[1][1])
+
+
+def test_layernorm_backward_twice_into_one_gradient_before_the_flush(dev):
+    from toist_amd import kernels as k
+    g = torch.Generator().manual_seed(11)
+    rows, D = 300, 256
+    x = _bf(torch.randn(rows, D, generator=g) * 2 + 0.3).to(dev)
+    gamma, beta = (torch.rand(D, generator=g) + 0.5).to(dev), torch.zeros(D, device=dev)
+    y, dx = torch.empty_like(x), torch.empty_like(x)
+    mean, rstd = torch.empty(rows, device=dev), torch.empty(rows, device=dev)
+    k.layernorm_fwd(x, gamma, beta, 1e-5, y, mean, rstd)
+    dys = [_bf(torch.randn(rows, D, generator=g)).to(dev) for _ in range(2)]
+    assert k.LN_DEFER
+    _added_in_call_order(lambda i, dg, db: k.layernorm_bwd(dys[i], x, mean, rstd, gamma, dx, dg, db, defer=True), dev)
+
+
+def test_rowgemm_layernorm_backward_twice_into_one_gradient_before_the_flush(dev):
+    from toist_amd import kernels as k
+    g = torch.Generator().manual_seed(12)
+    M, K = 300, 256
+    w = _bf(torch.randn(K, 256, generator=g) / math.sqrt(K)).to(dev)
+    z = _bf(torch.randn(M, 256, generator=g) * 2 + 0.3)
+    zz = z.float()
+    mu = zz.mean(1)
+    rs = (((zz - mu[:, None]) ** 2).mean(1) + 1e-5).rsqrt()
+    z, mu, rs, gamma = z.to(dev), mu.to(dev), rs.to(dev), (torch.rand(256, generator=g) + 0.5).to(dev)
+    grads = [_bf(torch.randn(M, K, generator=g)).to(dev) for _ in range(2)]
+    dz = torch.empty(M, 256, dtype=BF, device=dev)
+    _added_in_call_order(lambda i, dg, db: k.rowgemm(grads[i], w, dz, b_kind=k.B_KROW, epi=k.ROW_LN_BWD, gamma=gamma, z=z, mean=mu, rstd=rs,
+                                                     dgamma=dg, dbeta=db), dev)
+
+
 def test_rowgemm_plain(dev):
     from toist_amd import kernels as k
     g = torch.Generator().manual_seed(5)

@@ -10,6 +10,7 @@ import os
 import torch
 
 from . import _lib
+from .folds import FOLDS, _raw_stream
 from .knobs import knob
 from ._lib import (A_CONV, A_CONVT, A_KROW, A_ROWK, ACT_GELU, ACT_GELU_BWD, ACT_MASK_POS, ACT_NONE, ACT_RELU,
                    ACT_SIGMOID, ACT_SIGMOID_BWD, B_CONVX, B_KROW, B_ROWK, Epilogue, Gemm, Operand)
@@ -51,47 +52,15 @@ def _workspace(elems, device):
 # ---- deferred split-K reductions -----------------------------------------------------------------------------
 # A weight-gradient GEMM with few output tiles is cut into k-slices whose fp32 partials land in an arena; with
 # defer_reduce=True the fold into the gradient buffer is not launched per GEMM (178 launches of ~6 us per step) but
-# queued, and flush_reductions() folds everything queued on the current stream with one launch per 48 GEMMs.
-# The queue must be flushed before anything reads those outputs: engine.Tape.backward() does it at program end.
+# queued (toist_amd/folds.py).  The queue must be flushed before anything reads those outputs: engine.Tape.backward() does it at program end.
 GEMM_DEFER_REDUCE = 2
 GEMM_SPLIT_EPILOGUE = 4
 GEMM_COLSUM_SLICES = 32768    # include/toist_hip.h: a_colsum = [k-slice][M] partials, folded in slice order
-_ARENA = {}     # (device, stream) -> [buffer, used elements]
-_PENDING = {}   # (device, stream) -> list of (ReduceDesc, keep-alive tensors)
-
-
-def _arena_take(elems, device):
-    key = (device, _raw_stream())
-    ent = _ARENA.get(key)
-    elems = (elems + 63) // 64 * 64
-    if ent is None or ent[1] + elems > ent[0].numel():
-        flush_reductions()                      # queued descriptors point into the old arena
-        size = max(elems, 1 << 26 if ent is None else 2 * ent[0].numel())
-        ent = _ARENA[key] = [torch.empty(size, dtype=torch.float32, device=device), 0]
-    off = ent[1]
-    ent[1] += elems
-    return ent[0][off:off + elems]
 
 
 def flush_reductions():
     """Fold every queued split-K partial of the current stream into its output (one launch per 48 GEMMs)."""
-    if not torch.cuda.is_available():
-        return
-    key_s = _raw_stream()
-    for key in [kk for kk in _PENDING if kk[1] == key_s]:
-        items = _PENDING.pop(key)
-        if items:
-            arr = (_lib.ReduceDesc * len(items))(*[it[0] for it in items])
-            _lib.check(_lib.lib().toist_splitk_reduce_batch(ctypes.cast(arr, ctypes.c_void_p), len(items), _stream()), "toist_splitk_reduce_batch")
-        ent = _ARENA.get(key)
-        if ent is not None:
-            ent[1] = 0
-
-
-def _fold_now(rd):
-    """Fold one split-K descriptor at once, on the current stream (not queued)."""
-    arr = (_lib.ReduceDesc * 1)(rd)
-    _lib.check(_lib.lib().toist_splitk_reduce_batch(ctypes.cast(arr, ctypes.c_void_p), 1, _stream()), "toist_splitk_reduce_batch")
+    FOLDS.flush()
 
 
 GROUP_MAX = 64
@@ -194,12 +163,6 @@ class tables_beside_graph:
         return False
 
 
-def _raw_stream():
-    """hipStream_t of torch's current stream as an int.  torch.cuda.current_stream() builds a Stream object through three
-    Python layers (~9 us): at ~1500 launches per step that alone was 13 ms of host time; the C accessor takes ~0.3 us."""
-    return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
-
-
 def _stream():
     return ctypes.c_void_p(_raw_stream())
 
@@ -274,42 +237,25 @@ def gemm(M, N, K, a_kind, a, b_kind, b, c, ldc, *, batch=1, batch_inner=1, cs_ou
     d.group = _p(group, torch.int64)          # [batch, 6] int64 rows (a, b pointers; c, rscale, colsum, shift offsets): toist_group
     if a2 is not None:                        # output columns >= a2_from take their A rows from a2 (packed in_proj on two inputs)
         d.a2, d.a2_from = _p(a2, torch.bfloat16), a2_from
-    deferred = None
+    folds = []      # queued behind the launch: the column sums' fold first, then one per output
     if split_k > 1 and split_epilogue:
         # k-slices folded by a second kernel that applies the complete epilogue (any output type): csrc/gemm.hip splitk_epilogue_kernel
         d.workspace = _p(_workspace(split_k * M * N, c.device), torch.float32)
         d.flags |= GEMM_SPLIT_EPILOGUE
-    elif split_k > 1 and group is not None:
-        # grouped + split: [problem][k-slice][M][N] partials, one queued fold per problem (group_out = [(c_i, rscale_i)])
-        eff = int(_lib.lib().toist_gemm_effective_split(ctypes.byref(d)))
-        if eff > 1:
-            key = (c.device, _raw_stream())
-            outs = {ci.data_ptr() for ci, _ in group_out}
-            if any(it[0].out in outs for it in _PENDING.get(key, ())):
-                flush_reductions()
-            ws = _arena_take(eff * M * N * batch, c.device)
-            d.workspace = _p(ws, torch.float32)
-            d.flags |= GEMM_DEFER_REDUCE
-            for i, (ci, ri) in enumerate(group_out):
-                rd = _lib.ReduceDesc(ws.data_ptr() + 4 * i * eff * M * N, ci.data_ptr(), _p(ri, torch.float32), eff, M, N, ldc, alpha, 1 if accumulate else 0)
-                _PENDING.setdefault(key, []).append((rd, (ci, ri)))
-        else:
-            d.split_k = 1
     elif split_k > 1:
-        eff = int(_lib.lib().toist_gemm_effective_split(ctypes.byref(d))) if defer_reduce else 0
+        # grouped + split: [problem][k-slice][M][N] partials, one queued fold per problem (group_out = [(c_i, rscale_i)]); else one fold when deferred
+        outs = group_out if group is not None else [(c, rscale)] if defer_reduce else ()
+        eff = int(_lib.lib().toist_gemm_effective_split(ctypes.byref(d))) if outs else 0
         if eff > 1:
-            # a second deferred reduction into the same output would race with the queued one: fold first
-            key = (c.device, _raw_stream())
-            if any(it[0].out == c.data_ptr() for it in _PENDING.get(key, ())):
-                flush_reductions()
-            ws = _arena_take(eff * M * N, c.device)
+            ws = FOLDS.acquire(eff * M * N * (batch if group is not None else 1), c.device, [ci for ci, _ in outs])
             d.workspace = _p(ws, torch.float32)
             d.flags |= GEMM_DEFER_REDUCE
-            rd = _lib.ReduceDesc(ws.data_ptr(), c.data_ptr(), _p(rscale, torch.float32), eff, M, N, ldc, alpha, 1 if accumulate else 0)
-            deferred = (key, (rd, (c, rscale)))
+            folds = [dict(ws=ws.data_ptr() + 4 * i * eff * M * N, out=ci, rscale=ri, splits=eff, M=M, N=N, ldc=ldc, alpha=alpha, accumulate=accumulate)
+                     for i, (ci, ri) in enumerate(outs)]
+        elif group is not None:
+            d.split_k = 1
         else:
             d.workspace = _p(_workspace(split_k * M * N, c.device), torch.float32)
-    colsum_now = None
     if a_colsum is not None and split_k > 1 and group is None and not split_epilogue:
         # the bias gradient of a split-K weight-gradient GEMM: each k-slice stores its column sums in a row of its own and one fold adds
         # the rows in slice order -- float atomics would add them in whatever order the slices finish, a different sum in every run
@@ -318,49 +264,38 @@ def gemm(M, N, K, a_kind, a, b_kind, b, c, ldc, *, batch=1, batch_inner=1, cs_ou
             cs = torch.empty(eff_c * M, dtype=torch.float32, device=c.device)      # (not the arena: a take may flush / move it under this GEMM)
             d.a_colsum = cs.data_ptr()
             d.flags |= GEMM_COLSUM_SLICES
-            rd_c = _lib.ReduceDesc(cs.data_ptr(), a_colsum.data_ptr(), None, eff_c, 1, M, M, 1.0, 1)
-            key = (c.device, _raw_stream())
-            busy = any(it[0].out == a_colsum.data_ptr() for it in _PENDING.get(key, ()))
-            if (d.flags & GEMM_DEFER_REDUCE) and not busy:
-                _PENDING.setdefault(key, []).append((rd_c, (a_colsum, cs)))
-            else:
-                # folded on its own right after this GEMM: the GEMM is not deferred, or a queued fold already adds into the same bias
-                # (two folds of one output must not share a launch); the other queued folds stay batched
-                colsum_now = (rd_c, cs)
-    if deferred is not None:
-        _PENDING.setdefault(deferred[0], []).append(deferred[1])
+            # folded on its own right after this GEMM when the GEMM is not deferred, or when a queued fold already adds into the same bias
+            # (two folds of one output must not share a launch); the other queued folds stay batched
+            folds.insert(0, dict(ws=cs.data_ptr(), out=a_colsum, splits=eff_c, M=1, N=M, ldc=M, keep=(cs,),
+                                 now=not d.flags & GEMM_DEFER_REDUCE, when_busy="now"))
     if DEBUG_WS is not None and split_k <= 1:
         d.workspace = _p(DEBUG_WS, torch.float32)
         d.flags |= 2048 | DEBUG_FLAGS
-    prof = PROFILE
-    if prof is None:
-        _lib.check(_lib.lib().toist_gemm_bf16(ctypes.byref(d), _stream()), "toist_gemm_bf16")
-        if colsum_now is not None:
-            _fold_now(colsum_now[0])
-        return
-    if not flops:
-        flops = 2 * M * N * K * max(batch, 1)
-    t = int(_lib.lib().toist_gemm_pick_tile(ctypes.byref(d)))
-    key = (t, a_kind, b_kind)
-    want = prof["key"]
-    if want is not None and not (want(key) if callable(want) else (key == want or (isinstance(want, (set, frozenset)) and key in want))):
-        _lib.check(_lib.lib().toist_gemm_bf16(ctypes.byref(d), _stream()), "toist_gemm_bf16")
-        if colsum_now is not None:
-            _fold_now(colsum_now[0])
-        prof["other"][key] = prof["other"].get(key, 0) + flops
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
+    prof, events = PROFILE, None
+    if prof is not None:
+        if not flops:
+            flops = 2 * M * N * K * max(batch, 1)
+        t = int(_lib.lib().toist_gemm_pick_tile(ctypes.byref(d)))
+        key = (t, a_kind, b_kind)
+        want = prof["key"]
+        if want is not None and not (want(key) if callable(want) else (key == want or (isinstance(want, (set, frozenset)) and key in want))):
+            prof["other"][key] = prof["other"].get(key, 0) + flops
+        else:
+            events = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            events[0].record()
     _lib.check(_lib.lib().toist_gemm_bf16(ctypes.byref(d), _stream()), "toist_gemm_bf16")
-    e1.record()
-    if colsum_now is not None:
-        _fold_now(colsum_now[0])
+    if events is not None:
+        events[1].record()
+    for f in folds:
+        FOLDS.queue(**f)
+    if events is None:
+        return
     ta = max(int(a.R) * int(a.S), 1) if a_kind in (A_CONV, A_CONVT) else 1
     tb = max(int(b.R) * int(b.S), 1) if b_kind == B_CONVX else 1
     nb = max(batch, 1)
     nbytes = 2 * M * K * nb // ta + 2 * N * K * nb // tb + (4 if c.dtype == torch.float32 else 2) * M * N * nb
     nbytes += 2 * M * N * nb * ((res is not None) + (aux is not None) + (pre_out is not None))
-    prof["records"].append((e0, e1, flops, key, (M, N, K, nb, split_k, ta * tb), nbytes))
+    prof["records"].append((*events, flops, key, (M, N, K, nb, split_k, ta * tb), nbytes))
 
 
 def matcher(logits, boxes, tgt_boxes, pos_map, tgt_off, match_off, max_T, w_class, w_bbox, w_giou, src_idx, tgt_idx,
@@ -385,20 +320,22 @@ def layernorm_fwd(x, gamma, beta, eps, y, mean=None, rstd=None, add=None, y2=Non
 LN_DEFER = knob("TOIST_LN_DEFER", True)
 
 
+def _queue_ln_param_grads(blocks, D, dgamma, dbeta):
+    """Arena space for two stacked [blocks, D] partial blocks, with their folds into dgamma and dbeta (f32 [D], accumulated) queued."""
+    partials = FOLDS.acquire(2 * blocks * D, dgamma.device, (dgamma, dbeta))
+    for i, out in enumerate((dgamma, dbeta)):
+        FOLDS.queue(partials.data_ptr() + 4 * i * blocks * D, out, blocks, 1, D, D)
+    return partials
+
+
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None, dx_drop=None, drop_p=0.0, seed=0, defer=False):
     """defer=True: dgamma / dbeta (f32, accumulated) are not updated by contended atomics inside the kernel -- every block writes its
     partial sums to the split-K arena and the fold is queued for flush_reductions() (engine.Tape.backward ends with it)."""
     rows, D = x.shape
     partials, blocks = None, 0
     if defer and LN_DEFER and dgamma is not None:
-        key = (x.device, _raw_stream())
-        if any(it[0].out in (dgamma.data_ptr(), dbeta.data_ptr()) for it in _PENDING.get(key, ())):
-            flush_reductions()          # two queued folds into one output would race
         blocks = int(_lib.lib().toist_layernorm_bwd_blocks(rows))
-        partials = _arena_take(2 * blocks * D, x.device)
-        for i, out in enumerate((dgamma, dbeta)):
-            rd = _lib.ReduceDesc(partials.data_ptr() + 4 * i * blocks * D, out.data_ptr(), None, blocks, 1, D, D, 1.0, 1)
-            _PENDING.setdefault(key, []).append((rd, (out, partials)))
+        partials = _queue_ln_param_grads(blocks, D, dgamma, dbeta)
     _lib.check(
         _lib.lib().toist_layernorm_bwd(_p(dy, torch.bfloat16), _p(x, torch.bfloat16), _p(mean, torch.float32),
                                        _p(rstd, torch.float32), _p(gamma, torch.float32), rows, D, _p(dx, torch.bfloat16),
@@ -694,14 +631,10 @@ def wgrad3x3_small(dy, x, out, defer=False, accumulate=True):
     n_img, H, W, C = x.shape
     Co = dy.shape[-1]
     blocks = int(_lib.lib().toist_wgrad3x3_small_blocks())
-    ws = _arena_take(blocks * Co * 9 * C, x.device)
+    ws = FOLDS.acquire(blocks * Co * 9 * C, x.device, (out,))
     _lib.check(_lib.lib().toist_wgrad3x3_small(_p(dy, torch.bfloat16), _p(x, torch.bfloat16), _p(ws, torch.float32), n_img, H, W, C, Co, _stream()),
                "toist_wgrad3x3_small")
-    key = (x.device, _raw_stream())
-    if any(it[0].out == out.data_ptr() for it in _PENDING.get(key, ())):
-        flush_reductions()
-    rd = _lib.ReduceDesc(ws.data_ptr(), out.data_ptr(), None, blocks, Co, 9 * C, 9 * C, 1.0, 1 if accumulate else 0)
-    _PENDING.setdefault(key, []).append((rd, (out,)))
+    FOLDS.queue(ws.data_ptr(), out, blocks, Co, 9 * C, 9 * C, accumulate=accumulate)
     if not defer:
         flush_reductions()
 
@@ -757,16 +690,8 @@ def rowgemm(a, w, out, *, b_kind, epi, K=None, bias=None, res=None, res2=None, d
     d.out, d.ldo = _p(out, torch.bfloat16), out.stride(0)
     keep = None
     if epi == _lib.ROW_LN_BWD and dgamma is not None:
-        key = (a.device, _raw_stream())
-        if any(it[0].out in (dgamma.data_ptr(), dbeta.data_ptr()) for it in _PENDING.get(key, ())):
-            flush_reductions()          # two queued folds into one output would race
-        blocks = int(_lib.lib().toist_rowgemm_blocks(M))
-        partials = _arena_take(2 * blocks * 256, a.device)
-        for i, o in enumerate((dgamma, dbeta)):
-            rd = _lib.ReduceDesc(partials.data_ptr() + 4 * i * blocks * 256, o.data_ptr(), None, blocks, 1, 256, 256, 1.0, 1)
-            _PENDING.setdefault(key, []).append((rd, (o, partials)))
-        d.partials = _p(partials, torch.float32)
-        keep = partials
+        keep = _queue_ln_param_grads(int(_lib.lib().toist_rowgemm_blocks(M)), 256, dgamma, dbeta)
+        d.partials = _p(keep, torch.float32)
     _lib.check(_lib.lib().toist_rowgemm(ctypes.byref(d), _stream()), "toist_rowgemm")
     return keep
 
@@ -903,11 +828,7 @@ def xdec_bwd(B, Q, S, kv, key_pad, drop_p, saved, g_out, outs, layers, scratch):
 def queue_fold(partials, out, splits, keep=()):
     """out[256] += sum over `splits` rows of partials [splits, 256] (f32), folded with the other deferred reductions of the current stream
     (flush_reductions): the LayerNorm parameter gradients of the XCD-resident backward."""
-    key = (out.device, _raw_stream())
-    if any(it[0].out == out.data_ptr() for it in _PENDING.get(key, ())):
-        flush_reductions()
-    rd = _lib.ReduceDesc(partials.data_ptr(), out.data_ptr(), None, splits, 1, 256, 256, 1.0, 1)
-    _PENDING.setdefault(key, []).append((rd, (out, partials) + tuple(keep)))
+    FOLDS.queue(partials.data_ptr(), out, splits, 1, 256, 256, keep=(partials,) + tuple(keep), when_busy="flush")
 
 
 def xdec_check(raise_on_failure=True):

@@ -511,6 +511,8 @@ typedef struct toist_xdec_desc {
     int32_t B, Q, S, L;
     const void* x0;            /* bf16 [B*Q, 256]: tgt entering layer 0 (zeros in the reference) */
     const void* qpos;          /* bf16 [B*Q, 256]: query_pos broadcast over the batch */
+    const void* xe0;           /* bf16 [B*Q, 256]: x0 + query_pos, the rows layer 0's q | k projections read (later layers keep y4 + query_pos themselves: y4e).
+                                * With x0 = 0 (the reference) pass qpos itself. */
     const void* kv;            /* bf16 [B*S, ldkv]: memory K (with pos) / V projections of layer l at columns l*512 / l*512 + 256 */
     int32_t ldkv;
     int32_t ff;                /* dim_feedforward of linear1 / linear2: the launch is compiled for 2048, anything else is refused (TOIST_EINVAL) */

@@ -8,23 +8,11 @@ import math
 import pytest
 import torch
 
+from oracle.xdec_ref import pair_hash
+
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
-
-
-def pair_hash(pair, seed):
-    """csrc/attn2.hip pair_hash in int64 arithmetic (values kept below 2^32)"""
-    M32 = 0xFFFFFFFF
-    s0 = seed & M32
-    s1 = ((seed >> 32) ^ ((seed & M32) * 0x9E3779B9)) & M32
-    a = (pair ^ s0) & M32
-    a = a ^ (a >> 12)
-    h = ((a & 0xFFFFFF) * 0x9E3779 + s1) & M32
-    h = h ^ (h >> 15)
-    h = ((h & 0xFFFFFF) * 0x85EBCB + (a >> 8)) & M32
-    h = h ^ (h >> 13)
-    return h
 
 
 def keep_mask(BH, Sq, Sk, p, seed):

@@ -38,16 +38,19 @@ GRAD_TENSORS = [
 ]
 
 
-def _report(key, val):
+def _report(key, val, name=None):
     try:
         os.makedirs("gpurun_out", exist_ok=True)
         path = "gpurun_out/b8_oracle_parity.json"
+        if name is not None:            # another test's measurements (tests/test_gpu_xdec_reference.py): its own file in the same directory
+            path = os.path.join(os.path.dirname(path), name)
         d = json.load(open(path)) if os.path.exists(path) else {}
         d[key] = val
         json.dump(d, open(path, "w"), indent=1, sort_keys=True)
     except OSError:
         pass
-    print(key, val)
+    if name is None:
+        print(key, val)
 
 
 def _elem(a, b):
@@ -85,14 +88,20 @@ def run(dev):
     stem_calls = []
     real_stem = k.stem_fwd
     k.stem_fwd = lambda *a, **kw: (stem_calls.append(1), real_stem(*a, **kw))[1]
+    xdec_bwd_calls = []
+    real_xdec_bwd = k.xdec_bwd
+    k.xdec_bwd = lambda *a, **kw: (xdec_bwd_calls.append(a[:3]), real_xdec_bwd(*a, **kw))[1]
+    res["xdec_supported"] = bool(k.xdec_supported(B, 100, 416, 6))
     try:
         # ---- HIP path: forward (tile tally), criterion, backward (tile tally) ----
         with torch.no_grad():
             res["feats"] = [f.permute(0, 3, 1, 2).float().cpu() for f in model.backbone[0].forward_native(samples.tensors.to(dev), (1, 2, 3, 4))]
         model.zero_grad(set_to_none=True)
         k.PROFILE = {"key": frozenset(), "records": [], "other": {}}
+        xdec_launches = k.XDEC_LAUNCHES
         mc = model(samples.to(dev), tok.to(dev), encode_and_save=True)
         out = model(samples.to(dev), tok.to(dev), encode_and_save=False, memory_cache=mc)
+        res["xdec_fwd_launches"] = k.XDEC_LAUNCHES - xdec_launches
         res["fwd_tiles"] = dict(k.PROFILE["other"])
         losses = criterion(mc, out, t_dev, pmap.to(dev), None)
         total = toist_amd.weighted_total(losses, weight_dict)
@@ -103,7 +112,9 @@ def run(dev):
     finally:
         k.PROFILE = None
         k.stem_fwd = real_stem
+        k.xdec_bwd = real_xdec_bwd
     res["stem_calls"] = len(stem_calls)
+    res["xdec_bwd_calls"], res["xdec_spin_expired"] = xdec_bwd_calls, k.xdec_check(raise_on_failure=False)
     res["mc"], res["out"], res["losses"], res["total"] = mc, out, {k_: float(v) for k_, v in losses.items()}, float(total)
     L = out["_stacked"]["pred_logits"].shape[0]
     match = criterion.last_match
@@ -141,6 +152,16 @@ def test_benchmarked_kernels_were_dispatched(run):
     assert 136 in fwd and 135 in fwd, sorted(fwd)
     assert {136, 137, 138} <= bwd, sorted(bwd)
     assert run["stem_calls"] >= 2          # forward_native + the model's own forward
+
+
+def test_xcd_resident_decoder_was_dispatched(run):
+    """the decoder of the compared passes ran as the two XCD-resident launches (csrc/xdec.hip), not on the per-op launches xdec_supported() falls back to:
+    one forward launch for the six layers, one backward launch, no expired spin"""
+    if not run["xdec_supported"]:
+        pytest.skip("kernels.xdec_supported(8, 100, 416, 6) is False on this device (no 8 XCDs x 32 CUs, or the launches are switched off)")
+    assert run["xdec_fwd_launches"] == 1, run["xdec_fwd_launches"]
+    assert run["xdec_bwd_calls"] == [(8, 100, 416)], run["xdec_bwd_calls"]
+    assert run["xdec_spin_expired"] is False
 
 
 def test_forward_values_at_batch8(run):

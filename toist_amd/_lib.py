@@ -72,7 +72,7 @@ class XdecLayer(Structure):
 
 class Xdec(Structure):
     """toist_xdec_desc (include/toist_hip.h): the XCD-resident decoder stack of csrc/xdec.hip"""
-    _fields_ = [("B", c_int32), ("Q", c_int32), ("S", c_int32), ("L", c_int32), ("x0", c_void_p), ("qpos", c_void_p), ("kv", c_void_p), ("ldkv", c_int32),
+    _fields_ = [("B", c_int32), ("Q", c_int32), ("S", c_int32), ("L", c_int32), ("x0", c_void_p), ("qpos", c_void_p), ("xe0", c_void_p), ("kv", c_void_p), ("ldkv", c_int32),
                 ("ff", c_int32), ("test_absent", c_int32), ("reserved", c_int32), ("key_pad", c_void_p), ("drop_p", c_float), ("eps", c_float), ("seed_dev", c_void_p)] + \
                [(n, c_void_p) for n in ("qkv", "ctx_s", "lse_s", "z1", "y1", "y1e", "mean1", "rstd1", "qc", "ctx_c", "lse_c", "z3", "y3", "mean3", "rstd3", "h", "z4", "y4",
                                         "y4e", "mean4", "rstd4", "part", "ctl", "prof")] + \

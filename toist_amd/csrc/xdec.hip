@@ -485,7 +485,7 @@ __global__ __launch_bounds__(XNT) void xdec_fwd_kernel(const toist_xdec_desc p) 
             const toist_xdec_layer& ly = p.layer[layer];
             const size_t lrow = (size_t)layer * M + row0;        // row offset of (layer, image) in the stacked outputs
             const bf16_t* const x_img = layer == 0 ? reinterpret_cast<const bf16_t*>(p.x0) + row0 * XD : reinterpret_cast<const bf16_t*>(p.y4) + (lrow - M) * XD;
-            const bf16_t* const xe_img = layer == 0 ? reinterpret_cast<const bf16_t*>(p.qpos) + row0 * XD : reinterpret_cast<const bf16_t*>(p.y4e) + (lrow - M) * XD;
+            const bf16_t* const xe_img = layer == 0 ? reinterpret_cast<const bf16_t*>(p.xe0) + row0 * XD : reinterpret_cast<const bf16_t*>(p.y4e) + (lrow - M) * XD;
             bf16_t* const qkv_img = reinterpret_cast<bf16_t*>(p.qkv) + lrow * (3 * XD);
             const bf16_t* const qpos_img = reinterpret_cast<const bf16_t*>(p.qpos) + row0 * XD;
             const bool last = layer + 1 == p.L;
@@ -1257,7 +1257,7 @@ extern "C" int toist_xdec_fwd(const toist_xdec_desc* d, void* stream) {
                   d->S, d->L);
     TOIST_REQUIRE(d->ff == XFF, "toist_xdec_fwd: dim_feedforward %d: the launch is compiled for linear1 [%d, 256] / linear2 [256, %d] (use the per-op path)", d->ff, XFF, XFF);
     TOIST_REQUIRE(d->test_absent >= 0 && d->test_absent <= XWG, "toist_xdec_fwd: bad test_absent");
-    TOIST_REQUIRE(d->x0 && d->qpos && d->kv && d->qkv && d->ctx_s && d->lse_s && d->z1 && d->y1 && d->y1e && d->mean1 && d->rstd1 && d->qc && d->ctx_c && d->lse_c &&
+    TOIST_REQUIRE(d->x0 && d->qpos && d->xe0 && d->kv && d->qkv && d->ctx_s && d->lse_s && d->z1 && d->y1 && d->y1e && d->mean1 && d->rstd1 && d->qc && d->ctx_c && d->lse_c &&
                       d->z3 && d->y3 && d->mean3 && d->rstd3 && d->h && d->z4 && d->y4 && d->y4e && d->mean4 && d->rstd4 && d->part && d->ctl,
                   "toist_xdec_fwd: every buffer of the descriptor is required");
     TOIST_REQUIRE((d->ldkv % 8) == 0 && d->ldkv >= d->L * 2 * XD, "toist_xdec_fwd: ldkv %d must be a multiple of 8 and cover L * 512 columns", d->ldkv);

@@ -743,14 +743,17 @@ def xdec_supported(B, Q, S, L, ff=2048):
     return _xdec_ctl(torch.device("cuda", torch.cuda.current_device())) is not None
 
 
-def xdec_fwd(B, Q, S, x0, qpos, kv, key_pad, drop_p, eps, out, layers, part):
+def xdec_fwd(B, Q, S, x0, qpos, kv, key_pad, drop_p, eps, out, layers, part, *, xe0):
     """All decoder layers in one launch (include/toist_hip.h: toist_xdec_fwd).  `out` = dict of the stacked per-layer tensors named as the
-    descriptor's fields; `layers` = one dict per layer with the 18 parameter tensors + "seed" (6 ints)."""
+    descriptor's fields; `layers` = one dict per layer with the 18 parameter tensors + "seed" (6 ints).  xe0 = bf16(x0 + qpos), the rows layer 0's
+    q | k projections read (required: a caller whose x0 is all zeros, the model's decoder, passes qpos itself)."""
     d = _lib.Xdec()
     d.B, d.Q, d.S, d.L = B, Q, S, len(layers)
     d.ff, d.test_absent = int(layers[0]["w1"].shape[0]), XDEC_TEST_ABSENT
     assert all(tuple(ly["w1"].shape) == (d.ff, 256) and tuple(ly["w2"].shape) == (256, d.ff) for ly in layers)
     d.x0, d.qpos, d.kv, d.ldkv = _p(x0, torch.bfloat16), _p(qpos, torch.bfloat16), _p(kv, torch.bfloat16), kv.stride(0)
+    assert xe0.is_contiguous() and xe0.shape == qpos.shape
+    d.xe0 = _p(xe0, torch.bfloat16)
     d.key_pad = _p(key_pad, torch.uint8) if key_pad is not None else None
     d.drop_p, d.eps = drop_p, eps
     d.seed_dev = _p(SEED_DEV) if drop_p > 0 else None

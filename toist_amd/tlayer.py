@@ -202,18 +202,37 @@ def encoder_program(tape, ps, x, pos, key_pad, B, S, H, n_layers):
 
 
 # ------------------------------------------------------------------------------------------------------------------ decoder
-def _decoder_layers_xcd(tape, ps, Wself, Wcross, x0, qpos, kv, key_pad, tgt_stack, B, S, Q, H, L_):
-    """Forward of all decoder layers as ONE launch (csrc/xdec.hip: one image per XCD, XCD-local barriers); returns the per-layer records the
-    backward steps of decoder_program read -- every saved tensor has the layout / statistics / dropout hash of the per-op launches, so the
-    backward pass is the same code.  Seeds are drawn in the order of the per-op path (tests compare the two paths WITH dropout)."""
-    d, M, p = 256, B * Q, tape.drop_p
-    dev = x0.device
+def xdec_fwd_buffers(B, Q, L_, dev, tgt_stack, H=8):
+    """The stacked per-layer tensors toist_xdec_fwd saves (`out`, named as the descriptor's fields; y4 = tgt_stack [L, B*Q, 256]) and the scratch of
+    its linear2 partial sums (`part`): one allocation routine for the product and for the tests that call the launch directly."""
+    d, M = 256, B * Q
     bf = lambda *shape: torch.empty(*shape, dtype=BF16, device=dev)
     f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
     out = dict(qkv=bf(L_, M, 3 * d), ctx_s=bf(L_, M, d), lse_s=f32(L_, B * H, Q, 2), z1=bf(L_, M, d), y1=bf(L_, M, d), y1e=bf(L_, M, d), mean1=f32(L_, M), rstd1=f32(L_, M),
                qc=bf(L_, M, d), ctx_c=bf(L_, M, d), lse_c=f32(L_, B * H, Q, 2), z3=bf(L_, M, d), y3=bf(L_, M, d), mean3=f32(L_, M), rstd3=f32(L_, M),
                h=bf(L_, M, 2048), z4=bf(L_, M, d), y4=tgt_stack, y4e=bf(L_, M, d), mean4=f32(L_, M), rstd4=f32(L_, M))
     part = bf(B * 32 * 128 * 256)
+    return out, part
+
+
+def xdec_bwd_buffers(B, Q, L_, dev, sink, dkv, part):
+    """Outputs (`outs`) and scratch of toist_xdec_bwd: sink [B*Q, >= L*1024] and dkv [B*S, >= L*512] are the caller's (column slices of wider tensors are
+    fine), part = the forward launch's scratch."""
+    d, M = 256, B * Q
+    bf = lambda *shape: torch.empty(*shape, dtype=BF16, device=dev)
+    nblk = B * ((Q + 3) // 4)
+    outs = dict(gb4=bf(L_, M, d), dh=bf(L_, M, 2048), go3=bf(L_, M, d), go1=bf(L_, M, d), sink=sink, dkv=dkv,
+                ln_part=torch.empty(L_, 3, 2, nblk, d, dtype=torch.float32, device=dev))
+    scratch = dict(dctx=bf(2, M, d), part=part, dq_part=bf(4, M, d))
+    return outs, scratch
+
+
+def _decoder_layers_xcd(tape, ps, Wself, Wcross, x0, qpos, kv, key_pad, tgt_stack, B, S, Q, H, L_):
+    """Forward of all decoder layers as ONE launch (csrc/xdec.hip: one image per XCD, XCD-local barriers); returns the per-layer records the
+    backward steps of decoder_program read -- every saved tensor has the layout / statistics / dropout hash of the per-op launches, so the
+    backward pass is the same code.  Seeds are drawn in the order of the per-op path (tests compare the two paths WITH dropout)."""
+    d, M, p = 256, B * Q, tape.drop_p
+    out, part = xdec_fwd_buffers(B, Q, L_, x0.device, tgt_stack, H)
     recs, table = [], []
     for i in range(L_):
         lp = f"layers.{i}."
@@ -242,7 +261,7 @@ def _decoder_layers_xcd(tape, ps, Wself, Wcross, x0, qpos, kv, key_pad, tgt_stac
                           b_oc=L.boc.f32, g3=norms[1][0].f32, be3=norms[1][1].f32, w1=L.W1.w, b1=L.b1.f32, w2=L.W2.w, b2=L.b2.f32, g4=norms[2][0].f32,
                           be4=norms[2][1].f32, seed=seeds))
         recs.append(L)
-    k.xdec_fwd(B, Q, S, x0, qpos, kv, key_pad, p, 1e-5, out, table, part)
+    k.xdec_fwd(B, Q, S, x0, qpos, kv, key_pad, p, 1e-5, out, table, part, xe0=qpos)       # x0 = 0 (decoder_program): x0 + qpos is qpos
     tape.keep.append((out, part))
     return recs, SimpleNamespace(out=out, part=part, table=table)
 
@@ -251,13 +270,9 @@ def _decoder_backward_xcd(tape, layers, fw, g_out, kv, dkv, sink, key_pad, B, S,
     """Backward of all decoder layers: ONE launch for the data-gradient chain (csrc/xdec.hip xdec_bwd_kernel), then the weight gradients exactly as
     the per-op steps queue them (grouped launches at the program's end) and the LayerNorm parameter gradients as deferred folds of the
     launch's per-row-block partial sums."""
-    d, M, L_ = 256, B * Q, len(layers)
-    dev = kv.device
-    bf = lambda *shape: torch.empty(*shape, dtype=BF16, device=dev)
+    d, L_ = 256, len(layers)
     nblk = B * ((Q + 3) // 4)
-    outs = dict(gb4=bf(L_, M, d), dh=bf(L_, M, 2048), go3=bf(L_, M, d), go1=bf(L_, M, d), sink=sink, dkv=dkv,
-                ln_part=torch.empty(L_, 3, 2, nblk, d, dtype=torch.float32, device=dev))
-    scratch = dict(dctx=bf(2, M, d), part=fw.part, dq_part=bf(4, M, d))
+    outs, scratch = xdec_bwd_buffers(B, Q, L_, kv.device, sink, dkv, fw.part)
     table = [dict(w_in=L.Ws.w, w_os=L.Wos.w, w_q=L.Wq.w, w_oc=L.Woc.w, w1=L.W1.w, w2=L.W2.w, g1=L.ln1.gamma.f32, g3=L.ln3.gamma.f32, g4=L.ln4.gamma.f32,
                   seed=t["seed"]) for L, t in zip(layers, fw.table)]
     k.xdec_bwd(B, Q, S, kv, key_pad, p, fw.out, g_out, outs, table, scratch)

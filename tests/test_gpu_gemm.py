@@ -395,7 +395,8 @@ def test_grouped_conv_wgrad_matches_separate_launches(dev, R, stride, min_tiles)
 @pytest.mark.parametrize("B,H,S,dh", [(8, 12, 16, 64), (3, 4, 11, 32), (2, 2, 40, 64), (1, 3, 64, 16)])
 def test_small_attention_against_autograd(dev, B, H, S, dh):
     """csrc/attn_small.hip (whole-head attention of the text encoder: S <= 64, head dim <= 64) forward and backward against fp32
-    autograd, with key padding and the three projection biases added on load; dropout off (the mask is a hash, covered by the model tests)."""
+    autograd, with key padding and the three projection biases added on load; dropout off here -- the mask, forward and backward, is held against the host
+    hash on the same shapes by tests/test_gpu_dropout_parity.py test_small_attention_dropout_against_autograd."""
     from toist_amd import kernels as k
     g = torch.Generator().manual_seed(S * dh)
     d = H * dh

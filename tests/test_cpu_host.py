@@ -5,7 +5,6 @@ import ctypes
 import json
 import os
 import re
-import subprocess
 
 import pytest
 import torch
@@ -13,43 +12,133 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _header():
+    with open(os.path.join(ROOT, "include", "toist_hip.h")) as f:
+        return f.read()
+
+
 def test_library_exports_every_declared_symbol():
+    """The names come from a regex of this test's own, not from the binding's parser: a prototype the parser skipped would be missing
+    from exported_symbols() and show here."""
     from toist_amd import _lib
-    header = open(os.path.join(ROOT, "include", "toist_hip.h")).read()
+    header = _header()
     declared = set(re.findall(r"\b(toist_[a-z0-9_]+)\s*\(", header))
     assert declared, "no declarations parsed"
     handle = _lib.lib()
     missing = [n for n in sorted(declared) if not hasattr(handle, n)]
     assert not missing, f"symbols declared in toist_hip.h but not exported: {missing}"
     assert set(_lib.exported_symbols()) == declared, (sorted(set(_lib.exported_symbols()) ^ declared))
+    assert set(_lib.parse_signatures(header, _lib._BYREF)) == declared and len(_lib.SIGNATURES) == len(declared)
+    for name, argtypes in _lib.SIGNATURES.items():
+        fn = getattr(handle, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is ctypes.c_int, name
     assert handle.toist_version() == 1
 
 
+# C name of every ctypes.Structure class of toist_amd/_lib.py: a new descriptor class goes here
+C_STRUCTS = {"toist_operand": "Operand", "toist_epilogue": "Epilogue", "toist_gemm": "Gemm", "toist_reduce_desc": "ReduceDesc",
+             "toist_rowgemm_desc": "RowGemm", "toist_xdec_layer": "XdecLayer", "toist_xdec_desc": "Xdec",
+             "toist_xdec_bwd_layer": "XdecBwdLayer", "toist_xdec_bwd_desc": "XdecBwd"}
+
+
 def test_struct_layouts_match_header(tmp_path):
+    """One generated C program: sizeof of every struct the Python side builds, offsetof and sizeof of every field BY NAME, and every
+    integer constant the binding parsed out of the header, each compared with what ctypes / numpy / the parser hold."""
+    from abi_probe import c_values
+    from toist_amd import _lib, optim
+    classes = {n for n, v in vars(_lib).items() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    assert classes == set(C_STRUCTS.values()), "every Structure class of _lib.py is probed"
+    layouts = {}                                                    # C struct name -> (sizeof, [(field, offset, size)])
+    for c_name, py_name in C_STRUCTS.items():
+        cls = getattr(_lib, py_name)
+        layouts[c_name] = (ctypes.sizeof(cls), [(f[0], getattr(cls, f[0]).offset, getattr(cls, f[0]).size) for f in cls._fields_])
+    # the optimizer tail's device tables and state word are numpy records (toist_amd/optim.py)
+    for c_name, dt in (("toist_opt_tensor", optim._TENSOR_DT), ("toist_opt_group", optim._GROUP_DT), ("toist_opt_state", optim._STATE_DT)):
+        layouts[c_name] = (dt.itemsize, [(n, dt.fields[n][1], dt.fields[n][0].itemsize) for n in dt.names])
+    want = {}
+    for c_name, (size, fields) in layouts.items():
+        want[f"sizeof({c_name})"] = size
+        for name, offset, fsize in fields:
+            want[f"offsetof({c_name}, {name})"] = offset
+            want[f"sizeof((({c_name}*)0)->{name})"] = fsize
+    assert _lib.CONSTANTS and all(re.fullmatch(r"TOIST_\w+", n) for n in _lib.CONSTANTS)
+    want.update(_lib.CONSTANTS)                                     # the parser against the real preprocessor
+    # the grouped-launch table rows are six int64 per problem (toist_amd/kernels.py: group_table), not a class: pinned below
+    pins = ["sizeof(toist_group)", "offsetof(toist_group, c_off)", "offsetof(toist_group, colsum_off)"]
+    exprs = list(want) + pins
+    got = dict(zip(exprs, c_values(tmp_path, exprs)))
+    wrong = {e: {"C": got[e], "python": v} for e, v in want.items() if got[e] != v}
+    assert not wrong, wrong
+    assert [got[e] for e in pins] == [48, 16, 32]
+    assert got["sizeof(toist_opt_tensor)"] == 64 and got["sizeof(toist_opt_state)"] == 32 and got["offsetof(toist_opt_state, step)"] == 16
+    assert got["offsetof(toist_gemm, epi)"] == _lib.Gemm.epi.offset and got["offsetof(toist_gemm, a_colsum)"] == _lib.Gemm.a_colsum.offset
+    assert got["offsetof(toist_gemm, group)"] == _lib.Gemm.group.offset
+    assert got["offsetof(toist_opt_tensor, numel)"] == optim._TENSOR_DT.fields["numel"][1]
+    assert got["offsetof(toist_opt_tensor, group)"] == optim._TENSOR_DT.fields["group"][1]
+
+
+SYNTHETIC_HEADER = """
+/* TOIST_API int toist_commented_out(double x); */
+// TOIST_API int toist_commented_out_too(unsigned k);
+#define TOIST_API __attribute__((visibility("default")))
+#define TOIST_SEVEN 7
+#define TOIST_MINUS (-2)   /* in parentheses */
+#define TOIST_NOT_A_NUMBER seven
+enum { TOIST_E0 = 0, TOIST_E5 = 5 };
+TOIST_API int toist_none(void);
+TOIST_API int toist_every(int a, int32_t b, int64_t c, long long d, uint64_t e, float f, size_t g,
+                          char* buf, const float* x, /* tables are cast by the caller */ const int32_t* const* table,
+                          const toist_gemm* desc, toist_group* rows,
+                          void* stream);
+"""
+
+
+def test_parser_binds_every_accepted_type():
+    from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_longlong, c_size_t, c_uint64, c_void_p
     from toist_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include "toist_hip.h"\n#include <stdio.h>\nint main(void){printf("%zu %zu %zu %zu %zu\\n", sizeof(toist_operand), '
-                   'sizeof(toist_epilogue), sizeof(toist_gemm), offsetof(toist_gemm, epi), offsetof(toist_gemm, a_colsum));return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == [ctypes.sizeof(_lib.Operand), ctypes.sizeof(_lib.Epilogue), ctypes.sizeof(_lib.Gemm), _lib.Gemm.epi.offset,
-                   _lib.Gemm.a_colsum.offset]
-    # the optimizer-tail table rows (built with numpy in toist_amd/optim.py) and the split-K reduction descriptor
-    src.write_text('#include "toist_hip.h"\n#include <stdio.h>\nint main(void){printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(toist_opt_tensor), '
-                   'offsetof(toist_opt_tensor, numel), offsetof(toist_opt_tensor, group), sizeof(toist_opt_state), offsetof(toist_opt_state, step), '
-                   'sizeof(toist_reduce_desc));return 0;}\n')
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    from toist_amd import optim
-    dt = optim._TENSOR_DT
-    assert got == [dt.itemsize, dt.fields["numel"][1], dt.fields["group"][1], 32, 16, ctypes.sizeof(_lib.ReduceDesc)]
-    # the grouped-launch table rows (six int64 per problem, toist_amd/kernels.py: group_table) and the descriptor's group pointer
-    src.write_text('#include "toist_hip.h"\n#include <stdio.h>\nint main(void){printf("%zu %zu %zu %zu\\n", sizeof(toist_group), '
-                   'offsetof(toist_group, c_off), offsetof(toist_group, colsum_off), offsetof(toist_gemm, group));return 0;}\n')
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == [48, 16, 32, _lib.Gemm.group.offset]
+    sigs = _lib.parse_signatures(SYNTHETIC_HEADER, _lib._BYREF)
+    assert sigs == {"toist_none": [],
+                    "toist_every": [c_int32, c_int32, c_int64, c_longlong, c_uint64, c_float, c_size_t, c_char_p, c_void_p, c_void_p,
+                                    POINTER(_lib.Gemm), c_void_p, c_void_p]}
+    assert _lib.parse_constants(SYNTHETIC_HEADER) == {"TOIST_SEVEN": 7, "TOIST_MINUS": -2, "TOIST_E0": 0, "TOIST_E5": 5}
+
+
+@pytest.mark.parametrize("param", ["unsigned k", "double x", "toist_gemm d", "float*", "int"])
+def test_parser_refuses_what_it_does_not_know(param):
+    from toist_amd import _lib
+    with pytest.raises(ValueError) as e:
+        _lib.parse_signatures(f"TOIST_API int toist_ok(int n);\nTOIST_API int toist_odd(const void* x,\n    {param}, void* stream);\n", _lib._BYREF)
+    assert "toist_odd" in str(e.value) and param in str(e.value)
+    for text in ("TOIST_API float toist_odd(int n);", "TOIST_API int toist_odd(int n)\nTOIST_API int toist_next(void);", "TOIST_API int toist_odd(int (*f)(int));"):
+        with pytest.raises(ValueError, match="toist_odd"):
+            _lib.parse_signatures(text, {})
+    with pytest.raises(ValueError, match="TOIST_BARE"):
+        _lib.parse_constants("enum { TOIST_BARE, TOIST_NEXT = 1 };")
+
+
+def test_signatures_of_the_irregular_entry_points():
+    """Hand-written expectations on the real header, by ctypes kind and size (whether c_int64 and c_longlong are one class or two depends on the
+    platform), plus the pointee class of the typed descriptor pointers."""
+    from toist_amd import _lib
+
+    def kinds(argtypes):
+        return [("P", t._type_) if issubclass(t, ctypes._Pointer) else (t._type_, ctypes.sizeof(t)) for t in argtypes]
+
+    void_p, i32, i64, ll = ("P", 8), ("i", 4), (ctypes.c_int64._type_, 8), (ctypes.c_longlong._type_, 8)
+    sig = _lib.SIGNATURES
+    assert kinds(sig["toist_last_error"]) == [("z", 8), (ctypes.c_size_t._type_, 8)] and sig["toist_last_error"][0] is ctypes.c_char_p
+    assert kinds(sig["toist_gemm_bf16"]) == [("P", _lib.Gemm), void_p]
+    assert kinds(sig["toist_rowgemm"]) == [("P", _lib.RowGemm), void_p] and kinds(sig["toist_xdec_fwd"]) == [("P", _lib.Xdec), void_p]
+    assert kinds(sig["toist_xdec_bwd"]) == [("P", _lib.XdecBwd), void_p] and kinds(sig["toist_gemm_pick_tile"]) == [("P", _lib.Gemm)]
+    assert kinds(sig["toist_image_prep"]) == [void_p, ll, void_p, void_p, ll, void_p, i32, i32, i32, void_p, void_p, void_p, ll, void_p]
+    assert kinds(sig["toist_splitk_reduce_batch"]) == [void_p, i32, void_p]
+    assert kinds(sig["toist_group_fill"]) == [void_p, i32, void_p, void_p]
+    assert kinds(sig["toist_add_bf16"]) == [void_p, void_p, i64, i64, void_p, void_p]
+    assert sig["toist_version"] == [] and sig["toist_wgrad3x3_small_blocks"] == []
+    # every launch ends with the stream, a pointer
+    last = dict(re.findall(r"\b(toist_\w+)\s*\([^()]*?(\w+)\s*\)\s*;", re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)))
+    with_stream = [n for n, p in last.items() if p == "stream"]
+    assert len(with_stream) > 70 and all(sig[n][-1] is ctypes.c_void_p for n in with_stream)
 
 
 def test_bad_arguments_return_error_codes_without_a_gpu():

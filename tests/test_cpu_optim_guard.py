@@ -1,10 +1,6 @@
 """CPU-side checks of the optimizer tail's non-finite guard (toist_opt_finish_norm_guarded): the entry point is exported, refuses bad veto tables
 with an error code before anything is launched, and the three words it writes sit where toist_amd.optim.device_state() reads them."""
 import ctypes
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_the_guarded_finish_norm():
@@ -32,13 +28,9 @@ def test_bad_veto_tables_return_error_codes_without_a_gpu():
 
 
 def test_guard_words_sit_behind_the_step_count(tmp_path):
-    src = tmp_path / "st.c"
-    src.write_text('#include "toist_hip.h"\n#include <stdio.h>\nint main(void){printf("%zu %zu %zu %zu %zu %d\\n", sizeof(toist_opt_state), '
-                   'offsetof(toist_opt_state, step), offsetof(toist_opt_state, skipped), offsetof(toist_opt_state, skipped_total), '
-                   'offsetof(toist_opt_state, veto_mask), TOIST_OPT_MAX_VETO);return 0;}\n')
-    exe = tmp_path / "st"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    from abi_probe import c_values
+    got = c_values(tmp_path, ["sizeof(toist_opt_state)", "offsetof(toist_opt_state, step)", "offsetof(toist_opt_state, skipped)",
+                              "offsetof(toist_opt_state, skipped_total)", "offsetof(toist_opt_state, veto_mask)", "TOIST_OPT_MAX_VETO"])
     assert got == [32, 16, 20, 24, 28, 8]
     from toist_amd.optim import FusedClipAdamWEMA
     assert FusedClipAdamWEMA.MAX_VETO == 8

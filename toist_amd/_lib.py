@@ -1,21 +1,102 @@
-"""ctypes binding of libtoist_hip.so (include/toist_hip.h).
+"""ctypes binding of libtoist_hip.so, derived from include/toist_hip.h.
 
 The product path has exactly one backend: the hand-written HIP library.  If it is missing or fails
 to load, importing a kernel raises -- there is no CPU or eager-PyTorch fallback.
+
+The header is the only place a signature or a constant is written.  At import this module parses it once
+(`parse_signatures`, `parse_constants`: pure functions of the header text) and sets `argtypes` / `restype` of
+every `TOIST_API` prototype from what it finds; a parameter it cannot classify raises, it never guesses.  A new
+entry point needs its prototype in the header and its launcher in kernels.py, nothing here.  A new descriptor
+struct also needs a `Structure` class below (the field names are the launchers' vocabulary; they are not derived)
+and its C name in the layout probe's map (tests/test_cpu_host.py: C_STRUCTS), which holds every field of every
+class against the C compiler; if the launcher passes it with `byref`, its name goes into `_BYREF` as well.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+import re
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_longlong, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TOIST_HIP_LIB: another build of the same library (kernel experiments: A/B two builds inside one GPU session)
 LIB_PATH = os.environ.get("TOIST_HIP_LIB") or os.path.join(_HERE, "libtoist_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toist_hip.h")
 
-TOIST_OK = 0
-# operand kinds / activations (mirrors include/toist_hip.h)
-A_ROWK, A_KROW, A_CONV, A_CONVT = 0, 1, 2, 3
-B_ROWK, B_KROW, B_CONVX = 0, 1, 2
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_SIGMOID, ACT_MASK_POS, ACT_GELU_BWD, ACT_SIGMOID_BWD = range(7)
+_SCALARS = {"int": c_int32, "int32_t": c_int32, "int64_t": c_int64, "long long": c_longlong, "uint64_t": c_uint64,
+            "float": c_float, "size_t": c_size_t}
+_INT = r"\(?\s*(-?(?:0[xX][0-9a-fA-F]+|\d+))\s*\)?"
+
+
+def _strip_comments(text):
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def parse_constants(text):
+    """{name: value} of every `#define TOIST_NAME <integer or (integer)>` and every `TOIST_NAME = <integer>` of an enum body."""
+    text = _strip_comments(text)
+    out = {name: int(value, 0) for name, value in re.findall(rf"^[ \t]*#[ \t]*define[ \t]+(TOIST_\w+)[ \t]+{_INT}[ \t]*$", text, flags=re.M)}
+    for body in re.findall(r"\benum\s*\w*\s*\{([^}]*)\}", text):
+        for entry in filter(None, (e.strip() for e in body.split(","))):
+            m = re.fullmatch(rf"(TOIST_\w+)\s*=\s*{_INT}", entry)
+            if m is None:
+                raise ValueError(f"toist_hip.h: enum entry {entry!r} is not `TOIST_NAME = <integer>`")
+            out[m.group(1)] = int(m.group(2), 0)
+    return out
+
+
+def parse_signatures(text, byref):
+    """{function: [argtypes]} of every `TOIST_API int toist_name(<params>);` prototype, in the header's order.  A pointer parameter is
+    c_char_p (`char*`), POINTER(cls) for the descriptors of `byref` ({C struct name: Structure class}, see _BYREF) and c_void_p
+    otherwise (device tables and arrays: the caller casts); a value parameter is one of _SCALARS.  Anything else raises ValueError
+    naming the function and the parameter."""
+    text = re.sub(r"^[ \t]*#[^\n]*$", "", _strip_comments(text), flags=re.M)         # TOIST_API's own #define lines
+    out = {}
+    for chunk in re.split(r"\bTOIST_API\b", text)[1:]:
+        m = re.match(r"\s+([\w\s*]+?)\s*\b(toist_\w+)\s*\(([^()]*)\)\s*;", chunk)
+        if m is None:
+            raise ValueError(f"toist_hip.h: TOIST_API is not followed by a prototype: {' '.join(chunk.split())[:80]!r}")
+        ret, name, params = m.group(1), m.group(2), [" ".join(p.split()) for p in m.group(3).split(",")]
+        if ret != "int" or name in out:
+            raise ValueError(f"toist_hip.h: {name}: " + ("declared twice" if ret == "int" else f"returns {ret!r}, every entry point returns int"))
+        out[name] = [] if params == ["void"] else [_argtype(name, p, byref) for p in params]
+    return out
+
+
+def _argtype(fn, param, byref):
+    *kind, name = [w for w in param.replace("*", " * ").split() if w != "const"] or [""]            # <type> <name>
+    stars = kind.count("*")
+    base = " ".join(kind[:len(kind) - stars])                                                         # the stars follow the pointee
+    if name.isidentifier() and base and "*" not in base:
+        if stars == 0 and base in _SCALARS:
+            return _SCALARS[base]
+        if stars == 1:
+            return c_char_p if base == "char" else POINTER(byref[base]) if base in byref else c_void_p
+        if stars > 1:
+            return c_void_p                                                                           # a table of pointers
+    raise ValueError(f"toist_hip.h: {fn}: cannot bind parameter {param!r}")
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        _HEADER = _f.read()
+except OSError as e:
+    raise RuntimeError(f"{HEADER_PATH} is missing: toist_amd binds libtoist_hip.so from the header it was built against") from e
+CONSTANTS = parse_constants(_HEADER)
+
+
+def _consts(names):
+    return [CONSTANTS["TOIST_" + n] for n in names.split()]
+
+
+TOIST_OK = CONSTANTS["TOIST_OK"]
+# operand kinds / activations
+A_ROWK, A_KROW, A_CONV, A_CONVT = _consts("A_ROWK A_KROW A_CONV A_CONVT")
+B_ROWK, B_KROW, B_CONVX = _consts("B_ROWK B_KROW B_CONVX")
+ACT_NONE, ACT_RELU, ACT_GELU, ACT_SIGMOID, ACT_MASK_POS, ACT_GELU_BWD, ACT_SIGMOID_BWD = _consts(
+    "ACT_NONE ACT_RELU ACT_GELU ACT_SIGMOID ACT_MASK_POS ACT_GELU_BWD ACT_SIGMOID_BWD")
+ROW_PLAIN, ROW_LN_FWD, ROW_LN_BWD = _consts("ROW_PLAIN ROW_LN_FWD ROW_LN_BWD")
+XDEC_MAX_LAYERS, XDEC_CTL_WORDS = _consts("XDEC_MAX_LAYERS XDEC_CTL_WORDS")
+PREP_DESC_WORDS = CONSTANTS["TOIST_PREP_DESC_WORDS"]        # int32 words of one image's row in toist_image_prep's descriptor table
+TMASK_DESC_WORDS = CONSTANTS["TOIST_TMASK_DESC_WORDS"]      # int32 words of one slot's row in toist_target_masks' descriptor table
 
 
 class Operand(Structure):
@@ -45,9 +126,6 @@ class Gemm(Structure):
     ]
 
 
-ROW_PLAIN, ROW_LN_FWD, ROW_LN_BWD = 0, 1, 2
-
-
 class RowGemm(Structure):
     """toist_rowgemm_desc (include/toist_hip.h): row-complete sub-layer launch of csrc/tlayer.hip"""
     _fields_ = [
@@ -57,11 +135,6 @@ class RowGemm(Structure):
         ("drop_seed_dev", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("z", c_void_p), ("mean", c_void_p), ("rstd", c_void_p),
         ("out", c_void_p), ("ldo", c_int32), ("reserved", c_int32), ("add", c_void_p), ("out2", c_void_p), ("partials", c_void_p),
     ]
-
-
-XDEC_MAX_LAYERS, XDEC_CTL_WORDS = 8, 1024
-PREP_DESC_WORDS = 20          # TOIST_PREP_DESC_WORDS: int32 words of one image's row in toist_image_prep's descriptor table
-TMASK_DESC_WORDS = 8          # TOIST_TMASK_DESC_WORDS: int32 words of one slot's row in toist_target_masks' descriptor table
 
 
 class XdecLayer(Structure):
@@ -98,105 +171,16 @@ class ReduceDesc(Structure):
                 ("ldc", c_int32), ("alpha", c_float), ("accumulate", c_int32)]
 
 
-_SIGNATURES = {
-    "toist_version": ([], ctypes.c_int),
-    "toist_last_error": ([c_char_p, c_size_t], ctypes.c_int),
-    "toist_matcher": ([c_void_p] * 6 + [c_int32] * 5 + [c_float] * 3 + [c_void_p] * 5, ctypes.c_int),
-    "toist_gemm_bf16": ([POINTER(Gemm), c_void_p], ctypes.c_int),
-    "toist_group_fill": ([c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_layernorm_fwd": ([c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_layernorm_bwd": ([c_void_p] * 5 + [c_int32, c_int32] + [c_void_p] * 4 + [c_float, c_uint64, c_void_p, c_void_p, c_int32, c_void_p], ctypes.c_int),
-    "toist_layernorm_bwd_blocks": ([c_int32], ctypes.c_int),
-    "toist_softmax_fwd": ([c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_float, c_uint64, c_void_p, c_void_p], ctypes.c_int),
-    "toist_softmax_bwd": ([c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_uint64, c_void_p, c_void_p], ctypes.c_int),
-    "toist_colsum": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_add_bf16": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p], ctypes.c_int),
-    "toist_pack_image": ([c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_maxpool3x3s2": ([c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_stem_fwd": ([c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_unpack_nhwc": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_stamp": ([c_void_p, c_int32, c_void_p], ctypes.c_int),
-    "toist_text_prep": ([c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_sine_position": ([c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_sine_position_seq": ([c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_int32, c_void_p], ctypes.c_int),
-    "toist_embed_fwd": ([c_void_p] * 5 + [c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_embed_bwd": ([c_void_p] * 3 + [c_int32, c_int32, c_int64] + [c_void_p] * 4, ctypes.c_int),
-    "toist_criterion_fwd": ([c_void_p] * 9 + [c_int32] * 4 + [c_float, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_criterion_bwd": ([c_void_p] * 9 + [c_int32] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_contrastive_fwd": ([c_void_p] * 8 + [c_int32] * 5 + [c_float, c_void_p, c_void_p], ctypes.c_int),
-    "toist_contrastive_bwd": ([c_void_p] * 8 + [c_int32] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_contrastive_bwd_ws": ([c_void_p] * 8 + [c_int32] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_l2norm_fwd": ([c_void_p, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_l2norm_bwd": ([c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_attnmap_softmax_fwd": ([c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p], ctypes.c_int),
-    "toist_attnmap_softmax_bwd": ([c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p], ctypes.c_int),
-    "toist_groupnorm_apply": ([c_void_p] * 4 + [c_int32] * 4 + [c_float, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_groupnorm_fwd": ([c_void_p] * 3 + [c_int32] * 4 + [c_float, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_groupnorm_bwd": ([c_void_p] * 6 + [c_int32] * 4 + [c_float, c_int32] + [c_void_p] * 5, ctypes.c_int),
-    "toist_upsample_add": ([c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p], ctypes.c_int),
-    "toist_upsample_add_bwd": ([c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p], ctypes.c_int),
-    "toist_sum_queries": ([c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p], ctypes.c_int),
-    "toist_upsample_add_rows": ([c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p], ctypes.c_int),
-    "toist_resize_add": ([c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p, c_void_p], ctypes.c_int),
-    "toist_resize_add_bwd": ([c_void_p] + [c_int32] * 6 + [c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_stage_fwd": ([c_void_p] * 9 + [c_int32] * 9 + [c_float, c_void_p], ctypes.c_int),
-    "toist_sum_segments": ([c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_loss_fwd": ([c_void_p] * 4 + [c_int32] * 5 + [c_float, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_loss_bwd": ([c_void_p] * 4 + [c_int32] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_loss_bwd_compact": ([c_void_p] * 4 + [c_int32] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_dropout_bf16": ([c_void_p, c_int64, c_float, c_uint64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_attn2_splits": ([c_int32], ctypes.c_int),
-    "toist_attn2_fwd": ([c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p] + [c_int32] * 5 + [c_float, c_float, c_uint64, c_void_p, c_void_p,
-                        c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_attn2_bwd": ([c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p] + [c_int32] * 5 +
-                        [c_float, c_float, c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_rowgemm_blocks": ([c_int32], ctypes.c_int),
-    "toist_rowgemm": ([POINTER(RowGemm), c_void_p], ctypes.c_int),
-    "toist_xdec_supported": ([c_int32] * 4, ctypes.c_int),
-    "toist_xdec_fwd": ([POINTER(Xdec), c_void_p], ctypes.c_int),
-    "toist_xdec_bwd": ([POINTER(XdecBwd), c_void_p], ctypes.c_int),
-    "toist_scatter_rows_f32": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p], ctypes.c_int),
-    "toist_kmeans": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_float, c_int32,
-                     c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_attn_small_fwd": ([c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p] + [c_int32] * 4 + [c_float, c_float, c_uint64, c_void_p, c_void_p,
-                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_attn_small_bwd": ([c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p] + [c_int32] * 4 + [c_float, c_float, c_uint64, c_void_p, c_void_p,
-                             c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_conv3x3_small": ([c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p], ctypes.c_int),
-    "toist_wgrad3x3_small_blocks": ([], ctypes.c_int),
-    "toist_wgrad3x3_small": ([c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p], ctypes.c_int),
-    "toist_lsap": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_gemm_effective_split": ([POINTER(Gemm)], ctypes.c_int),
-    "toist_gemm_pick_tile": ([POINTER(Gemm)], ctypes.c_int),
-    "toist_splitk_reduce_batch": ([c_void_p, c_int32, c_void_p], ctypes.c_int),
-    "toist_opt_chunk_elems": ([], ctypes.c_int),
-    "toist_opt_sqnorm": ([c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_opt_finish_norm": ([c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p], ctypes.c_int),
-    "toist_opt_finish_norm_guarded": ([c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p], ctypes.c_int),
-    "toist_opt_adamw_ema": ([c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_void_p], ctypes.c_int),
-    "toist_opt_adamw_ema_blocks": ([c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int32, c_void_p], ctypes.c_int),
-    "toist_mask_resize_pack": ([c_void_p] + [c_int32] * 9 + [c_float, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_resize_pack_batch": ([c_void_p] + [c_int32] * 6 + [c_void_p, c_int32, c_int32, ctypes.c_longlong, c_float, c_void_p, c_void_p], ctypes.c_int),
-    "toist_postprocess": ([c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32] + [c_void_p] * 4, ctypes.c_int),
-    "toist_mask_pack": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_unpack": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_area": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_iou": ([c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_rle_count": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_mask_rle_emit": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
-    "toist_coco_match": ([c_void_p] * 8 + [c_int32, c_void_p, c_int32, c_void_p, c_int32] + [c_void_p] * 5, ctypes.c_int),
-    "toist_mask_rle_counts": ([c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-    "toist_image_prep": ([c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
-                         ctypes.c_longlong, c_void_p], ctypes.c_int),
-    "toist_target_masks": ([c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_int32, c_int32, c_int32, c_void_p, c_void_p], ctypes.c_int),
-}
+# the descriptors the launchers pass with ctypes.byref: their pointer parameters are typed, every other pointer is a c_void_p
+_BYREF = {"toist_gemm": Gemm, "toist_rowgemm_desc": RowGemm, "toist_xdec_desc": Xdec, "toist_xdec_bwd_desc": XdecBwd}
+SIGNATURES = parse_signatures(_HEADER, _BYREF)
 
 _lib = None
 
 
 def exported_symbols():
     """Names every include/toist_hip.h entry point must be exported under."""
-    return sorted(_SIGNATURES)
+    return sorted(SIGNATURES)
 
 
 def lib():
@@ -211,10 +195,10 @@ def lib():
                 "(toist_amd has no CPU / eager fallback)"
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in _SIGNATURES.items():
+        for name, argtypes in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
-            fn.restype = restype
+            fn.restype = ctypes.c_int
         _lib = handle
     return _lib
 

@@ -53,9 +53,9 @@ def _workspace(elems, device):
 # A weight-gradient GEMM with few output tiles is cut into k-slices whose fp32 partials land in an arena; with
 # defer_reduce=True the fold into the gradient buffer is not launched per GEMM (178 launches of ~6 us per step) but
 # queued (toist_amd/folds.py).  The queue must be flushed before anything reads those outputs: engine.Tape.backward() does it at program end.
-GEMM_DEFER_REDUCE = 2
-GEMM_SPLIT_EPILOGUE = 4
-GEMM_COLSUM_SLICES = 32768    # include/toist_hip.h: a_colsum = [k-slice][M] partials, folded in slice order
+GEMM_DEFER_REDUCE = _lib.CONSTANTS["TOIST_GEMM_DEFER_REDUCE"]
+GEMM_SPLIT_EPILOGUE = _lib.CONSTANTS["TOIST_GEMM_SPLIT_EPILOGUE"]
+GEMM_COLSUM_SLICES = _lib.CONSTANTS["TOIST_GEMM_COLSUM_SLICES"]    # a_colsum = [k-slice][M] partials, folded in slice order
 
 
 def flush_reductions():

@@ -14,7 +14,7 @@ There is no CPU path: tensors must live on the GPU and the HIP library must be l
 import numpy as np
 import torch
 
-from . import engine
+from . import _lib, engine
 from . import kernels as k
 from .knobs import knob
 
@@ -23,6 +23,9 @@ LATE_BLOCKS = knob("TOIST_LATE_BLOCKS", 0)     # workgroups of a late group's up
 _TENSOR_DT = np.dtype([("p", "<i8"), ("m", "<i8"), ("v", "<i8"), ("ema", "<i8"), ("w", "<i8"), ("row_scale", "<i8"),
                        ("numel", "<i8"), ("row_len", "<i4"), ("group", "<i4")])
 assert _TENSOR_DT.itemsize == 64  # toist_opt_tensor
+_GROUP_DT = np.dtype([("lr", "<f4"), ("weight_decay", "<f4")])     # toist_opt_group
+_STATE_DT = np.dtype([("clip_coef", "<f4"), ("grad_norm", "<f4"), ("bias1", "<f4"), ("bias2_sqrt", "<f4"),
+                      ("step", "<i4"), ("skipped", "<i4"), ("skipped_total", "<i4"), ("veto_mask", "<i4")])     # toist_opt_state
 
 
 def ema_pairs(model, model_ema):
@@ -88,7 +91,7 @@ class FusedClipAdamWEMA:
     non-finite and are skipped too.  With the option off (the default) nothing is ever skipped: NaN gradients reach the weights, as
     with torch.optim.AdamW."""
 
-    MAX_VETO = 8        # words of each kind (include/toist_hip.h: TOIST_OPT_MAX_VETO)
+    MAX_VETO = _lib.CONSTANTS["TOIST_OPT_MAX_VETO"]        # words of each kind
 
     def __init__(self, param_groups, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4, max_norm=0.1, ema=None, ema_decay=0.9998,
                  defer_ema=False, skip_nonfinite=False):
@@ -152,13 +155,13 @@ class FusedClipAdamWEMA:
         for p, e in zip(params, self._ema_of):
             if e is not None and (e.shape != p.shape or e.stride() != p.stride()):
                 raise ValueError("FusedClipAdamWEMA: an EMA tensor must share its source's shape and strides")
-        self.state = torch.zeros(32, dtype=torch.uint8, device=self.device)          # toist_opt_state
+        self.state = torch.zeros(_STATE_DT.itemsize, dtype=torch.uint8, device=self.device)          # toist_opt_state
         self.skip_nonfinite = bool(skip_nonfinite)
         # the veto words' addresses: fixed-address device tables (a captured finish-norm launch holds the tables, not the words), rewritten by add_veto
         self._veto_words = ([], [])                                                    # (int32 words, fp32 words): kept alive here
         self._veto_dev = tuple(torch.zeros(self.MAX_VETO, dtype=torch.int64, device=self.device) for _ in range(2)) if self.skip_nonfinite else None
         self._groups_host = None
-        self._groups_dev = torch.zeros(len(self.param_groups), 2, dtype=torch.float32, device=self.device)
+        self._groups_dev = torch.zeros(len(self.param_groups), len(_GROUP_DT.names), dtype=torch.float32, device=self.device)     # toist_opt_group rows
         self._chunk = k.opt_chunk_elems()
         n_t = len(params) + len(self._ema_only)
         # gradient-pointer table: two pinned host copies used alternately, each guarded by an event recorded behind its upload, so a host
@@ -185,7 +188,8 @@ class FusedClipAdamWEMA:
         cur = [(float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups]
         if cur != self._groups_host:
             self._groups_host = cur
-            self._groups_dev.copy_(torch.tensor(cur, dtype=torch.float32), non_blocking=False)
+            rows = np.array(cur, dtype=_GROUP_DT)         # (lr, weight_decay): the fields' order
+            self._groups_dev.copy_(torch.from_numpy(rows.view(np.float32).reshape(len(rows), -1)), non_blocking=False)
 
     def _build_table(self):
         rows = np.zeros(len(self.params) + len(self._ema_only), dtype=_TENSOR_DT)
@@ -428,11 +432,8 @@ class FusedClipAdamWEMA:
     def device_state(self):
         """{'clip_coef', 'grad_norm', 'bias1', 'bias2_sqrt', 'step', 'skipped', 'skipped_total', 'veto_mask'} read back from the device
         (synchronises).  step counts APPLIED steps; skipped: the last step() was vetoed (skip_nonfinite=True), veto_mask says why."""
-        raw = self.state.cpu().numpy()
-        f = raw[:16].view(np.float32)
-        i = raw[16:32].view(np.int32)
-        return {"clip_coef": float(f[0]), "grad_norm": float(f[1]), "bias1": float(f[2]), "bias2_sqrt": float(f[3]),
-                "step": int(i[0]), "skipped": bool(i[1]), "skipped_total": int(i[2]), "veto_mask": int(i[3])}
+        s = self.state.cpu().numpy().view(_STATE_DT)[0]
+        return {n: bool(s[n]) if n == "skipped" else s[n].item() for n in _STATE_DT.names}
 
     def state_dict(self):
         """torch.optim.AdamW's layout ({"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [{..., "params": [i, ...]}]}),
@@ -464,9 +465,9 @@ class FusedClipAdamWEMA:
             steps.append(int(float(st["step"])))
         if steps and min(steps) != max(steps):
             raise ValueError("FusedClipAdamWEMA.load_state_dict: parameters with different step counts (the fused tail keeps one counter)")
-        raw = np.zeros(32, dtype=np.uint8)          # (skipped / skipped_total / veto_mask are not part of a checkpoint: zero)
-        raw[16:20] = np.array([steps[0] if steps else 0], dtype=np.int32).view(np.uint8)
-        self.state.copy_(torch.from_numpy(raw))
+        raw = np.zeros(1, dtype=_STATE_DT)          # (skipped / skipped_total / veto_mask are not part of a checkpoint: zero)
+        raw["step"] = steps[0] if steps else 0
+        self.state.copy_(torch.from_numpy(raw.view(np.uint8)))
         for g, src in zip(self.param_groups, sd.get("param_groups", [])):
             g.update({kk: vv for kk, vv in src.items() if kk in ("lr", "weight_decay", "initial_lr")})
         self.sync_hyperparams()

@@ -665,7 +665,8 @@ TOIST_API int toist_lsap(const float* cost, const int64_t* offset, const int32_t
 /* flags bit 15: with split_k > 1 and no group, a_colsum is a [split][M] fp32 buffer that receives each k-slice's column sums (plain stores,
  * no atomics); the caller folds the slices in order (toist_splitk_reduce_batch with M = 1) -- a bias gradient that is the same in every run */
 #define TOIST_GEMM_COLSUM_SLICES 32768
-/* tile code the dispatcher would pick for this descriptor (`tile` = 0) */
+/* tile code toist_gemm_bf16 would run this descriptor on: the dispatcher's pick for `tile` = 0, for a forced `tile` its low byte -- or
+ * 137 / 138 where a weight-gradient kernel replaces 129 / 130 / 134.  Answered for descriptors toist_gemm_bf16 would refuse, too. */
 TOIST_API int toist_gemm_pick_tile(const toist_gemm* desc);
 typedef struct toist_reduce_desc {
     const float* ws;          /* [splits][M][N] fp32 partials                */

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "../../include/toist_hip.h"
+#include "tuning.h"
 
 typedef unsigned short bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -26,18 +27,6 @@ int check_launch(const char* what);  // hipGetLastError -> TOIST_EHIP / TOIST_OK
             return TOIST_EINVAL;                  \
         }                                         \
     } while (0)
-
-// ---- tuning switches --------------------------------------------------------------------
-// The dispatcher's thresholds were found with environment switches (tools/dbg/ab_*.sh).  A product build compiles them to their
-// defaults; `make KNOBS=1` (-DTOIST_TUNING_KNOBS) reads the environment once per process for A/B runs.
-#ifdef TOIST_TUNING_KNOBS
-inline long long tuning_knob(const char* name, long long dflt) {
-    const char* e = std::getenv(name);
-    return e ? std::atoll(e) : dflt;
-}
-#else
-inline long long tuning_knob(const char*, long long dflt) { return dflt; }
-#endif
 
 // ---- per-device one-time kernel attributes (> 64 KiB of dynamic LDS) ----------------------
 // hipFuncSetAttribute is per device; a process that drives several devices must set it on each.  Lock-free and idempotent: two

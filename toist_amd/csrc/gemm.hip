@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_route.h"
 
 namespace toist {
 
@@ -992,7 +993,7 @@ __global__ __launch_bounds__(256, (gemm_min_waves<BM, BN, NS>())) void gemm_kern
 //   dgrad    (A_CONVT, B_KROW): src = dy [N,H,W,Co], dy = 1-r, dx = 1-s, B tile k-major (k = co, columns = c)
 // Pipeline: patch double-buffered per chunk (its 28 pieces are issued one per wave during the first 7 taps of the
 // previous chunk), weight tiles in a 3-slot ring, one raw s_barrier per (chunk, tap) step, hand-counted vmcnt.
-constexpr int C3_BM = 128, C3_BN = 64, C3_BK = 64, C3_NP = 28, C3_NB = 3;
+constexpr int C3_BN = 64, C3_NB = 3;                    // C3_BM, C3_BK, C3_NP: gemm_route.h
 constexpr int C3_PATCH = C3_NP * 512;                 // elements per patch buffer (28 KiB)
 constexpr int C3_BT = C3_BN * C3_BK;                  // elements per weight tile (8 KiB)
 constexpr int C3_LDS = (2 * C3_PATCH + C3_NB * C3_BT) * 2;   // 80 KiB: two workgroups per CU
@@ -1189,7 +1190,6 @@ __global__ __launch_bounds__(256) void conv3_kernel(const toist_gemm p) {
 // spills (128 accumulator + fragment registers, ~40 for everything else) and no LDS band in the epilogue (fragments are finished where
 // the MFMA left them, 8-byte accesses).  Staged bytes per MFMA: half of the 64 x 64 tiling.
 #ifndef GEMM_UNIT   // main translation unit only
-constexpr int G8_BM = 128, G8_BN = 128, G8_BK = 64;
 constexpr int G8_TILE = G8_BM * G8_BK;                 // elements of one operand tile (16 KiB)
 constexpr int G8_STAGE_BYTES = 2 * G8_TILE * 2;        // A + B
 
@@ -1747,7 +1747,7 @@ __global__ __launch_bounds__(512, 2) void gemm128w_kernel(const toist_gemm p) {
 // tiles (the grouped 3x3 launch: 18 instead of 36 workgroups per problem, 2 rounds per XCD instead of 4).  8 waves = 4 x 2 of 64 x 64, no k-split
 // (so no fold in the epilogue); k-tiles of 32 pixels -- [32][256] + [32][128] bf16 = 24 KiB per ring slot, 6 slots, five k-tiles in flight --
 // keep the 16 MFMAs per wave and barrier of the 128 x 128 kernel.
-constexpr int G9_BM = 256, G9_BN = 128, G9_BK = 32, G9_NS = 6;
+constexpr int G9_BK = 32;                                // G9_BM, G9_BN, G9_NS: gemm_route.h
 constexpr int G9_A_BYTES = G9_BM * G9_BK * 2, G9_STAGE_BYTES = (G9_BM + G9_BN) * G9_BK * 2;     // 16 KiB, 24 KiB
 constexpr int G9_LDS = G9_NS * G9_STAGE_BYTES;                                                 // 144 KiB
 
@@ -1864,7 +1864,7 @@ __global__ __launch_bounds__(512, 2) void gemm256w_kernel(const toist_gemm p) {
         ++i_t;
     };
 #pragma unroll
-    for (int i = 0; i < NS - 1; ++i) issue(i);         // a slice holds at least NS k-tiles (gemm256w_applies)
+    for (int i = 0; i < NS - 1; ++i) issue(i);         // a slice holds at least NS k-tiles (gemm_route.cpp)
 
     int a_base[FM][2], b_base[FN][2];
     {
@@ -1969,24 +1969,6 @@ __global__ __launch_bounds__(512, 2) void gemm256w_kernel(const toist_gemm p) {
 
 #endif  // GEMM_UNIT (128x128 kernels)
 
-static bool aligned16(const void* p) { return (((size_t)p) & 15) == 0; }
-
-// what epilogue_lean (and the panel kernel's epilogue) covers
-static bool lean_epilogue_ok(const toist_gemm& d) {
-    // TOIST_LEAN_EPILOGUE: 0 = never, 1 = only scale / shift / residual / ReLU / mask, 2 (default) = also dropout, GELU, aux-based gradients, row map
-    static const int level = (int)tuning_knob("TOIST_LEAN_EPILOGUE", 2);
-    const toist_epilogue& e = d.epi;
-    if (level == 1 && (e.drop_where || e.cmap || (e.act != TOIST_ACT_NONE && e.act != TOIST_ACT_RELU && e.act != TOIST_ACT_MASK_POS))) return false;
-    if (level <= 0 || d.split_k > 1 || d.group != nullptr || d.a_colsum != nullptr) return false;
-    if (e.out_f32 || e.accumulate || e.rscale || e.pre_out || e.res_div > 0) return false;
-    if (e.act == TOIST_ACT_SIGMOID) return false;
-    if ((d.N % 8) != 0 || (d.ldc % 8) != 0 || !aligned16(d.c) || (d.cs_outer % 8) != 0 || (d.cs_inner % 8) != 0) return false;
-    if (e.res && ((e.ldr % 8) != 0 || !aligned16(e.res))) return false;
-    if (e.act >= TOIST_ACT_MASK_POS && (e.aux == nullptr || (e.ldaux % 8) != 0 || !aligned16(e.aux))) return false;
-    if ((e.scale && (((size_t)e.scale) & 15)) || (e.shift && (((size_t)e.shift) & 15))) return false;
-    return true;
-}
-
 // ---- short reductions (K <= 256): one resident weight panel per workgroup ------------------------------------------------
 // The 1x1 convolutions of ResNet layers 1-3 and their data gradients are GEMMs with K = 64 .. 256 and tens of thousands of rows
 // (12800 x 1024 x 256 at batch 8: 45 launches per step).  Through the generic tiles every 64x64 output tile stages 64 KB of
@@ -2076,7 +2058,7 @@ __global__ __launch_bounds__(256, 2) void panel_kernel(const toist_gemm p) {
                                   m0 + a_row[it] < M && t * BK + a_col[it] < K);
     };
 
-    // ---- lean epilogue (panel_applies admits only what it covers): bf16 rows of 8 columns, 16-byte accesses, optional per-column scale /
+    // ---- lean epilogue (gemm_route.cpp admits only what it covers): bf16 rows of 8 columns, 16-byte accesses, optional per-column scale /
     // shift, optional residual, ACT in {none, ReLU, mask by aux > 0}.  A thread finishes chunk c8 of band row `brow` of both bands; the
     // residual / mask chunks of a tile are requested one tile ahead. ----
     const int c8 = tid & 7, brow = tid >> 3;
@@ -2560,31 +2542,6 @@ __global__ __launch_bounds__(256, 2) void panel2_kernel(const toist_gemm p, cons
     }
 }
 
-// Tile code 135, or picked by the dispatcher (panel_min_tiles) when the call qualifies.
-static bool panel_applies(const toist_gemm& d) {
-    if (d.a_kind != TOIST_A_ROWK || (d.b_kind != TOIST_B_ROWK && d.b_kind != TOIST_B_KROW)) return false;
-    if (d.b_kind == TOIST_B_KROW && d.b.kin > 0) return false;
-    if (d.K > 256 || (d.K % 8) != 0 || (d.a.ld % 8) != 0 || (d.b.ld % 8) != 0) return false;
-    if (d.batch != 1 || d.split_k != 1 || d.group != nullptr || d.a2 != nullptr || d.a_colsum != nullptr || (d.flags & 1)) return false;
-    if ((d.N + 63) / 64 > 64 || (d.M + 63) / 64 < 8) return false;      // row tiles are dealt to 8 XCDs: too few would leave XCDs idle
-    if ((long long)d.M * d.a.ld >= (1ll << 30) || (long long)d.K * d.b.ld >= (1ll << 30) || (long long)d.N * d.b.ld >= (1ll << 30)) return false;   // 32-bit element offsets
-    // the kernel's lean epilogue: bf16 rows in whole 16-byte chunks, per-column scale / shift, residual, {none, ReLU, aux > 0 mask}
-    const toist_epilogue& e = d.epi;
-    if (e.out_f32 || e.accumulate || e.rscale || e.pre_out || e.cmap || e.res_div > 0) return false;
-    if (e.drop_where && !(e.drop_p >= 0.f && e.drop_p < 1.f)) return false;
-    if (e.act != TOIST_ACT_NONE && e.act != TOIST_ACT_RELU && e.act != TOIST_ACT_MASK_POS) return false;
-    if ((d.N % 8) != 0 || (d.ldc % 8) != 0 || !aligned16(d.c) || (long long)d.M * d.ldc >= (1ll << 31)) return false;
-    if (e.res && ((e.ldr % 8) != 0 || !aligned16(e.res) || (long long)d.M * e.ldr >= (1ll << 31))) return false;
-    if (e.act == TOIST_ACT_MASK_POS && ((e.ldaux % 8) != 0 || !aligned16(e.aux) || (long long)d.M * e.ldaux >= (1ll << 31))) return false;
-    if ((e.scale && (((size_t)e.scale) & 15)) || (e.shift && (((size_t)e.shift) & 15))) return false;
-    return true;
-}
-
-static long long panel_min_tiles() {   // (32 -- the 800-query decoder linears, 52 tiles -- measured 559.8 -> 563.8 images/s over two noisy rounds: not taken)
-    static const long long v = tuning_knob("TOIST_PANEL_MIN_TILES", 128);
-    return v;
-}
-
 static int launch_panel(const toist_gemm& d, hipStream_t st) {
     const int nt_m = (d.M + 63) / 64, nt_n = (d.N + 63) / 64;
     const int m_per = (nt_m + 7) / 8;
@@ -2605,16 +2562,6 @@ static int launch_panel(const toist_gemm& d, hipStream_t st) {
     }
 #undef TOIST_PANEL
     return TOIST_OK;
-}
-
-// panel2_kernel: what panel_applies admits, with byte offsets that fit the 2 GiB buffer descriptors of the DMA / store path
-static bool panel2_applies(const toist_gemm& d) {
-    if (!panel_applies(d)) return false;
-    const long long lim = 1ll << 30;
-    if ((long long)d.M * d.ldc >= lim) return false;
-    if (d.epi.res && (long long)d.M * d.epi.ldr >= lim) return false;
-    if (d.epi.act == TOIST_ACT_MASK_POS && (long long)d.M * d.epi.ldaux >= lim) return false;
-    return true;
 }
 
 // variant = ring code of the tile word (tile >> 8): low nibble = ring stages (2..4; 0 = pick), bit 4 = 32-row blocks
@@ -2677,67 +2624,7 @@ static int launch_panel2(const toist_gemm& d, int variant, hipStream_t st) {
     return TOIST_OK;
 }
 
-// true when the halo kernel covers this call (the dispatcher then never looks at the tile code)
-static bool conv3_applies(const toist_gemm& d) {
-    const bool fwd = d.a_kind == TOIST_A_CONV && d.b_kind == TOIST_B_ROWK;
-    const bool dgr = d.a_kind == TOIST_A_CONVT && d.b_kind == TOIST_B_KROW;
-    if (!fwd && !dgr) return false;
-    const toist_operand& a = d.a;
-    if (a.R != 3 || a.S != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return false;
-    if (a.PH != a.SH || a.PW != a.SW || (a.SC % C3_BK) != 0 || d.K != 9 * a.SC) return false;
-    if (C3_BM + 2 * (a.SW + 1) > C3_NP * 8) return false;            // patch rows must fit the 28 pieces
-    if (d.batch != 1 || d.split_k != 1 || d.a_colsum != nullptr) return false;
-    if ((long long)d.M * a.SC >= (1ll << 30)) return false;           // 32-bit element offsets
-    if (fwd && d.b.ld != d.K) return false;
-    if (dgr && (d.b.kin != a.SC || (d.N % 8) != 0)) return false;
-    return d.M >= 2048;                                                // tiny grids: the generic 64x64 tiles fill more CUs
-}
-
 #ifndef GEMM_UNIT
-static int clamp_split(int split_k, int K, int tile);
-// gemm128_kernel (tile code 136): one problem, K a multiple of 64 with at least 4 k-tiles, bf16 rows finished by {alpha, scale, shift,
-// residual, ReLU | aux > 0 mask}.  Operands: row-major A with row-major or plain k-major B (1x1 convolutions, nn.Linear and their data
-// gradients); convolution gather of stride 1 or 2 with row-major weights (forward); its stride-1 transposed gather on a same-size plane with the
-// two-level k-major weights (data gradient) -- up to 16 taps, source channels a multiple of 64.
-static bool gemm128_applies(const toist_gemm& d) {
-    const bool plain = d.a_kind == TOIST_A_ROWK && (d.b_kind == TOIST_B_ROWK || (d.b_kind == TOIST_B_KROW && d.b.kin == 0));
-    const bool fwd = d.a_kind == TOIST_A_CONV && d.b_kind == TOIST_B_ROWK;
-    const bool dgr = d.a_kind == TOIST_A_CONVT && d.b_kind == TOIST_B_KROW;
-    if (!plain && !fwd && !dgr) return false;
-    if (d.K < 256 || (d.K % 64) != 0 || (d.b.ld % 8) != 0) return false;
-    if (d.batch != 1 || d.split_k != 1 || d.group != nullptr || d.a2 != nullptr || d.a_colsum != nullptr || (d.flags & 1)) return false;
-    const long long lim = 1ll << 30;
-    if ((long long)d.K * d.b.ld >= lim || (long long)d.N * d.b.ld >= lim) return false;       // 32-bit byte offsets
-    if (plain) {
-        if ((d.a.ld % 8) != 0 || (long long)d.M * d.a.ld >= lim) return false;
-    } else {
-        const toist_operand& a = d.a;
-        if ((a.stride != 1 && !fwd) || a.stride < 1 || a.stride > 2 || a.R * a.S > 16 || (a.SC % 64) != 0 || d.K != a.R * a.S * a.SC) return false;
-        if ((long long)(d.M / (a.PH * a.PW) + 1) * a.SH * a.SW * a.SC >= lim) return false;
-        if (fwd && d.b.ld != d.K) return false;
-        if (dgr && (a.PH != a.SH || a.PW != a.SW || d.b.kin != a.SC)) return false;
-        if (dgr && (a.pad - (a.R - 1) * a.dil > 0 || a.pad - (a.S - 1) * a.dil > 0)) return false;   // the shifted base must not lie beyond tap (0, 0)
-    }
-    const toist_epilogue& e = d.epi;
-    if (!lean_epilogue_ok(d) || e.drop_where || e.cmap) return false;
-    if (e.act != TOIST_ACT_NONE && e.act != TOIST_ACT_RELU && e.act != TOIST_ACT_MASK_POS) return false;
-    if ((d.N % 8) != 0) return false;                     // ldc / ldr / ldaux % 8 and 16-byte bases: lean_epilogue_ok above
-    return true;
-}
-
-// Where the dispatcher picks it (profiles/r03_gemm128_us.txt): one block per CU, so it needs about a chip of 128 x 128 tiles and a deep
-// reduction to amortise its prologue / k-fold epilogue.  Gathers: every stride-1 3x3 of layers 2-4 at the bench batch (-1 .. -16 us per
-// launch against the 64 x 64 tiles and the halo kernel).  Plain GEMMs: K >= 768 from 150 tiles on (12800 x 256 x 1024: 14.7 / 15.5 vs
-// 18.2 / 20.3 us forward / data gradient, 12800 x 512 x 1024: 25.4 / 27.5 vs 29.2 / 31.8, 4096^3: 150 vs 169); K = 512 loses (two rounds of
-// 8 k-tiles do not amortise the fixed costs), 100 tiles are a draw.
-static bool gemm128_pays(const toist_gemm& d) {
-    static const int on = (int)tuning_knob("TOIST_GEMM128", 1);
-    if (!on || !gemm128_applies(d)) return false;
-    const long long tiles = (long long)((d.M + G8_BM - 1) / G8_BM) * ((d.N + G8_BN - 1) / G8_BN);
-    if (d.a_kind != TOIST_A_ROWK) return tiles >= 96 && (d.N % G8_BN) == 0;
-    return d.K >= 768 && tiles >= 150;
-}
-
 template <int NS>
 static int launch_gemm128_ring(const toist_gemm& d, hipStream_t st) {
     static std::atomic<unsigned long long> done{0};
@@ -2765,58 +2652,6 @@ static int launch_gemm128(const toist_gemm& d, hipStream_t st) {
     return (ring == 5 && d.K >= 5 * G8_BK) ? launch_gemm128_ring<5>(d, st) : launch_gemm128_ring<4>(d, st);
 }
 
-// gemm128w_kernel (tile code 137): weight gradients -- k-major A (dy [pixels][Co]), B = k-major rows (1x1) or the stride-1 same-size
-// gather with whole 128-column tiles inside a tap; f32 output with alpha / rscale / accumulate, or k-slice partials; grouped or single.
-static bool gemm128w_applies(const toist_gemm& d) {
-    if (d.a_kind != TOIST_A_KROW) return false;
-    const bool plain = d.b_kind == TOIST_B_KROW && d.b.kin == 0, gather = d.b_kind == TOIST_B_CONVX;
-    if (!plain && !gather) return false;
-    if ((d.K % 64) != 0 || (d.M % 8) != 0 || (d.N % 8) != 0 || (d.a.ld % 8) != 0) return false;
-    if (d.batch_inner != 1 || (d.batch != 1 && d.group == nullptr) || d.a2 != nullptr || d.a_colsum != nullptr || (d.flags & (1 | TOIST_GEMM_SPLIT_EPILOGUE))) return false;
-    const int split = clamp_split(d.split_k, d.K, 65);                                  // the slices the launch will really make
-    const int ktiles = d.K / 64, kper = (ktiles + split - 1) / split;
-    if (kper < 4 || (long long)(split - 1) * kper + 4 > ktiles) return false;          // every k-slice holds at least 4 k-tiles
-    if (split > 1 && d.workspace == nullptr) return false;
-    const long long lim = 1ll << 30;
-    if ((long long)d.K * d.a.ld >= lim) return false;                                   // 32-bit byte offsets
-    if (plain) {
-        if ((d.b.ld % 8) != 0 || (long long)d.K * d.b.ld >= lim) return false;
-    } else {
-        const toist_operand& b = d.b;
-        if (b.stride < 1 || b.stride > 2 || (b.SC % 128) != 0 || d.N != b.R * b.S * b.SC) return false;
-        if (b.stride == 1 && (b.PH != b.SH || b.PW != b.SW)) return false;                 // stride 1: the same-size plane trick (address = pixel + constant)
-        if ((d.K % (b.PH * b.PW)) != 0) return false;
-        if ((long long)(d.K / (b.PH * b.PW) + 1) * b.SH * b.SW * b.SC + (long long)b.SW * (b.pad + 1) * b.SC >= lim) return false;
-    }
-    const toist_epilogue& e = d.epi;
-    if (!e.out_f32 || e.scale || e.shift || e.res || e.pre_out || e.act != TOIST_ACT_NONE || e.drop_where || e.cmap || e.res_div > 0) return false;
-    if ((d.ldc % 4) != 0 || (((size_t)d.c) & 15) != 0) return false;
-    return true;
-}
-
-// where it replaces the grouped / split tiles the host asked for (profiles/r03_gemm128w_us.txt)
-static bool gemm128w_pays(const toist_gemm& d) {
-    static const int on = (int)tuning_knob("TOIST_GEMM128W", 1);
-    if (!on || !gemm128w_applies(d)) return false;
-    const long long wgs = (long long)((d.M + G8_BM - 1) / G8_BM) * ((d.N + G8_BN - 1) / G8_BN) * d.batch * clamp_split(d.split_k, d.K, 65);
-    return wgs >= 128 && (d.M % 64) == 0 && (d.N % 128) == 0;
-}
-
-// gemm256w_kernel (tile code 138): what gemm128w_kernel takes, with M a multiple of 256 and k-slices of at least 6 x 32 rows
-static bool gemm256w_applies(const toist_gemm& d) {
-    if (!gemm128w_applies(d) || (d.M % G9_BM) != 0 || (d.N % G9_BN) != 0) return false;
-    const int split = clamp_split(d.split_k, d.K, 65);
-    const int k64 = d.K / 64, kper = (k64 + split - 1) / split;
-    return 2 * (k64 - (split - 1) * kper) >= G9_NS;      // the last (shortest) slice fills the ring
-}
-
-static bool gemm256w_pays(const toist_gemm& d) {
-    static const int on = (int)tuning_knob("TOIST_GEMM256W", 1);
-    if (!on || !gemm256w_applies(d)) return false;
-    const long long wgs = (long long)(d.M / G9_BM) * (d.N / G9_BN) * d.batch * clamp_split(d.split_k, d.K, 65);
-    return wgs >= 128;
-}
-
 static int launch_gemm256w(const toist_gemm& d, hipStream_t st) {
     static std::atomic<unsigned long long> done{0};
     if (!lds_attr_once_flag(done, [] {
@@ -2826,8 +2661,7 @@ static int launch_gemm256w(const toist_gemm& d, hipStream_t st) {
         set_last_error("toist_gemm_bf16: cannot enable %d bytes of LDS for the 256x128 weight-gradient kernel", G9_LDS);
         return TOIST_EHIP;
     }
-    toist_gemm dd = d;
-    dd.split_k = clamp_split(d.split_k, d.K, 65);
+    const toist_gemm& dd = d;                                       // split_k: the slices gemm_route() planned
     const int tiles = (d.M / G9_BM) * (d.N / G9_BN);
     const int nz = dd.batch * dd.split_k;
     dim3 grid((tiles + 7) & ~7, nz, 1);
@@ -2835,14 +2669,6 @@ static int launch_gemm256w(const toist_gemm& d, hipStream_t st) {
     if (d.b_kind == TOIST_B_CONVX) hipLaunchKernelGGL((gemm256w_kernel<TOIST_B_CONVX>), grid, dim3(512), G9_LDS, st, dd);
     else hipLaunchKernelGGL((gemm256w_kernel<TOIST_B_KROW>), grid, dim3(512), G9_LDS, st, dd);
     return TOIST_OK;
-}
-
-// the big generic tiles the host asks for on (grouped) weight gradients -- and the automatic choice -- give way to the 128x128 kernel
-static int wgrad_tile_replaced(const toist_gemm& d) {       // 0 = no, else 137 / 138
-    const int t = d.tile & 255;
-    if (!((t == 0 || t == 129 || t == 130 || t == 134) && d.a_kind == TOIST_A_KROW)) return 0;
-    if (gemm256w_pays(d)) return 138;
-    return gemm128w_pays(d) ? 137 : 0;
 }
 
 static int launch_gemm128w(const toist_gemm& d, hipStream_t st) {
@@ -2857,8 +2683,7 @@ static int launch_gemm128w(const toist_gemm& d, hipStream_t st) {
         return TOIST_EHIP;
     }
     const int tiles = ((d.M + G8_BM - 1) / G8_BM) * ((d.N + G8_BN - 1) / G8_BN);
-    toist_gemm dd = d;
-    dd.split_k = clamp_split(d.split_k, d.K, 65);
+    const toist_gemm& dd = d;                                       // split_k: the slices gemm_route() planned
     const int nz = dd.batch * dd.split_k;
     dim3 grid((tiles + 7) & ~7, nz, 1);
     if (nz >= 8) grid = dim3(8 * ((nz + 7) / 8) * tiles, 1, 1);     // pairs pinned to XCDs (see the kernel)
@@ -3112,6 +2937,7 @@ static int launch_variant(const toist_gemm& d, int ring, hipStream_t st) {
     return TOIST_OK;
 }
 
+// (the operand pairs below are gemm_route.cpp's generic_operands(): it refuses any other pair before a launch gets here)
 template <int BM, int BN, int BK>
 static int launch_tile(const toist_gemm& d, int ring, hipStream_t st) {
     const int ak = d.a_kind, bk = d.b_kind;
@@ -3131,6 +2957,7 @@ static int launch_tile(const toist_gemm& d, int ring, hipStream_t st) {
 // hipcc needs ~5 minutes for every tile family in one unit.  gemm_tiles_b.hip and gemm_tiles_c.hip include this file with GEMM_UNIT = 1 / 2
 // and compile one launch_tiles_*() each (make -j builds the three side by side); everything below this block -- dispatcher, plain kernels,
 // the extern "C" entry points -- belongs to the main unit.
+// (the tile codes of the three are gemm_route.cpp's generic_tile(): it refuses any other code before a launch gets here)
 int launch_tiles_a(int tile, const toist_gemm& d, int ring, hipStream_t st);   // 64x64x32, 128x128x{32,64}, 128x32x64, 32x128x64
 int launch_tiles_b(int tile, const toist_gemm& d, int ring, hipStream_t st);   // 64x64x64
 int launch_tiles_c(int tile, const toist_gemm& d, int ring, hipStream_t st);   // 128x64x64, 64x128x64
@@ -3154,46 +2981,6 @@ int launch_tiles_c(int tile, const toist_gemm& d, int ring, hipStream_t st) {
 }
 #endif
 
-#ifndef GEMM_UNIT
-
-// tile code the dispatcher picks for tile == 0
-static int auto_tile(const toist_gemm& d) {
-    // measured on MI355X (tools/sweep_gemm.py): 128x128x64 only pays once >= ~4 tiles per CU exist and K
-    // is deep; below that 64x64x64 tiles keep more workgroups (and DMA) in flight.
-    const long long t128 = (long long)((d.M + 127) / 128) * ((d.N + 127) / 128) * (d.batch > 0 ? d.batch : 1) * (d.split_k > 0 ? d.split_k : 1);
-    // (round 2: the 128x64 tile beats 128x128 on every large problem measured -- 4096^3: 675 vs 555 TFLOP/s, 8192 x 8192 x 2048: 708 vs 443;
-    // 128x128 needs 231-247 VGPRs, two waves per SIMD)
-    static const int big_tile = (int)tuning_knob("TOIST_BIG_TILE", 130);
-    if (t128 >= 1024 && d.K >= 1024) return big_tile;
-    if (d.K > 64 && d.N <= 32 && d.M >= 4096) return 132;   // a 64-wide tile would idle half (or more) of its MFMA columns
-    if (d.K > 64 && d.M <= 32 && d.N >= 128) return 133;
-    // Wave quantisation of the 64x64 grid: four two-slot workgroups fit a CU (1024 slots; three before the occupancy hint of gemm_kernel,
-    // when 800 tiles -- ResNet layer3 at batch 8 -- were a full round plus a 4 % one and this rule bought 28 -> 21 us).  When the last
-    // round would be < 1/4 full and there are at most two full ones, 64x128 tiles (half the workgroups, half the A traffic through LDS)
-    // finish in fewer rounds: 17000 x 256 x 1024 25.8 -> 21.2 us, 20000 x 256 x 1024 26.6 -> 22.1, 12800 x 384 x 1024 25.9 -> 22.1; at
-    // 1.5-1.6 rounds (12800 x 512 x 1024) the 64x64 grid stays ahead (29.3 vs 31.0), as it does below one round (tools/dbg/gemm_tiles.py).
-    const long long t64 = (long long)((d.M + 63) / 64) * ((d.N + 63) / 64) * (d.batch > 0 ? d.batch : 1) * (d.split_k > 0 ? d.split_k : 1);
-    const long long rounds = t64 / 1024, last = t64 - rounds * 1024;
-    static const bool wide = tuning_knob("TOIST_TILE_64x128", 1) != 0;
-    if (wide && d.K >= 512 && (d.N % 128) == 0 && rounds >= 1 && rounds <= 2 && last * 4 < 1024 &&
-        (d.a_kind == TOIST_A_ROWK || d.a_kind == TOIST_A_CONV) && !d.group)
-        return 134;
-    // (a nearly full single round -- 800 tiles of 1024 -- stays on 64x64: 64x128 there measured 552 vs 556 images/s for the conv gathers, 546 with row-major A too)
-    return (d.K > 64) ? 65 : 64;
-}
-
-// drop k-slices that would own no k-tile
-static int clamp_split(int split_k, int K, int tile) {
-    const int bk0 = (tile == 64 || tile == 128) ? 32 : 64;
-    const int ktiles = (K + bk0 - 1) / bk0;
-    if (split_k < 1) split_k = 1;
-    if (split_k > ktiles) split_k = ktiles;
-    const int kper = (ktiles + split_k - 1) / split_k;
-    return (ktiles + kper - 1) / kper;
-}
-
-#endif  // GEMM_UNIT (dispatcher helpers)
-
 }  // namespace toist
 
 #ifndef GEMM_UNIT
@@ -3215,30 +3002,6 @@ extern "C" int toist_group_fill(const toist_group* rows, int n, toist_group* tab
     for (int i = n; i < GROUP_MAX; ++i) a.g[i] = toist_group{nullptr, nullptr, 0, 0, 0, 0};
     hipLaunchKernelGGL(group_fill_kernel, dim3(1), dim3(GROUP_MAX), 0, (hipStream_t)stream, a, n, table);
     return check_launch("toist_group_fill");
-}
-
-extern "C" int toist_gemm_pick_tile(const toist_gemm* desc) {
-    using namespace toist;
-    if (desc == nullptr) return 0;
-    toist_gemm d = *desc;
-    if (d.batch <= 0) d.batch = 1;
-    if (d.split_k <= 0) d.split_k = 1;
-    if (const int wt = wgrad_tile_replaced(d)) return wt;
-    if (desc->tile & 255) return desc->tile & 255;
-    if (gemm128_pays(d)) return 136;                    // the order of toist_gemm_bf16's dispatch
-    if (d.a_kind == TOIST_A_CONVT && conv3_applies(d)) return 131;
-    if ((long long)((d.M + 63) / 64) * ((d.N + 63) / 64) >= panel_min_tiles() && panel_applies(d)) return 135;
-    return auto_tile(d);
-}
-
-extern "C" int toist_gemm_effective_split(const toist_gemm* desc) {
-    using namespace toist;
-    if (desc == nullptr) return 0;
-    toist_gemm d = *desc;
-    if (d.batch <= 0) d.batch = 1;
-    if (d.workspace == nullptr) d.workspace = (float*)16;      // asked BEFORE the caller sizes the scratch: "a workspace will be there"
-    const int tile = wgrad_tile_replaced(d) ? 137 : (desc->tile & 255) ? (desc->tile & 255) : auto_tile(*desc);     // 137 and 138 slice alike
-    return clamp_split(desc->split_k, desc->K, tile);
 }
 
 extern "C" int toist_splitk_reduce_batch(const toist_reduce_desc* descs, int n, void* stream) {
@@ -3283,104 +3046,29 @@ extern "C" int toist_gemm_bf16(const toist_gemm* desc, void* stream) {
     using namespace toist;
     TOIST_REQUIRE(desc != nullptr, "toist_gemm_bf16: null descriptor");
     toist_gemm d = *desc;
-    TOIST_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0, "toist_gemm_bf16: bad shape M=%d N=%d K=%d", d.M, d.N, d.K);
-    if (d.batch <= 0) d.batch = 1;
-    if (d.batch_inner <= 0) d.batch_inner = 1;
-    if (d.split_k <= 0) d.split_k = 1;
-    TOIST_REQUIRE(d.a.ptr && d.b.ptr && d.c, "toist_gemm_bf16: null operand");
-    TOIST_REQUIRE(aligned16(d.a.ptr) && aligned16(d.b.ptr), "toist_gemm_bf16: A/B must be 16-byte aligned");
-    const toist_operand* ops[2] = {&d.a, &d.b};
-    const int kinds[2] = {d.a_kind, d.b_kind == TOIST_B_CONVX ? TOIST_A_CONV : (d.b_kind == TOIST_B_KROW ? TOIST_A_KROW : TOIST_A_ROWK)};
-    for (int i = 0; i < 2; ++i) {
-        const toist_operand& o = *ops[i];
-        TOIST_REQUIRE((o.bs_outer % 8) == 0 && (o.bs_inner % 8) == 0, "toist_gemm_bf16: batch strides must be multiples of 8 elements");
-        if (kinds[i] == TOIST_A_CONV || kinds[i] == TOIST_A_CONVT) {
-            TOIST_REQUIRE(o.SC > 0 && (o.SC % 8) == 0, "toist_gemm_bf16: source channels must be a multiple of 8 (got %d)", o.SC);
-            TOIST_REQUIRE(o.R > 0 && o.S > 0 && o.stride > 0 && o.dil > 0 && o.PH > 0 && o.PW > 0 && o.SH > 0 && o.SW > 0,
-                          "toist_gemm_bf16: bad conv geometry");
-        } else {
-            TOIST_REQUIRE(o.ld > 0 && (o.ld % 8) == 0, "toist_gemm_bf16: leading dimension must be a multiple of 8 (got %d)", o.ld);
-        }
-    }
-    if (d.b_kind == TOIST_B_CONVX) TOIST_REQUIRE((d.N % 8) == 0, "toist_gemm_bf16: CONVX needs N %% 8 == 0");
-    // k-major operands are read in 8-row chunks: rows beyond M/N inside the last chunk are read
-    // (and discarded), so ld must cover the rounded-up extent.
-    if (d.a_kind == TOIST_A_KROW) TOIST_REQUIRE(d.a.ld >= ((d.M + 7) & ~7), "toist_gemm_bf16: A_KROW needs lda >= roundup8(M)");
-    if (d.b_kind == TOIST_B_KROW) TOIST_REQUIRE(d.b.ld >= ((d.N + 7) & ~7), "toist_gemm_bf16: B_KROW needs ldb >= roundup8(N)");
-    const bool split_epi = (d.flags & TOIST_GEMM_SPLIT_EPILOGUE) != 0 && d.split_k > 1;
-    if ((d.split_k > 1 && !split_epi) || d.epi.accumulate)
-        TOIST_REQUIRE(d.epi.out_f32, "toist_gemm_bf16: split_k/accumulate needs an f32 output");
-    if (split_epi)
-        TOIST_REQUIRE(d.workspace != nullptr && d.batch == 1 && d.group == nullptr && (d.N % 4) == 0 && !d.epi.cmap && !d.epi.accumulate &&
-                          !(d.flags & TOIST_GEMM_DEFER_REDUCE) && (d.tile & 255) != 131 && !d.a_colsum,
-                      "toist_gemm_bf16: TOIST_GEMM_SPLIT_EPILOGUE needs a workspace, batch = 1, no group / row map / accumulate, N %% 4 == 0");
-    if (d.a_colsum) TOIST_REQUIRE(d.a_kind == TOIST_A_KROW, "toist_gemm_bf16: a_colsum needs a k-major A operand");
-    if (d.flags & TOIST_GEMM_COLSUM_SLICES)
-        TOIST_REQUIRE(d.a_colsum != nullptr && d.group == nullptr && d.batch == 1 && d.split_k > 1 && !split_epi,
-                      "toist_gemm_bf16: TOIST_GEMM_COLSUM_SLICES needs a_colsum, split_k > 1, batch = 1, no group and no split epilogue");
-    if (d.group) TOIST_REQUIRE((d.split_k <= 1 || (d.flags & TOIST_GEMM_DEFER_REDUCE)) && d.batch_inner == 1 && !d.epi.cmap && (d.tile & 255) != 131 &&
-                                   d.a_kind != TOIST_A_CONVT,
-                               "toist_gemm_bf16: a grouped launch takes batch_inner = 1, no cmap, a generic tile, and folds its k-slices through "
-                               "toist_splitk_reduce_batch (TOIST_GEMM_DEFER_REDUCE; workspace = [problem][k-slice][M][N])");
-    if (d.split_k > 1 && !split_epi) {
-        TOIST_REQUIRE(!d.epi.scale && !d.epi.shift && !d.epi.res && d.epi.act == TOIST_ACT_NONE && !d.epi.pre_out && d.epi.drop_where == 0 &&
-                          !d.epi.cmap && (d.batch == 1 || d.group != nullptr),
-                      "toist_gemm_bf16: split_k only supports alpha/rscale/accumulate epilogues on a single batch (or a grouped launch)");
-        TOIST_REQUIRE(d.workspace != nullptr && (d.N % 4) == 0 && (d.ldc % 4) == 0, "toist_gemm_bf16: split_k needs a workspace and N, ldc %% 4 == 0");
-    }
-    if (d.epi.act >= TOIST_ACT_MASK_POS) TOIST_REQUIRE(d.epi.aux != nullptr, "toist_gemm_bf16: activation %d needs aux", d.epi.act);
-    if (d.a2) TOIST_REQUIRE(d.a_kind == TOIST_A_ROWK && aligned16(d.a2) && d.a2_from > 0 && (d.a2_from % 128) == 0 && d.split_k <= 1,
-                            "toist_gemm_bf16: a2 needs a row-major A, 16-byte alignment, a2_from %% 128 == 0 and no split");
-    if (d.epi.drop_where) TOIST_REQUIRE(d.epi.drop_p >= 0.f && d.epi.drop_p < 1.f, "toist_gemm_bf16: bad dropout p");
-
+    const gemm_verdict ok = gemm_check(d);
+    if (ok.code != TOIST_OK) { set_last_error("%s", ok.msg); return ok.code; }
+    const gemm_plan r = gemm_route(d);
+    if (r.code != TOIST_OK) { set_last_error("%s", r.msg); return r.code; }
+    d.batch = r.batch, d.batch_inner = r.batch_inner, d.split_k = r.split;
     hipStream_t st = (hipStream_t)stream;
-    // the 3x3 shared-halo kernel: picked for dgrad (measured 395 vs 351 TFLOP/s on layer 3), explicit tile code 131 otherwise
-    // (forward: 384 vs 451 for the generic tiles)
-    if (d.tile == 136 || (d.tile == 0 && gemm128_pays(d))) {
-        TOIST_REQUIRE(gemm128_applies(d), "toist_gemm_bf16: the 128x128 kernel does not cover this call");
-        const int rc8 = launch_gemm128(d, st);
-        return rc8 != TOIST_OK ? rc8 : check_launch("toist_gemm_bf16(gemm128)");
-    }
-    if ((d.tile == 131 || (d.tile == 0 && d.a_kind == TOIST_A_CONVT)) && conv3_applies(d)) {
-        const int rc3 = launch_conv3(d, st);
-        return rc3 != TOIST_OK ? rc3 : check_launch("toist_gemm_bf16(conv3)");
-    }
-    TOIST_REQUIRE(d.tile != 131, "toist_gemm_bf16: the 3x3 halo kernel does not cover this call");
-    if ((d.tile & 255) == 135 || (d.tile == 0 && (long long)((d.M + 63) / 64) * ((d.N + 63) / 64) >= panel_min_tiles())) {
-        if (panel_applies(d)) {
-            // tile word 135 | variant << 8: variant 1 = the round-2 kernel, otherwise panel2_kernel (see launch_panel2)
-            static const int def_variant = (int)tuning_knob("TOIST_PANEL_VARIANT", 0);
-            const int variant = (d.tile >> 8) ? (d.tile >> 8) : def_variant;
-            const int rcp = (variant == 1 || !panel2_applies(d)) ? launch_panel(d, st) : launch_panel2(d, variant == 255 ? 0 : variant, st);
-            return rcp != TOIST_OK ? rcp : check_launch("toist_gemm_bf16(panel)");
-        }
-        TOIST_REQUIRE((d.tile & 255) != 135, "toist_gemm_bf16: the short-K panel kernel does not cover this call");
-    }
-    int tile = d.tile & 255;
-    const int ring = d.tile >> 8;   // 0 = pick; else slots of the DMA ring (2..4)
-    if (tile == 137) TOIST_REQUIRE(gemm128w_applies(d), "toist_gemm_bf16: the 128x128 weight-gradient kernel does not cover this call");
-    if (tile == 138) TOIST_REQUIRE(gemm256w_applies(d), "toist_gemm_bf16: the 256x128 weight-gradient kernel does not cover this call");
-    if (const int wt = wgrad_tile_replaced(d)) tile = wt;
-    if (tile == 0) tile = auto_tile(d);
-    d.split_k = clamp_split(d.split_k, d.K, tile);
-    if (d.flags & TOIST_GEMM_COLSUM_SLICES)      // the caller sized a_colsum (and its fold) by toist_gemm_effective_split: one row per slice
-        TOIST_REQUIRE(d.split_k > 1, "toist_gemm_bf16: TOIST_GEMM_COLSUM_SLICES with a split that clamps to 1 (see toist_gemm_effective_split)");
-    // tile codes: 64 = 64x64x32, 65 = 64x64x64, 128 = 128x128x32, 129 = 128x128x64, 130 = 128x64x64, 132 = 128x32x64, 133 = 32x128x64
-    const int bkt = (tile == 64 || tile == 128) ? 32 : 64;   // (134 = 64x128x64)
-    if (d.b_kind == TOIST_B_KROW && d.b.kin > 0) TOIST_REQUIRE((d.b.kin % 8) == 0, "toist_gemm_bf16: kin %% 8 != 0");
-    (void)bkt;
+    const char* what = "toist_gemm_bf16";
     int rc;
-    switch (tile) {       // tile families by translation unit
-        case 65: rc = launch_tiles_b(tile, d, ring, st); break;
-        case 130: case 134: rc = launch_tiles_c(tile, d, ring, st); break;
-        case 137: rc = launch_gemm128w(d, st); break;
-        case 138: rc = launch_gemm256w(d, st); break;
-        default: rc = launch_tiles_a(tile, d, ring, st); break;
+    switch (r.family) {
+        case GEMM_128: rc = launch_gemm128(d, st); what = "toist_gemm_bf16(gemm128)"; break;
+        case GEMM_CONV3: rc = launch_conv3(d, st); what = "toist_gemm_bf16(conv3)"; break;
+        case GEMM_PANEL: rc = r.ring == 1 ? launch_panel(d, st) : launch_panel2(d, r.ring, st); what = "toist_gemm_bf16(panel)"; break;
+        case GEMM_128W: rc = launch_gemm128w(d, st); break;
+        case GEMM_256W: rc = launch_gemm256w(d, st); break;
+        default:          // GEMM_TILES: tile families by translation unit
+            rc = r.tile == 65 ? launch_tiles_b(r.tile, d, r.ring, st)
+               : (r.tile == 130 || r.tile == 134) ? launch_tiles_c(r.tile, d, r.ring, st) : launch_tiles_a(r.tile, d, r.ring, st);
+            break;
     }
     if (rc != TOIST_OK) return rc;
-    rc = check_launch("toist_gemm_bf16");
-    if (rc != TOIST_OK || d.split_k <= 1 || (d.flags & TOIST_GEMM_DEFER_REDUCE)) return rc;
-    if (split_epi) {
+    rc = check_launch(what);
+    if (rc != TOIST_OK || r.post == GEMM_POST_NONE || r.post == GEMM_POST_DEFERRED) return rc;
+    if (r.post == GEMM_POST_EPILOGUE) {
         const long long chunks = (long long)d.M * ((d.N + 7) / 8);
         hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, d);
         return check_launch("toist_gemm_bf16(splitk epilogue)");

@@ -245,8 +245,10 @@ def gemm(M, N, K, a_kind, a, b_kind, b, c, ldc, *, batch=1, batch_inner=1, cs_ou
     elif split_k > 1:
         # grouped + split: [problem][k-slice][M][N] partials, one queued fold per problem (group_out = [(c_i, rscale_i)]); else one fold when deferred
         outs = group_out if group is not None else [(c, rscale)] if defer_reduce else ()
-        eff = int(_lib.lib().toist_gemm_effective_split(ctypes.byref(d))) if outs else 0
-        if eff > 1:
+        slice_sums = a_colsum is not None and group is None
+        # the slices the launch will make, asked once: it sizes the fold arena and the per-slice column sums (neither changes the answer)
+        eff = int(_lib.lib().toist_gemm_effective_split(ctypes.byref(d))) if outs or slice_sums else 0
+        if outs and eff > 1:
             ws = FOLDS.acquire(eff * M * N * (batch if group is not None else 1), c.device, [ci for ci, _ in outs])
             d.workspace = _p(ws, torch.float32)
             d.flags |= GEMM_DEFER_REDUCE
@@ -256,17 +258,15 @@ def gemm(M, N, K, a_kind, a, b_kind, b, c, ldc, *, batch=1, batch_inner=1, cs_ou
             d.split_k = 1
         else:
             d.workspace = _p(_workspace(split_k * M * N, c.device), torch.float32)
-    if a_colsum is not None and split_k > 1 and group is None and not split_epilogue:
         # the bias gradient of a split-K weight-gradient GEMM: each k-slice stores its column sums in a row of its own and one fold adds
         # the rows in slice order -- float atomics would add them in whatever order the slices finish, a different sum in every run
-        eff_c = int(_lib.lib().toist_gemm_effective_split(ctypes.byref(d)))
-        if eff_c > 1 and M % 4 == 0 and a_colsum.data_ptr() % 16 == 0:      # (otherwise: one atomic add per slice, as before)
-            cs = torch.empty(eff_c * M, dtype=torch.float32, device=c.device)      # (not the arena: a take may flush / move it under this GEMM)
+        if slice_sums and eff > 1 and M % 4 == 0 and a_colsum.data_ptr() % 16 == 0:      # (otherwise: one atomic add per slice, as before)
+            cs = torch.empty(eff * M, dtype=torch.float32, device=c.device)      # (not the arena: a take may flush / move it under this GEMM)
             d.a_colsum = cs.data_ptr()
             d.flags |= GEMM_COLSUM_SLICES
             # folded on its own right after this GEMM when the GEMM is not deferred, or when a queued fold already adds into the same bias
             # (two folds of one output must not share a launch); the other queued folds stay batched
-            folds.insert(0, dict(ws=cs.data_ptr(), out=a_colsum, splits=eff_c, M=1, N=M, ldc=M, keep=(cs,),
+            folds.insert(0, dict(ws=cs.data_ptr(), out=a_colsum, splits=eff, M=1, N=M, ldc=M, keep=(cs,),
                                  now=not d.flags & GEMM_DEFER_REDUCE, when_busy="now"))
     if DEBUG_WS is not None and split_k <= 1:
         d.workspace = _p(DEBUG_WS, torch.float32)

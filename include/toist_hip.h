@@ -679,6 +679,33 @@ typedef struct toist_reduce_desc {
 TOIST_API int toist_gemm_effective_split(const toist_gemm* desc);
 TOIST_API int toist_splitk_reduce_batch(const toist_reduce_desc* descs, int n, void* stream);
 
+/* ---- two chained 1x1 convolutions of a ResNet stage in one row-local launch (csrc/gemm.hip conv_pair_kernel): conv3 of bottleneck i and
+ * conv1 of bottleneck i + 1 (torchvision Bottleneck as reached through /root/reference/models/backbone.py:75), or their data gradients
+ * in the opposite order.  A workgroup owns 64 rows, finishes and stores them 4C wide, and multiplies the same rows again:
+ *   dgrad = 0:  mid[M][4C] = relu(a[M][C] w_first^T + shift_mid + res),  w_first  bf16 [4C][C];   out[M][C] = relu(mid w_second^T + shift_out),  w_second bf16 [C][4C]
+ *   dgrad = 1:  mid[M][4C] = (a[M][C] w_first + res) where aux_mid > 0,  w_first  bf16 [C][4C];   out[M][C] = (mid w_second) where aux_out > 0,  w_second bf16 [4C][C]
+ * Both results are, bit for bit, what the two toist_gemm_bf16 calls they replace write for the same M (mid is rounded to bf16 before the
+ * second product reads it).  C = 256 only; weights contiguous; every pointer 16-byte aligned, every leading dimension a multiple of 8
+ * and at least the row's width; res is required; aux_mid / aux_out are required with dgrad = 1 and must be NULL with dgrad = 0; shift_mid
+ * [4C] / shift_out [C] f32 are optional with dgrad = 0 and must be NULL with dgrad = 1. */
+typedef struct toist_conv_pair {
+    int32_t M, C;             /* rows; channels of a / out (mid has 4C) */
+    int32_t dgrad;            /* 0 = forward pair, 1 = data-gradient pair */
+    int32_t lda;
+    const void* a;
+    const void* w_first;
+    const void* w_second;
+    const float* shift_mid;
+    const float* shift_out;
+    const void* res;          /* bf16 [M][4C], row stride ldr */
+    const void* aux_mid;      /* bf16 [M][4C], row stride ldaux_mid */
+    const void* aux_out;      /* bf16 [M][C], row stride ldaux_out */
+    void* mid;                /* bf16 [M][4C], row stride ldmid */
+    void* out;                /* bf16 [M][C], row stride ldout */
+    int32_t ldr, ldaux_mid, ldaux_out, ldmid, ldout, reserved;
+} toist_conv_pair;            /* 120 bytes */
+TOIST_API int toist_conv_pair_bf16(const toist_conv_pair* desc, void* stream);
+
 TOIST_API int toist_opt_chunk_elems(void);
 TOIST_API int toist_opt_sqnorm(const toist_opt_tensor* table, const int64_t* grads, const int32_t* chunks, int n_chunks, float* partial, void* stream);
 TOIST_API int toist_opt_finish_norm(const float* partial, int n_chunks, float max_norm, float beta1, float beta2, toist_opt_state* state, void* stream);

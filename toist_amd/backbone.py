@@ -203,6 +203,7 @@ class BackboneBase(nn.Module):
             outs = []
             for li in range(first, last + 1):
                 layer = getattr(body, f"layer{li}")
+                take = None       # hand-over from the previous block (engine.pair_link)
                 for bi, blk in enumerate(layer):
                     pre = f"layer{li}.{bi}."
                     Wd = {"conv1": ps[pre + "conv1.weight"], "conv2": ps[pre + "conv2.weight"], "conv3": ps[pre + "conv3.weight"]}
@@ -212,7 +213,18 @@ class BackboneBase(nn.Module):
                         Wd["down"] = ps[pre + "downsample.0.weight"]
                         bnd["down"] = bn(pre + "downsample.1")
                     train = Wd["conv1"].g is not None
-                    nxt = engine.bottleneck(tape, cur, Wd, bnd, blk.stride, has_down, train)
+                    # layer 3 (256 / 1024 channels): conv3 of this block and conv1 of the next run as one launch, forward and data gradient
+                    # (kernels.conv_pair).  A block's output inside the layer is read by the next block alone; the layer's last output (a
+                    # level, or the next stage's input -- where stage_cuts cut) is never part of a pair.
+                    give = None
+                    if k.CONV_PAIR and li == 3 and bi + 1 < len(layer):
+                        nb = layer[bi + 1]
+                        if nb.stride == 1 and nb.downsample is None and tuple(nb.conv1.weight.shape[:2]) == (256, 1024) \
+                                and tuple(blk.conv3.weight.shape[:2]) == (1024, 256):
+                            npre = f"layer{li}.{bi + 1}."
+                            give = engine.pair_link(ps[npre + "conv1.weight"], bn(npre + "bn1")[1])
+                    nxt = engine.bottleneck(tape, cur, Wd, bnd, blk.stride, has_down, train, take=take, give=give)
+                    take = give
                     nxt.needs_grad = train
                     cur = nxt
                 if li in levels:
@@ -267,6 +279,8 @@ class BackboneBase(nn.Module):
         tr_all = self._transforms()
         caches = self.__dict__.setdefault("_stage_caches", [{} for _ in self.STAGES])
         x = images
+        # stages are whole layers, so a cut never separates two blocks of layer 3 that share a pair launch (_program)
+        assert sum(first <= 3 <= last for first, last, _ in self.STAGES) == 1
         for si, (first, last, stem) in enumerate(self.STAGES):
             def build(first=first, last=last, stem=stem):
                 keep = tuple(f"layer{li}." for li in range(first, last + 1)) + (("conv1.",) if stem else ())

@@ -2652,6 +2652,311 @@ static int launch_gemm128(const toist_gemm& d, hipStream_t st) {
     return (ring == 5 && d.K >= 5 * G8_BK) ? launch_gemm128_ring<5>(d, st) : launch_gemm128_ring<4>(d, st);
 }
 
+// ---- conv_pair_kernel: two chained 1x1 convolutions of a ResNet stage, row-local (toist_conv_pair_bf16) -----------------------------------
+// conv3 of bottleneck i and conv1 of bottleneck i + 1 (DG = false), or the data gradients of conv1 and of the previous block's conv3 (DG = true):
+//   mid[M][1024] = epilogue1(a[M][256] x W_first),  out[M][256] = epilogue2(bf16(mid) x W_second).
+// One workgroup of 8 waves owns 64 rows and needs nobody else's: the 64 x 256 input block stays in LDS, and for each of the eight 128-column
+// chunks of mid it (1) multiplies the block by that chunk of the first weight (K = 256, two steps), (2) finishes the chunk -- global store plus
+// a bf16 copy in LDS -- and (3) adds the chunk's 128-deep k-slice to the 64 x 256 output accumulators (two steps).  The weights stream through a
+// three-stage LDS-DMA ring, 32 KiB (two 128 x 64 tiles) per step, prefetched two steps ahead; the 64 x 1024 block of mid is never held.
+// Waves: phase 1 as 2 x 4 wave tiles of 32 x 32 with panel2_kernel's column order (a lane ends up with 8 consecutive columns of a row = one
+// 16-byte chunk for the store and for the LDS copy); phase 2 as 8 wave tiles of 64 rows x 32 columns over the whole k-slice.
+// Rounding: phase 1 sums each element over the 8 k-steps of 32 in ascending order from zero (panel2_kernel and the generic tiles).  Phase 2
+// sums ascending k-steps into ONE accumulator (the generic tiles) or, SPLIT, the even and the odd k-steps into two that are added once at the end
+// (gemm128_kernel's two k-halves of every 64-deep k-tile): the host picks what gemm_route() says the replaced call would run on.  Epilogues are
+// those kernels' expressions.  vmcnt: a wave's memory operations retire in issue order and hipcc sees none of them inside the loop (DMA,
+// residual / mask loads and stores are inline asm), so every wait is the exact number of operations issued after the one it needs; per chunk
+// the order is I(s+2) R | I(s+3) S | I(s+4) | I(s+5) with I = the 4 DMA pieces of a step, R = NR residual / mask loads, S = 2 stores.
+// 16 / 8 bytes of every lane from (descriptor base + byte offset) into registers; an offset >= num_records reads zeros.  hipcc does not see
+// these loads: the consumer names the registers in a counted s_waitcnt before their first use.
+__device__ __forceinline__ u32x4_t load16_asm(const i32x4_t& r, const int byte_off) {
+    u32x4_t v;
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(v) : "v"(byte_off), "s"(r) : "memory");
+    return v;
+}
+__device__ __forceinline__ u32x2_t load8_asm(const i32x4_t& r, const int byte_off) {
+    u32x2_t v;
+    asm volatile("buffer_load_dwordx2 %0, %1, %2, 0 offen" : "=&v"(v) : "v"(byte_off), "s"(r) : "memory");
+    return v;
+}
+
+constexpr int CP_TILE_BYTES = 128 * 64 * 2;                  // one weight tile: 128 rows x 64 k (k-contiguous) or 64 k x 128 columns (k-major)
+constexpr int CP_STEP_BYTES = 2 * CP_TILE_BYTES;
+constexpr int CP_NS = 3;                                     // ring stages
+constexpr int CP_STEPS = 32;                                 // 8 chunks x (2 + 2)
+constexpr int CP_A_OFF = 0;                                  // [4 k-tiles][64][64] input block
+constexpr int CP_MID_OFF = CP_A_OFF + CP_BM * CP_C * 2;      // [2 k-tiles][64][64] finished chunk of mid
+constexpr int CP_RING_OFF = CP_MID_OFF + CP_BM * 128 * 2;
+constexpr int CP_SHIFT_OFF = CP_RING_OFF + CP_NS * CP_STEP_BYTES;   // f32 [1024 + 256]
+constexpr int CP_LDS = CP_SHIFT_OFF + 5 * CP_C * 4;
+static_assert(CP_LDS <= 160 * 1024, "conv_pair_kernel: LDS");
+
+template <bool DG, bool SPLIT>
+__global__ __launch_bounds__(512, 2) void conv_pair_kernel(const toist_conv_pair p, const float alpha) {
+    constexpr int BK = 64, KT = BK * CP_BM;                  // elements of one 64 x 64 k-tile of the input block / of mid
+    constexpr int C = CP_C, C4 = 4 * CP_C;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    bf16_t* const smem = reinterpret_cast<bf16_t*>(lds_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, c16 = lane & 15;
+    const int wm1 = wave >> 2, wn1 = wave & 3;               // phase 1: 32-row half, 32-column quarter of the chunk
+    const int M = p.M;
+    const int nt = (M + CP_BM - 1) / CP_BM, per = (nt + 7) >> 3;
+    // consecutive row blocks on one XCD (workgroups go round the 8 XCDs): the 1 MB of weights is served by every XCD's L2
+    const int tile_m = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    if (tile_m >= nt) return;
+    const int m0 = tile_m * CP_BM;
+    const unsigned lds0 = (unsigned)(size_t)lds_raw;
+    const unsigned ring0 = lds0 + CP_RING_OFF;
+
+    float* const sh = reinterpret_cast<float*>(lds_raw + CP_SHIFT_OFF);
+    sh[tid] = (!DG && p.shift_mid) ? p.shift_mid[tid] : 0.f;
+    sh[tid + 512] = (!DG && p.shift_mid) ? p.shift_mid[tid + 512] : 0.f;
+    if (tid < C) sh[C4 + tid] = (!DG && p.shift_out) ? p.shift_out[tid] : 0.f;
+
+    const i32x4_t rsA = make_rsrc(p.a), rsW1 = make_rsrc(p.w_first), rsW2 = make_rsrc(p.w_second), rsMid = make_rsrc(p.mid);
+    const i32x4_t rsR = make_rsrc(p.res), rsXm = make_rsrc(DG ? p.aux_mid : p.res), rsXo = make_rsrc(DG ? p.aux_out : p.res);
+    constexpr int NR = DG ? 4 : 2;                           // residual (+ mask) loads of a wave per chunk
+    auto pcol = [](const int j, const int q) { return 8 * (q >> 2) + 4 * j + (q & 3); };     // panel2_kernel's fragment column order
+
+    // ---- lane offsets (bytes) of the DMA pieces; the step's tile travels in the scalar offset ----
+    int v1[2], v2[2];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int pch = (it * 8 + wave) * 64 + lane;         // 16-byte chunk of a tile, lane linear
+        if (DG) {                                            // k-major [64 k][128 columns]
+            const int krow = pch >> 4, rc = swz_m<128>(krow, pch & 15);
+            v1[it] = (krow * C4 + rc * 8) * 2;               // W1 [256][1024]
+            v2[it] = (krow * C + rc * 8) * 2;                // W3 [1024][256]
+        } else {                                             // k-contiguous [128 rows][64 k]
+            const int row = pch >> 3, kc = swz_k<BK>(row, pch & 7);
+            const int prow = (row & ~31) + pcol((row >> 4) & 1, row & 15);      // phase 1: fragment j of a 32-row group holds its rows in pcol order
+            v1[it] = (prow * C + kc * 8) * 2;                // W3 [1024][256]
+            v2[it] = (row * C4 + kc * 8) * 2;                // W1 [256][1024]
+        }
+    }
+    auto issue = [&](const int s, const int slot) {
+        const int c = s >> 2, q = s & 3;
+        const unsigned dst = ring0 + (unsigned)(slot * CP_STEP_BYTES) + (unsigned)wave * 1024u;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const unsigned d0 = dst + (unsigned)(tt * CP_TILE_BYTES);
+            if (q < 2) {                                     // first weight: mid columns [128 c, +128), k-tile 2 q + tt
+                const int so = DG ? ((2 * q + tt) * BK * C4 + 128 * c) * 2 : (128 * c * C + (2 * q + tt) * BK) * 2;
+                dma16s(d0, rsW1, v1[0], so);
+                dma16s(d0 + 8192u, rsW1, v1[1], so);
+            } else {                                         // second weight: k-tile 128 c + 64 (q - 2), output columns [128 tt, +128)
+                const int k0 = 128 * c + BK * (q - 2);
+                const int so = DG ? (k0 * C + 128 * tt) * 2 : (128 * tt * C4 + k0) * 2;
+                dma16s(d0, rsW2, v2[0], so);
+                dma16s(d0 + 8192u, rsW2, v2[1], so);
+            }
+        }
+    };
+
+    // the prologue's own loads (shifts) end here: from now on the wave's counter holds what `issue`, the residual loads and the stores put there
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    {
+        const int pa = wave * 64 + lane, ar = pa >> 3, akc = swz_k<BK>(ar, pa & 7);
+        const int va = (m0 + ar < M) ? ((m0 + ar) * p.lda + akc * 8) * 2 : OOB;       // rows beyond M read as zeros
+#pragma unroll
+        for (int it = 0; it < 4; ++it) dma16s(lds0 + (unsigned)(CP_A_OFF + it * KT * 2) + (unsigned)wave * 1024u, rsA, va, it * BK * 2);
+    }
+    issue(0, 0);
+    issue(1, 1);
+
+    f32x4_t acc1[2][2];
+    f32x4_t acc2[SPLIT ? 2 : 1][4][2];
+#pragma unroll
+    for (int h = 0; h < (SPLIT ? 2 : 1); ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc2[h][i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    u32x4_t rres[2], raux[2];
+    const u32x4_t zero4 = {0u, 0u, 0u, 0u};
+    rres[0] = rres[1] = raux[0] = raux[1] = zero4;
+
+    int slot = 0;
+    u32x2_t xo[4][2];                                        // DG: the output's mask rows, requested before the last two steps
+    // top of step s = 4 c + q: its two tiles have landed for every wave, everyone is done with the stage step s - 1 read; then refill that stage
+    auto step_top = [&](const int s, auto qc) {
+        constexpr int q = decltype(qc)::value;
+        if (q == 3 && s + 1 == CP_STEPS) wait_vm<(DG ? 10 : 2)>();      // the last step: the chunk's 2 stores (and the 8 mask loads) are younger
+        else wait_vm<(q == 0 ? 4 : q == 1 ? 4 + NR : q == 2 ? NR + 6 : 6)>();
+        lds_barrier();
+    };
+    auto refill = [&](const int s) {
+        if (s + 2 < CP_STEPS) issue(s + 2, slot >= 1 ? slot - 1 : CP_NS - 1);      // (slot + 2) % 3
+    };
+    auto next_slot = [&]() { slot = slot == CP_NS - 1 ? 0 : slot + 1; };
+
+#pragma unroll 1
+    for (int c = 0; c < 8; ++c) {
+        const int ncol = 128 * c + wn1 * 32 + g * 8;        // first of this lane's 8 columns of mid
+        // ---- phase 1: chunk c of mid, k-tiles 2 u, 2 u + 1 per step ----
+        static_for<2>([&](auto uc) {
+            constexpr int u = decltype(uc)::value;
+            const int s = c * 4 + u;
+            step_top(s, uc);
+            refill(s);
+            if (u == 0) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc1[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                    const int m = m0 + wm1 * 32 + i * 16 + c16;      // rows beyond M read as zeros
+                    rres[i] = load16_asm(rsR, m < M ? (m * p.ldr + ncol) * 2 : OOB);
+                    if (DG) raux[i] = load16_asm(rsXm, m < M ? (m * p.ldaux_mid + ncol) * 2 : OOB);
+                }
+            }
+            const unsigned char* const sB = lds_raw + CP_RING_OFF + slot * CP_STEP_BYTES;
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                const bf16_t* const sA = smem + CP_A_OFF / 2 + (2 * u + tt) * KT;
+                const bf16_t* const sBt = reinterpret_cast<const bf16_t*>(sB + tt * CP_TILE_BYTES);
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    bf16x8_t af[2], bfr[2];
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) af[i] = fragment<false, CP_BM, BK>(sA, wm1 * 32 + i * 16, ks, g, c16);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        bfr[j] = DG ? fragment_perm8<128, BK>(sBt, wn1 * 32, j, ks, g, c16) : fragment<false, 128, BK>(sBt, wn1 * 32 + j * 16, ks, g, c16);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc1[i][j], 0, 0, 0);
+                }
+            }
+            next_slot();
+        });
+        // ---- the chunk's epilogue (panel2_kernel's): global store + the bf16 copy phase 2 reads ----
+        {
+            // the residual / mask rows requested a step ago: only this step's refill (4 pieces) is younger
+            if (DG) asm volatile("s_waitcnt vmcnt(4)" : "+v"(rres[0]), "+v"(rres[1]), "+v"(raux[0]), "+v"(raux[1]) : : "memory");
+            else asm volatile("s_waitcnt vmcnt(4)" : "+v"(rres[0]), "+v"(rres[1]) : : "memory");
+            float csh[8];
+            const f32x4_t s0 = *reinterpret_cast<const f32x4_t*>(sh + ncol), s1 = *reinterpret_cast<const f32x4_t*>(sh + ncol + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { csh[e] = s0[e]; csh[4 + e] = s1[e]; }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int r = wm1 * 32 + i * 16 + c16, m = m0 + r;
+                float v[8];
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[jj * 4 + e] = acc1[i][jj][e] * alpha + csh[jj * 4 + e];
+                add8(v, rres[i]);
+                if (DG) {
+                    const u32x4_t x4 = raux[i];
+                    v[0] = __uint_as_float(x4[0] << 16) > 0.f ? v[0] : 0.f; v[1] = __uint_as_float(x4[0] & 0xffff0000u) > 0.f ? v[1] : 0.f;
+                    v[2] = __uint_as_float(x4[1] << 16) > 0.f ? v[2] : 0.f; v[3] = __uint_as_float(x4[1] & 0xffff0000u) > 0.f ? v[3] : 0.f;
+                    v[4] = __uint_as_float(x4[2] << 16) > 0.f ? v[4] : 0.f; v[5] = __uint_as_float(x4[2] & 0xffff0000u) > 0.f ? v[5] : 0.f;
+                    v[6] = __uint_as_float(x4[3] << 16) > 0.f ? v[6] : 0.f; v[7] = __uint_as_float(x4[3] & 0xffff0000u) > 0.f ? v[7] : 0.f;
+                }
+                u32x4_t o = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+                if (!DG) {                                   // ReLU on the packed pairs (see panel2_kernel)
+                    unsigned r0, r1, r2, r3;
+                    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r0) : "v"(o[0]));
+                    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r1) : "v"(o[1]));
+                    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r2) : "v"(o[2]));
+                    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r3) : "v"(o[3]));
+                    o[0] = r0; o[1] = r1; o[2] = r2; o[3] = r3;
+                }
+                const int cb = wn1 * 32 + g * 8;             // column inside the chunk: k-tile cb >> 6, 16-byte chunk (cb & 63) >> 3 of its row
+                *reinterpret_cast<u32x4_t*>(lds_raw + CP_MID_OFF + (cb >> 6) * KT * 2 + (r * BK + swz_k<BK>(r, (cb & 63) >> 3) * 8) * 2) = o;
+                store16_asm(rsMid, m < M ? (m * p.ldmid + ncol) * 2 : OOB, o);
+            }
+        }
+        // ---- phase 2: the chunk's two 64-deep k-tiles into the output accumulators ----
+        static_for<2>([&](auto ktc) {
+            constexpr int kt = decltype(ktc)::value;
+            const int s = c * 4 + 2 + kt;
+            step_top(s, std::integral_constant<int, 2 + kt>{});      // (its barrier also publishes the LDS copy of the chunk)
+            refill(s);
+            if (DG && s == CP_STEPS - 2) {                   // nothing is refilled any more: the output's mask rows fly under the last two steps
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int m = m0 + i * 16 + c16;
+                        xo[i][j] = load8_asm(rsXo, m < M ? (m * p.ldaux_out + wave * 32 + j * 16 + g * 4) * 2 : OOB);
+                    }
+            }
+            const bf16_t* const sM = smem + CP_MID_OFF / 2 + kt * KT;
+            const bf16_t* const sBh = reinterpret_cast<const bf16_t*>(lds_raw + CP_RING_OFF + slot * CP_STEP_BYTES + (wave >> 2) * CP_TILE_BYTES);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                bf16x8_t af[4], bfr[2];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) af[i] = fragment<false, CP_BM, BK>(sM, i * 16, ks, g, c16);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bfr[j] = fragment<DG, 128, BK>(sBh, (wave & 3) * 32 + j * 16, ks, g, c16);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc2[SPLIT ? ks : 0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc2[SPLIT ? ks : 0][i][j], 0, 0, 0);
+            }
+            next_slot();
+        });
+    }
+    if (DG) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("s_waitcnt vmcnt(0)" : "+v"(xo[i][0]), "+v"(xo[i][1]) : : "memory");
+    } else {
+        wait_vm<0>();
+    }
+
+    // ---- output epilogue (gemm128_kernel's / the generic tiles' expressions): a lane holds 4 consecutive columns of 4 x 2 rows ----
+    bf16_t* const outp = (bf16_t*)p.out;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int m = m0 + i * 16 + c16;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = wave * 32 + j * 16 + g * 4;
+            f32x4_t a = acc2[0][i][j];
+            if (SPLIT) a = a + acc2[SPLIT ? 1 : 0][i][j];
+            const f32x4_t sv = *reinterpret_cast<const f32x4_t*>(sh + C4 + col);
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = a[e] * alpha + sv[e];
+            if (m < M) {
+                if (DG) {
+                    const u32x2_t x2 = xo[i][j];
+                    v[0] = __uint_as_float(x2[0] << 16) > 0.f ? v[0] : 0.f; v[1] = __uint_as_float(x2[0] & 0xffff0000u) > 0.f ? v[1] : 0.f;
+                    v[2] = __uint_as_float(x2[1] << 16) > 0.f ? v[2] : 0.f; v[3] = __uint_as_float(x2[1] & 0xffff0000u) > 0.f ? v[3] : 0.f;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                }
+                *reinterpret_cast<uint2*>(outp + (size_t)m * p.ldout + col) = make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
+            }
+        }
+    }
+}
+
+static int launch_conv_pair(const toist_conv_pair& d, const bool split, hipStream_t st) {
+    const int nt = (d.M + CP_BM - 1) / CP_BM, per = (nt + 7) / 8;
+    const dim3 grid(8u * (unsigned)per, 1, 1);
+#define TOIST_CONV_PAIR(DG, SP)                                                                                                            \
+    do {                                                                                                                                   \
+        static std::atomic<unsigned long long> done{0};                                                                                    \
+        if (!lds_attr_once_flag(done, [] { return hipFuncSetAttribute((const void*)conv_pair_kernel<DG, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS) == hipSuccess; })) { \
+            set_last_error("toist_conv_pair_bf16: cannot enable %d bytes of LDS", CP_LDS);                                                 \
+            return TOIST_EHIP;                                                                                                             \
+        }                                                                                                                                  \
+        hipLaunchKernelGGL((conv_pair_kernel<DG, SP>), grid, dim3(512), CP_LDS, st, d, 1.f);                                               \
+    } while (0)
+    if (d.dgrad) { if (split) TOIST_CONV_PAIR(true, true); else TOIST_CONV_PAIR(true, false); }
+    else { if (split) TOIST_CONV_PAIR(false, true); else TOIST_CONV_PAIR(false, false); }
+#undef TOIST_CONV_PAIR
+    return TOIST_OK;
+}
+
 static int launch_gemm256w(const toist_gemm& d, hipStream_t st) {
     static std::atomic<unsigned long long> done{0};
     if (!lds_attr_once_flag(done, [] {
@@ -3078,5 +3383,17 @@ extern "C" int toist_gemm_bf16(const toist_gemm* desc, void* stream) {
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, st, (const float*)d.workspace, d.split_k, d.M, d.N, d.epi.alpha,
                        d.epi.rscale, d.epi.accumulate, (float*)d.c, d.ldc);
     return check_launch("toist_gemm_bf16(splitk reduce)");
+}
+
+extern "C" int toist_conv_pair_bf16(const toist_conv_pair* desc, void* stream) {
+    using namespace toist;
+    TOIST_REQUIRE(desc != nullptr, "toist_conv_pair_bf16: null descriptor");
+    const toist_conv_pair d = *desc;
+    const gemm_verdict ok = pair_check(d);
+    if (ok.code != TOIST_OK) { set_last_error("%s", ok.msg); return ok.code; }
+    // the second product rounds like the toist_gemm_bf16 call it replaces: two accumulators per element where that call runs on gemm128_kernel
+    const bool split = gemm_route(pair_second_gemm(d)).family == GEMM_128;
+    const int rc = launch_conv_pair(d, split, (hipStream_t)stream);
+    return rc != TOIST_OK ? rc : check_launch("toist_conv_pair_bf16");
 }
 #endif  // GEMM_UNIT (main unit)

@@ -337,6 +337,54 @@ gemm_plan gemm_route(const toist_gemm& desc) {
     return r;
 }
 
+// ---- toist_conv_pair_bf16 ----
+gemm_verdict pair_check(const toist_conv_pair& d) {
+    gemm_verdict v{};
+    const long long lim = 1ll << 30;      // byte offsets of the DMA / buffer-store path stay below 2 GiB
+    GEMM_REQUIRE(v, d.M > 0 && d.C == CP_C, "toist_conv_pair_bf16: bad shape M=%d C=%d (C = %d only)", d.M, d.C, CP_C);
+    GEMM_REQUIRE(v, d.dgrad == 0 || d.dgrad == 1, "toist_conv_pair_bf16: dgrad = %d (0 or 1)", d.dgrad);
+    GEMM_REQUIRE(v, d.a && d.w_first && d.w_second && d.mid && d.out, "toist_conv_pair_bf16: null operand");
+    GEMM_REQUIRE(v, d.res != nullptr, "toist_conv_pair_bf16: res is required");
+    if (d.dgrad) {
+        GEMM_REQUIRE(v, d.aux_mid && d.aux_out, "toist_conv_pair_bf16: the data gradient needs aux_mid and aux_out");
+        GEMM_REQUIRE(v, !d.shift_mid && !d.shift_out, "toist_conv_pair_bf16: the data gradient takes no shift");
+    } else {
+        GEMM_REQUIRE(v, !d.aux_mid && !d.aux_out, "toist_conv_pair_bf16: aux_mid / aux_out belong to the data gradient (dgrad = 1)");
+    }
+    GEMM_REQUIRE(v, aligned16(d.a) && aligned16(d.w_first) && aligned16(d.w_second) && aligned16(d.res) && aligned16(d.mid) && aligned16(d.out) &&
+                        aligned16(d.aux_mid) && aligned16(d.aux_out) && aligned16(d.shift_mid) && aligned16(d.shift_out),
+                 "toist_conv_pair_bf16: every pointer must be 16-byte aligned");
+    const int C = CP_C, C4 = 4 * CP_C;
+    GEMM_REQUIRE(v, d.lda >= C && d.ldout >= C && d.ldmid >= C4 && d.ldr >= C4 && (d.lda % 8) == 0 && (d.ldout % 8) == 0 && (d.ldmid % 8) == 0 && (d.ldr % 8) == 0,
+                 "toist_conv_pair_bf16: leading dimensions must cover the row and be multiples of 8 (lda=%d ldmid=%d ldr=%d ldout=%d)", d.lda, d.ldmid,
+                 d.ldr, d.ldout);
+    if (d.dgrad)
+        GEMM_REQUIRE(v, d.ldaux_mid >= C4 && d.ldaux_out >= C && (d.ldaux_mid % 8) == 0 && (d.ldaux_out % 8) == 0,
+                     "toist_conv_pair_bf16: leading dimensions must cover the row and be multiples of 8 (ldaux_mid=%d ldaux_out=%d)", d.ldaux_mid, d.ldaux_out);
+    const long long rows = (long long)((d.M + CP_BM - 1) / CP_BM) * CP_BM;
+    GEMM_REQUIRE(v, rows * d.lda < lim && rows * d.ldmid < lim && rows * d.ldr < lim && rows * d.ldout < lim &&
+                        (!d.dgrad || (rows * d.ldaux_mid < lim && rows * d.ldaux_out < lim)),
+                 "toist_conv_pair_bf16: M = %d rows exceed the 2 GiB byte offsets of the kernel", d.M);
+    return v;
+}
+
+bool pair_applies(const toist_conv_pair& desc) { return pair_check(desc).code == TOIST_OK; }
+
+toist_gemm pair_second_gemm(const toist_conv_pair& p) {
+    toist_gemm d{};
+    d.M = p.M, d.N = p.C, d.K = 4 * p.C;
+    d.a_kind = TOIST_A_ROWK, d.b_kind = p.dgrad ? TOIST_B_KROW : TOIST_B_ROWK;
+    d.a.ptr = p.mid, d.a.ld = p.ldmid;
+    d.b.ptr = p.w_second, d.b.ld = p.dgrad ? p.C : 4 * p.C;
+    d.c = p.out, d.ldc = p.ldout;
+    d.batch = d.batch_inner = d.split_k = 1;
+    d.epi.alpha = 1.f;
+    d.epi.shift = p.shift_out;
+    d.epi.act = p.dgrad ? TOIST_ACT_MASK_POS : TOIST_ACT_RELU;
+    d.epi.aux = p.aux_out, d.epi.ldaux = p.dgrad ? p.ldaux_out : 0;
+    return d;
+}
+
 }  // namespace toist
 
 extern "C" int toist_gemm_pick_tile(const toist_gemm* desc) { return desc == nullptr ? 0 : toist::gemm_route(*desc).tile; }

@@ -50,4 +50,13 @@ gemm_plan gemm_route(const toist_gemm& desc);
 // what epilogue_lean covers: launch_variant and launch_conv3 pick their instantiation by it
 bool lean_epilogue_ok(const toist_gemm& d);
 
+// conv_pair_kernel (toist_conv_pair_bf16): 64-row blocks, C = 256 channels with a 4C-wide intermediate
+constexpr int CP_BM = 64, CP_C = 256;
+// the preconditions of toist_conv_pair_bf16, first failure first
+gemm_verdict pair_check(const toist_conv_pair& desc);
+bool pair_applies(const toist_conv_pair& desc);
+// the toist_gemm_bf16 call the pair's second product replaces: conv_pair_kernel sums the two 32-deep halves of every 64-deep k-tile apart
+// exactly when that call would run on gemm128_kernel (gemm_route()), so both paths round alike at every M
+toist_gemm pair_second_gemm(const toist_conv_pair& desc);
+
 }  // namespace toist

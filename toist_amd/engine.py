@@ -915,16 +915,33 @@ def text_attention_block(tape, x, proj, Wpacked, Wo, bo, key_pad, B, L, H):
 
 
 # ------------------------------------------------------------------------------------------ ResNet blocks
-def bottleneck(tape, x, W, bn, stride, has_down, train):
+def pair_link(w1_next, t1_next):
+    """Hand-over between bottleneck i (`give`) and bottleneck i + 1 (`take`) of a stage whose conv3 / next conv1 run as one launch
+    (kernels.conv_pair): the next block's conv1 weight view and shift go in; the forward leaves a1 of block i + 1 (and, training,
+    block i's w3 / a2) in it, the backward of block i + 1 leaves (g3, g2) of block i.  Only for a block output that block i + 1 alone
+    consumes: nothing else may add into that gradient slot."""
+    return {"w1": w1_next, "t1": t1_next}
+
+
+def _pair_shapes_ok(a2, w3, w1n, idn):
+    C = a2.shape[-1]
+    return C == 256 and tuple(w3.shape) == (4 * C, 1, 1, C) and tuple(w1n.shape) == (C, 1, 1, 4 * C) and idn.is_contiguous() \
+        and tuple(idn.shape) == (*a2.shape[:3], 4 * C) and a2.is_contiguous()
+
+
+def bottleneck(tape, x, W, bn, stride, has_down, train, take=None, give=None):
     """torchvision Bottleneck (v1.5) on NHWC bf16 with FrozenBatchNorm folded: conv weights `W[name].w`
     are already multiplied by the BN scale, `bn[name]` = (scale, shift) fp32.  The gradient this block
     leaves in x.grad is already masked by (x > 0), i.e. it is the gradient w.r.t. the pre-ReLU sum of
-    the producing block (every block input is a ReLU output)."""
+    the producing block (every block input is a ReLU output).
+    take / give: pair_link() with the previous / the next block of the stage (None = the per-op calls)."""
     w1, w2, w3 = krsc(W["conv1"].w), krsc(W["conv2"].w), krsc(W["conv3"].w)
     s1, t1 = bn["bn1"]
     s2, t2 = bn["bn2"]
     s3, t3 = bn["bn3"]
-    a1 = ops.conv2d(x.data, w1, shift=t1, act=k.ACT_RELU)
+    a1 = take.pop("a1", None) if take is not None else None      # the previous block's pair launch already ran this block's conv1
+    if a1 is None:
+        a1 = ops.conv2d(x.data, w1, shift=t1, act=k.ACT_RELU)
     a2 = ops.conv2d(a1, w2, stride=stride, pad=1, shift=t2, act=k.ACT_RELU)
     if has_down:
         wd = krsc(W["down"].w)
@@ -932,7 +949,18 @@ def bottleneck(tape, x, W, bn, stride, has_down, train):
         idn = ops.conv2d(x.data, wd, stride=stride, shift=td)
     else:
         idn = x.data
-    y = ops.conv2d(a2, w3, shift=t3, res=idn, act=k.ACT_RELU)
+    w1n = krsc(give["w1"].w) if give is not None else None
+    if give is not None and (k.CONV_PAIR & 1) and _pair_shapes_ok(a2, w3, w1n, idn):
+        C, M = a2.shape[-1], a2.numel() // a2.shape[-1]
+        y = torch.empty(*a2.shape[:3], 4 * C, dtype=BF16, device=a2.device)
+        a1n = torch.empty_like(a2)
+        k.conv_pair(a2.view(M, C), w3.view(4 * C, C), w1n.view(C, 4 * C), idn.view(M, 4 * C), y.view(M, 4 * C), a1n.view(M, C),
+                    shift_mid=t3, shift_out=give["t1"])
+        give["a1"] = a1n
+    else:
+        y = ops.conv2d(a2, w3, shift=t3, res=idn, act=k.ACT_RELU)
+    if give is not None and train and (k.CONV_PAIR & 2) and _pair_shapes_ok(a2, w3, w1n, y):
+        give["w3"], give["a2"] = w3, a2          # the next block's backward runs this block's conv3 data gradient
     if has_down:
         del idn
     out = Var(y)
@@ -942,10 +970,14 @@ def bottleneck(tape, x, W, bn, stride, has_down, train):
 
     def bwd():
         g3 = out.take_grad()  # w.r.t. the pre-ReLU sum (masked by the consumer)
+        stash = give.pop("g", None) if give is not None else None
         if g3 is None:
             return
         tape.conv_wgrad(g3, a2, w3.shape, krsc(W["conv3"].g), s3, view=W["conv3"])
-        g2 = ops.conv2d_dgrad(g3, w3, a2.shape[1:3], act=k.ACT_MASK_POS, aux=a2)
+        if stash is not None and stash[0] is g3:
+            g2 = stash[1]          # the next block's pair launch already ran this block's conv3 data gradient on exactly this g3
+        else:
+            g2 = ops.conv2d_dgrad(g3, w3, a2.shape[1:3], act=k.ACT_MASK_POS, aux=a2)
         tape.conv_wgrad(g2, a1, w2.shape, krsc(W["conv2"].g), s2, stride=stride, pad=1, view=W["conv2"])
         g1 = ops.conv2d_dgrad(g2, w2, (H, Wd), stride=stride, pad=1, act=k.ACT_MASK_POS, aux=a1)
         tape.conv_wgrad(g1, x.data, w1.shape, krsc(W["conv1"].g), s1, view=W["conv1"])
@@ -954,6 +986,16 @@ def bottleneck(tape, x, W, bn, stride, has_down, train):
         if not x.needs_grad:
             return
         prev = x.take_grad()
+        if take is not None and "a2" in take and not has_down and prev is None and stride == 1 and g3.is_contiguous():
+            # plain case: this block's conv1 data gradient (residual = g3, mask x > 0) and the previous block's conv3 data gradient
+            C, M = g1.shape[-1], g1.numel() // g1.shape[-1]
+            pa2 = take.pop("a2")
+            gx, g2p = torch.empty_like(x.data), torch.empty_like(pa2)
+            k.conv_pair(g1.view(M, C), w1.view(C, 4 * C), take.pop("w3").view(4 * C, C), g3.view(M, 4 * C), gx.view(M, 4 * C), g2p.view(M, C),
+                        dgrad=True, aux_mid=x.data.view(M, 4 * C), aux_out=pa2.view(M, C))
+            x.grad = gx
+            take["g"] = (gx, g2p)
+            return
         if has_down:
             if stride == 1:
                 gx = ops.conv2d_dgrad(g3, wd, (H, Wd), res=prev)

@@ -298,6 +298,43 @@ def gemm(M, N, K, a_kind, a, b_kind, b, c, ldc, *, batch=1, batch_inner=1, cs_ou
     prof["records"].append((*events, flops, key, (M, N, K, nb, split_k, ta * tb), nbytes))
 
 
+class ConvPair(ctypes.Structure):
+    """toist_conv_pair (include/toist_hip.h); tests/test_cpu_conv_pair_check.py holds every field against the C compiler"""
+    _fields_ = [("M", ctypes.c_int32), ("C", ctypes.c_int32), ("dgrad", ctypes.c_int32), ("lda", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("a", "w_first", "w_second", "shift_mid", "shift_out", "res", "aux_mid", "aux_out", "mid", "out")] + \
+               [(n, ctypes.c_int32) for n in ("ldr", "ldaux_mid", "ldaux_out", "ldmid", "ldout", "reserved")]
+
+
+# conv3 of a layer-3 bottleneck and conv1 of the next one in one launch (csrc/gemm.hip conv_pair_kernel): bit 0 = forward, bit 1 = data
+# gradient (conv1 of a block with conv3 of the previous one); 0 = the per-op calls everywhere
+CONV_PAIR = knob("TOIST_CONV_PAIR", 3)
+CONV_PAIR_CALLS = [0, 0]     # launches so far: forward, data gradient (tests)
+
+
+def conv_pair(a, w_first, w_second, res, mid, out, *, dgrad=False, shift_mid=None, shift_out=None, aux_mid=None, aux_out=None):
+    """mid [M, 1024], out [M, 256] of two chained 1x1 convolutions on the rows of a [M, 256] (see toist_conv_pair in include/toist_hip.h).
+    Every tensor is a 2-D bf16 view whose rows are contiguous (stride(1) == 1); weights are contiguous."""
+    M, C = a.shape
+    for t in (a, res, mid, out, aux_mid, aux_out):
+        if t is not None and (t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != M):
+            raise ValueError("conv_pair: operands are [M, width] views with contiguous rows")
+    if tuple(w_first.shape) != ((C, 4 * C) if dgrad else (4 * C, C)) or tuple(w_second.shape) != ((4 * C, C) if dgrad else (C, 4 * C)) \
+            or not (w_first.is_contiguous() and w_second.is_contiguous()):
+        raise ValueError("conv_pair: weights are contiguous [4C, C] / [C, 4C] (forward) or [C, 4C] / [4C, C] (data gradient)")
+    if tuple(res.shape) != (M, 4 * C) or tuple(mid.shape) != (M, 4 * C) or tuple(out.shape) != (M, C):
+        raise ValueError("conv_pair: res / mid are [M, 4C], out is [M, C]")
+    d = ConvPair()
+    d.M, d.C, d.dgrad, d.lda = M, C, 1 if dgrad else 0, a.stride(0)
+    d.a, d.w_first, d.w_second = _p(a, torch.bfloat16), _p(w_first, torch.bfloat16), _p(w_second, torch.bfloat16)
+    d.shift_mid, d.shift_out = _p(shift_mid, torch.float32), _p(shift_out, torch.float32)
+    d.res, d.ldr = _p(res, torch.bfloat16), res.stride(0)
+    d.aux_mid, d.ldaux_mid = _p(aux_mid, torch.bfloat16), aux_mid.stride(0) if aux_mid is not None else 0
+    d.aux_out, d.ldaux_out = _p(aux_out, torch.bfloat16), aux_out.stride(0) if aux_out is not None else 0
+    d.mid, d.ldmid, d.out, d.ldout = _p(mid, torch.bfloat16), mid.stride(0), _p(out, torch.bfloat16), out.stride(0)
+    CONV_PAIR_CALLS[1 if dgrad else 0] += 1
+    _lib.check(_lib.lib().toist_conv_pair_bf16(ctypes.cast(ctypes.pointer(d), ctypes.c_void_p), _stream()), "toist_conv_pair_bf16")
+
+
 def matcher(logits, boxes, tgt_boxes, pos_map, tgt_off, match_off, max_T, w_class, w_bbox, w_giou, src_idx, tgt_idx,
             status, cost_out=None):
     L, B, Q, K = logits.shape

@@ -58,8 +58,7 @@ def tape_seeds(seed):
 # attention probabilities ("by_head_dim": the flash-style core at head dimension 32, the per-op softmax kernels otherwise)
 _ENC = dict(head=(), layer=("attn", "out", "hidden", "ffn_out"), tail=())
 ROUTES = {
-    "tlayer.encoder_program": dict(_ENC, attn="flash"),       # _core, _ln_fwd (out_proj), _ffn_fwd, _ln_fwd (linear2)
-    "prog_fused": dict(_ENC, attn="flash"),                   # self_attention_block (_attn_core, _out_proj), linear_chain (hidden, final)
+    "tlayer.encoder_program": dict(_ENC, attn="flash"),       # engine.flash_core, _ln_fwd (out_proj), _ffn_fwd, _ln_fwd (linear2)
     "per_op_encoder": dict(_ENC, attn="by_head_dim"),         # engine.attention (probabilities, out_proj), linear_chain (hidden, final)
     "text": dict(head=("emb",), layer=("attn", "out", "ffn_out"), tail=("resizer",), attn="small"),   # engine.dropout, text_attention_block, linear_chain (final), engine.dropout
 }

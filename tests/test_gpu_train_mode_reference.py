@@ -9,7 +9,7 @@ What fails here and nowhere else in the suite: a backward that masks with anothe
   blocks      linear_chain ReLU FFN (dropout_after + final_drop) + residual + layernorm (Var.drop / gdrop through the LayerNorm backward), the GELU chain with
               final_drop (take_branch_grad's own launch), engine.dropout (exact), engine.attention on the per-op core (cross attention 33 x 52 and packed
               self attention, head dim 64) and on the flash-style core (head dim 32), text_attention_block
-  programs    two layers each: Transformer.encode_tokens on its three routes (tlayer.encoder_program, prog_fused, the per-op program), Transformer.encode_text on
+  programs    two layers each: Transformer.encode_tokens on its two routes (tlayer.encoder_program, the per-op program), Transformer.encode_text on
               a tiny RoBERTa; for every route the seeds the tape drew must be the seeds the reference consumed, one per site of train_ref.ROUTES
 
 Bounds (none is fitted to what the kernels give):
@@ -419,7 +419,7 @@ def _encoder_route(dev, model, route, p):
     g = torch.Generator().manual_seed(40)
     x, pos, g_out = _rows(g, B * S, d), _rows(g, B * S, d), _rows(g, B * S, d)
     key_pad = _tail_pad(B, S)
-    tlayer.ENABLED, engine.FUSED_BLOCKS = {"tlayer.encoder_program": (True, True), "prog_fused": (False, True), "per_op_encoder": (False, False)}[route]
+    tlayer.ENABLED, engine.FUSED_BLOCKS = {"tlayer.encoder_program": (True, True), "per_op_encoder": (False, False)}[route]
     assert tlayer.supported(d, H, S) == (route == "tlayer.encoder_program")
     model.zero_grad(set_to_none=True)
     seed = model._step + 1
@@ -441,7 +441,7 @@ def _encoder_route(dev, model, route, p):
     return _program_check("encode_tokens/" + route, route, p, got, fn, leaves, g_out, used, drawn)
 
 
-@pytest.mark.parametrize("route", ["tlayer.encoder_program", "prog_fused", "per_op_encoder"])
+@pytest.mark.parametrize("route", ["tlayer.encoder_program", "per_op_encoder"])
 def test_encoder_program_with_dropout(dev, state, model, route):
     if _encoder_route(dev, model, route, P):          # loose at p = 0.1 (ReLU gates flipped by a rounding): the same program at p = 0
         _encoder_route(dev, model, route, 0.0)

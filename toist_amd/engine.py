@@ -22,14 +22,13 @@ BF16 = torch.bfloat16
 class Var:
     """An activation (bf16, [rows, features] or NHWC) and its gradient slot."""
 
-    __slots__ = ("data", "grad", "needs_grad", "drop", "gdrop", "plus", "raw_grad")
+    __slots__ = ("data", "grad", "needs_grad", "drop", "gdrop", "raw_grad")
 
     def __init__(self, data, needs_grad=True):
         self.data = data
         self.grad = None
         self.needs_grad = needs_grad
         self.raw_grad = False   # True: the program's backward wants the output gradient exactly as autograd delivered it (no dtype cast, no .contiguous())
-        self.plus = None    # data + a constant embedding (pos / query_pos), when the producing layernorm emitted it in the same pass
         self.drop = None    # (p, seed) when data = residual + dropout(branch): the branch gradient is dropout(grad) with that mask
         self.gdrop = None   # that masked gradient, when the consumer's backward produced it in the same pass (layernorm)
 
@@ -54,7 +53,7 @@ class Var:
 # every fork is a cross-stream edge of the graph) and is deliberately not done.
 OVERLAP = knob("TOIST_OVERLAP", "capture")   # "capture": fork the text branch inside captured graphs only; "on" / "off"
 FUSED_ATTENTION = True   # head-dim-32 attention cores run as one flash-style launch each way (csrc/attn2.hip); False = batched score GEMMs + softmax kernels
-FUSED_BLOCKS = True      # encoder / decoder layers: packed in_proj in one launch, decoder K/V of all layers grouped, LayerNorm emits y + pos
+FUSED_BLOCKS = True      # text encoder: text_attention_block for short captions; encoder / decoder: tlayer.supported honours it, so False = the per-op programs everywhere
 _SIDE = {}
 SIDE_PRIORITY = knob("TOIST_SIDE_PRIORITY", 0)   # -1 = high: the small kernels of a side branch get free CU slots first
 
@@ -482,8 +481,6 @@ def linear_chain(tape, x, layers, res=None, final_drop=False, out_dtype=BF16, la
             return
         if res is not None and res.needs_grad:
             accumulate(res, g)
-            if res.grad is g:  # keep our own copy if we are about to modify g
-                pass
         for i in range(n - 1, -1, -1):
             W, b, act, drop_after = layers[i]
             xin, y, pre = acts[i]
@@ -523,17 +520,14 @@ def linear_chain(tape, x, layers, res=None, final_drop=False, out_dtype=BF16, la
     return out
 
 
-def layernorm(tape, x, gamma, beta, eps, y=None, add=None):
-    """LayerNorm; with `add` (bf16 [rows, D], a constant of the backward pass) the same launch also writes out.plus = y + add."""
+def layernorm(tape, x, gamma, beta, eps, y=None):
     rows, D = x.data.shape
     if y is None:
         y = torch.empty_like(x.data)
     mean = torch.empty(rows, dtype=torch.float32, device=y.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=y.device)
-    y2 = torch.empty_like(x.data) if add is not None else None
-    k.layernorm_fwd(x.data, gamma.f32, beta.f32, eps, y, mean, rstd, add=add, y2=y2)
+    k.layernorm_fwd(x.data, gamma.f32, beta.f32, eps, y, mean, rstd)
     out = Var(y)
-    out.plus = y2
 
     def bwd():
         g = out.take_grad()
@@ -614,6 +608,29 @@ def dropout(tape, x):
     return out
 
 
+def flash_core(qb, kb, vb, key_pad, B, Sq, Sk, H, ctx, p, seed_p):
+    """attention core forward (csrc/attn2.hip, head dim 32); returns core_bwd(dctx, dq, dk, dv) -> None, or the bf16 [splits, B*Sq, H*dh] partial
+    sums of dq that the consumer of dq must fold (kernels.rowgemm(fold=...), or a sum) when the keys of a head are owned by several workgroups"""
+    dh = qb.shape[1] // H
+    lse = torch.empty(B * H, Sq, 2, dtype=torch.float32, device=qb.device)
+    k.attn2_fwd(qb, kb, vb, key_pad, B, H, Sq, Sk, dh, 1.0 / math.sqrt(dh), p, seed_p, ctx, lse)
+    return flash_core_bwd(qb, kb, vb, key_pad, B, Sq, Sk, H, ctx, p, seed_p, lse)
+
+
+def flash_core_bwd(qb, kb, vb, key_pad, B, Sq, Sk, H, ctx, p, seed_p, lse):
+    """backward closure of an attn2-convention forward that has already run (attn2_fwd above, or the XCD-resident decoder launch)"""
+    dh = qb.shape[1] // H
+    scale = 1.0 / math.sqrt(dh)
+    splits = k.attn2_splits(Sk)
+
+    def core_bwd(dctx, dq, dk, dv):
+        part = torch.empty(splits, B * Sq, H * dh, dtype=BF16, device=qb.device) if splits > 1 else None
+        k.attn2_bwd(qb, kb, vb, ctx, dctx, lse, key_pad, B, H, Sq, Sk, dh, scale, p, seed_p, dq if splits == 1 else None, dk, dv, dq_part=part)
+        return part
+
+    return core_bwd
+
+
 def attention(tape, q_in, k_in, v_in, Pq, Pk, Pv, Wo, bo, resid, key_pad, B, Sq, Sk, H, packed_qk=None):
     """resid + dropout(out_proj(softmax(q k^T / sqrt(dh) + mask) v)) -- nn.MultiheadAttention plus the
     residual/dropout that follows it (transformer.py:297-299, 370-400), also HF RobertaSelfAttention +
@@ -639,9 +656,7 @@ def attention(tape, q_in, k_in, v_in, Pq, Pk, Pv, Wo, bo, resid, key_pad, B, Sq,
         # scores -> mask -> softmax -> dropout -> P V in one flash-style launch (csrc/attn2.hip): nothing score-shaped is written (22 MB of P and
         # 22 MB of dropout(P) per encoder layer at B = 8 otherwise), only (row maximum, 1 / row sum) per score row; any key count
         prob = prob_used = None
-        ld = ops.round8(Sk)
-        lse = torch.empty(B * H, Sq, 2, dtype=torch.float32, device=dev)
-        k.attn2_fwd(qb, kb, vb, key_pad, B, H, Sq, Sk, dh, scale, p, seed_p, ctx, lse)
+        core_bwd = flash_core(qb, kb, vb, key_pad, B, Sq, Sk, H, ctx, p, seed_p)
     else:
         s = ops.attn_scores(qb, kb, B, H, Sq, Sk, dh, scale)
         ld = s.shape[-1]
@@ -683,9 +698,7 @@ def attention(tape, q_in, k_in, v_in, Pq, Pk, Pv, Wo, bo, resid, key_pad, B, Sq,
 
         if fused_core:
             # key-owning backward (csrc/attn2.hip): dK / dV written once, dQ directly or as one bf16 share per 128-key split
-            splits = k.attn2_splits(Sk)
-            part = torch.empty(splits, B * Sq, d, dtype=BF16, device=dev) if splits > 1 else None
-            k.attn2_bwd(qb, kb, vb, ctx, dctx, lse, key_pad, B, H, Sq, Sk, dh, scale, p, seed_p, dq if splits == 1 else None, dk, dv, dq_part=part)
+            part = core_bwd(dctx, dq, dk, dv)
             if part is not None:
                 dq.copy_(part.float().sum(0))
         else:
@@ -713,30 +726,6 @@ def attention(tape, q_in, k_in, v_in, Pq, Pk, Pv, Wo, bo, resid, key_pad, B, Sq,
     return out
 
 
-# ---- attention blocks with the packed in_proj applied in one launch (FUSED_BLOCKS) -------------------------------------
-# nn.MultiheadAttention(q = k = x + e, v = x) (transformer.py:293-297, 366-372): ONE GEMM forms [q | k | v] -- output columns
-# < 2d read their A rows from xe = x + e, the others from x (toist_gemm.a2) -- and one GEMM carries d[q | k | v] back to x.
-# The gradient w.r.t. a trainable e (the decoder's query embedding) is not formed per layer: every block leaves its dq / dk in a
-# column slice of one [rows, n] buffer (`e_sink`) and the caller multiplies that buffer once by the stacked projection weights.
-def _attn_core(tape, qb, kb, vb, key_pad, B, Sq, Sk, H, ctx, p, seed_p):
-    """attention core of the fused blocks (csrc/attn2.hip, head dim 32); returns core_bwd(dctx, dq, dk, dv)"""
-    dh = qb.shape[1] // H
-    scale = 1.0 / math.sqrt(dh)
-    if not (FUSED_ATTENTION and dh == 32):
-        raise NotImplementedError("fused attention blocks need head dim 32")
-    lse = torch.empty(B * H, Sq, 2, dtype=torch.float32, device=qb.device)
-    k.attn2_fwd(qb, kb, vb, key_pad, B, H, Sq, Sk, dh, scale, p, seed_p, ctx, lse)
-    splits = k.attn2_splits(Sk)
-
-    def core_bwd(dctx, dq, dk, dv):
-        part = torch.empty(splits, B * Sq, H * dh, dtype=BF16, device=qb.device) if splits > 1 else None
-        k.attn2_bwd(qb, kb, vb, ctx, dctx, lse, key_pad, B, H, Sq, Sk, dh, scale, p, seed_p, dq if splits == 1 else None, dk, dv, dq_part=part)
-        if part is not None:
-            dq.copy_(part.float().sum(0))
-
-    return core_bwd
-
-
 def _out_proj(tape, ctx, Wo, bo, resid, p):
     """resid + dropout(ctx Wo^T + bo); returns (Var, bwd_head) where bwd_head() -> gradient w.r.t. ctx (or None)."""
     seed_o = tape.next_seed() if p > 0 else 0
@@ -759,45 +748,6 @@ def _out_proj(tape, ctx, Wo, bo, resid, p):
     return out, head
 
 
-def self_attention_block(tape, x, xe, Win, bin_, Wo, bo, key_pad, B, S, H, e_sink=None):
-    """x + dropout(out_proj(MHA(q = k = xe, v = x)));  xe = x + e as a bf16 tensor.  e_sink = (buffer [B*S, n] bf16, column):
-    d q and d k are written at buffer[:, column : column + 2d] (and d v right after, buffer[:, column + 2d : column + 3d])."""
-    d = Wo.w.shape[0]
-    M = B * S
-    dev = x.data.device
-    p = tape.drop_p
-    qkv = torch.empty(M, 3 * d, dtype=BF16, device=dev)
-    k.gemm(M, 3 * d, d, k.A_ROWK, k.operand(xe, xe.stride(0)), k.B_ROWK, k.operand(Win.w, Win.w.stride(0)), qkv, 3 * d, shift=bin_.f32,
-           a2=x.data, a2_from=2 * d, flops=2 * M * 3 * d * d)
-    seed_p = tape.next_seed() if p > 0 else 0
-    ctx = torch.empty(M, d, dtype=BF16, device=dev)
-    core_bwd = _attn_core(tape, qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], key_pad, B, S, S, H, ctx, p, seed_p)
-    out, head = _out_proj(tape, ctx, Wo, bo, x, p)
-
-    def bwd():
-        dctx = head()
-        if dctx is None:
-            return
-        if e_sink is not None:
-            buf, col = e_sink
-            dqkv = buf[:, col:col + 3 * d]
-        else:
-            dqkv = torch.empty(M, 3 * d, dtype=BF16, device=dev)
-        core_bwd(dctx, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:])
-        if Win.g is not None:
-            tape.linear_wgrad(dqkv[:, :2 * d], xe, Win.rows(0, 2 * d), bin_.rows(0, 2 * d))
-            tape.linear_wgrad(dqkv[:, 2 * d:], x.data, Win.rows(2 * d, 3 * d), bin_.rows(2 * d, 3 * d))
-        if x.needs_grad:
-            x.grad = ops.linear_dgrad(dqkv, Win.w, res=x.grad)      # d x = [dq | dk | dv] W_in  (+ residual gradient)
-
-    tape.record(bwd)
-    return out
-
-
-def W0_has_grad(layers):
-    return layers[0][0].g is not None
-
-
 def cross_kv_projections(tape, mem, mem_e, layers):
     """k_i = mem_e Wk_i^T + bk_i, v_i = mem Wv_i^T + bv_i for every decoder layer i in ONE grouped launch (the inputs are the same
     for all layers, transformer.py:386-391): layers = [(Win_i, bin_i)] with the packed [3d, d] in_proj of cross_attn_image.
@@ -807,7 +757,7 @@ def cross_kv_projections(tape, mem, mem_e, layers):
     M = mem.data.shape[0]
     dev = mem.data.device
     kv = torch.empty(M, L * 2 * d, dtype=BF16, device=dev)
-    dkv = torch.empty(M, L * 2 * d, dtype=BF16, device=dev) if (mem.needs_grad or W0_has_grad(layers)) else None
+    dkv = torch.empty(M, L * 2 * d, dtype=BF16, device=dev) if (mem.needs_grad or layers[0][0].g is not None) else None
     W0, b0 = layers[0]
     rows = []
     for i, (W, b) in enumerate(layers):
@@ -832,38 +782,6 @@ def cross_kv_projections(tape, mem, mem_e, layers):
 
     tape.record(bwd)     # recorded before the decoder layers: runs after all of them have written their slices of dkv
     return kv, dkv
-
-
-def cross_attention_block(tape, t, te, Wq, bq, kv, dkv, col, Wo, bo, key_pad, B, Sq, Sk, H, e_sink=None):
-    """t + dropout(out_proj(MHA(q = te, k, v precomputed)));  te = t + e (bf16 tensor); k, v = kv[:, col : col + d], kv[:, col + d : col + 2d]
-    from cross_kv_projections, whose backward consumes the dk / dv this block writes into the same columns of dkv."""
-    d = Wo.w.shape[0]
-    M = B * Sq
-    dev = t.data.device
-    p = tape.drop_p
-    qb = ops.linear(te, Wq.w, bq.f32)
-    seed_p = tape.next_seed() if p > 0 else 0
-    ctx = torch.empty(M, d, dtype=BF16, device=dev)
-    core_bwd = _attn_core(tape, qb, kv[:, col:col + d], kv[:, col + d:col + 2 * d], key_pad, B, Sq, Sk, H, ctx, p, seed_p)
-    out, head = _out_proj(tape, ctx, Wo, bo, t, p)
-
-    def bwd():
-        dctx = head()
-        if dctx is None:
-            return
-        if e_sink is not None:
-            buf, c2 = e_sink
-            dq = buf[:, c2:c2 + d]
-        else:
-            dq = torch.empty(M, d, dtype=BF16, device=dev)
-        core_bwd(dctx, dq, dkv[:, col:col + d], dkv[:, col + d:col + 2 * d])
-        if Wq.g is not None:
-            tape.linear_wgrad(dq, te, Wq, bq)
-        if t.needs_grad:
-            t.grad = ops.linear_dgrad(dq, Wq.w, res=t.grad)
-
-    tape.record(bwd)
-    return out
 
 
 def packed_cast(view):

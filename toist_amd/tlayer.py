@@ -14,7 +14,6 @@ A LayerNorm's backward is computed by the kernel that produces the gradient of i
 gradient of a LayerNorm input appears directly; every stand-alone LayerNorm launch of the two stacks disappears except the ones whose
 output gradient arrives from outside the program (last encoder layer, last decoder layer) and the shared final decoder norm.
 Weight gradients go to the tape's grouped launches exactly as in toist_amd.engine."""
-import math
 import os
 from types import SimpleNamespace
 
@@ -25,7 +24,7 @@ from . import kernels as k
 from .knobs import knob
 
 BF16 = torch.bfloat16
-ENABLED = knob("TOIST_ROWS", True)          # tests flip this to compare with the per-op path of toist_amd.engine
+ENABLED = knob("TOIST_ROWS", True)          # TOIST_ROWS=0 (tests: ENABLED = False) selects the per-op programs of toist_amd.transformer
 
 
 FUSE_FWD_MAX_K = knob("TOIST_ROWS_FWD_MAX_K", 768)      # forward sub-layers with a longer reduction run as GEMM + LayerNorm launch ...
@@ -38,30 +37,6 @@ XDEC = os.environ.get("TOIST_XDEC", "1") != "0"
 
 def supported(d, H, Sk):
     return ENABLED and engine.FUSED_BLOCKS and d == 256 and d // H == 32
-
-
-def _core(tape, qb, kb, vb, key_pad, B, Sq, Sk, H, ctx, p, seed_p):
-    """attention core forward; returns core_bwd(dctx, dq, dk, dv) -> None, or the bf16 [splits, B*Sq, 256] partial sums of dq that the
-    consumer of dq must fold (kernels.rowgemm(fold=...)) when the keys of a head are owned by several workgroups"""
-    dh = qb.shape[1] // H
-    scale = 1.0 / math.sqrt(dh)
-    lse = torch.empty(B * H, Sq, 2, dtype=torch.float32, device=qb.device)
-    k.attn2_fwd(qb, kb, vb, key_pad, B, H, Sq, Sk, dh, scale, p, seed_p, ctx, lse)
-    return _core_bwd_of(qb, kb, vb, key_pad, B, Sq, Sk, H, ctx, p, seed_p, lse)
-
-
-def _core_bwd_of(qb, kb, vb, key_pad, B, Sq, Sk, H, ctx, p, seed_p, lse):
-    """backward closure of an attn2-convention forward that has already run (attn2_fwd above, or the XCD-resident decoder launch)"""
-    dh = qb.shape[1] // H
-    scale = 1.0 / math.sqrt(dh)
-    splits = k.attn2_splits(Sk)
-
-    def core_bwd(dctx, dq, dk, dv):
-        part = torch.empty(splits, B * Sq, H * dh, dtype=BF16, device=qb.device) if splits > 1 else None
-        k.attn2_bwd(qb, kb, vb, ctx, dctx, lse, key_pad, B, H, Sq, Sk, dh, scale, p, seed_p, dq if splits == 1 else None, dk, dv, dq_part=part)
-        return part
-
-    return core_bwd
 
 
 def _ln_fwd(ctx_in, W, b, res, gamma, beta, tape, add=None, y=None, eps=1e-5):
@@ -144,6 +119,25 @@ def _qkv(xe, x, Win, bin_, M, d):
     return qkv
 
 
+def _enc_layer(ps, i):
+    """ParamViews of encoder layer i; the program adds its inputs and saved tensors to the same record"""
+    P = lambda n: ps[f"layers.{i}.{n}"]
+    return SimpleNamespace(i=i, Win=P("self_attn.in_proj_weight"), bin=P("self_attn.in_proj_bias"), Wo=P("self_attn.out_proj.weight"), bo=P("self_attn.out_proj.bias"),
+                           W1=P("linear1.weight"), b1=P("linear1.bias"), W2=P("linear2.weight"), b2=P("linear2.bias"),
+                           norm1=(P("norm1.weight"), P("norm1.bias")), norm2=(P("norm2.weight"), P("norm2.bias")))
+
+
+def _dec_layer(ps, i, Wself, Wcross):
+    """ParamViews of decoder layer i (Wself / Wcross: the packed in_proj pairs of all layers) and `col`, the layer's column in kv / dkv"""
+    P = lambda n: ps[f"layers.{i}.{n}"]
+    d = 256
+    (Ws, bs), (Wc, bc) = Wself[i], Wcross[i]
+    return SimpleNamespace(i=i, col=i * 2 * d, Ws=Ws, bs=bs, Wc=Wc, bc=bc, Wq=Wc.rows(0, d), bq=bc.rows(0, d),
+                           Wos=P("self_attn.out_proj.weight"), bos=P("self_attn.out_proj.bias"), Woc=P("cross_attn_image.out_proj.weight"),
+                           boc=P("cross_attn_image.out_proj.bias"), W1=P("linear1.weight"), b1=P("linear1.bias"), W2=P("linear2.weight"), b2=P("linear2.bias"),
+                           norm1=(P("norm1.weight"), P("norm1.bias")), norm3=(P("norm3.weight"), P("norm3.bias")), norm4=(P("norm4.weight"), P("norm4.bias")))
+
+
 # ------------------------------------------------------------------------------------------------------------------ encoder
 def encoder_program(tape, ps, x, pos, key_pad, B, S, H, n_layers):
     """6 post-norm encoder layers over batch-major tokens x [B*S, 256]; pos = bf16 constant of the same shape"""
@@ -153,18 +147,15 @@ def encoder_program(tape, ps, x, pos, key_pad, B, S, H, n_layers):
     cur, cur_e = x.data, xe
     layers = []
     for i in range(n_layers):
-        lp = f"layers.{i}."
-        L = SimpleNamespace(i=i, x_in=cur, xe_in=cur_e)
-        L.Win, L.bin = ps[lp + "self_attn.in_proj_weight"], ps[lp + "self_attn.in_proj_bias"]
-        L.Wo, L.bo = ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"]
-        L.W1, L.b1, L.W2, L.b2 = ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], ps[lp + "linear2.weight"], ps[lp + "linear2.bias"]
+        L = _enc_layer(ps, i)
+        L.x_in, L.xe_in = cur, cur_e
         qkv = _qkv(cur_e, cur, L.Win, L.bin, M, d)
         seed_p = tape.next_seed() if p > 0 else 0
         L.ctx = torch.empty(M, d, dtype=BF16, device=cur.device)
-        L.core_bwd = _core(tape, qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], key_pad, B, S, S, H, L.ctx, p, seed_p)
-        L.ln1 = _ln_fwd(L.ctx, L.Wo, L.bo, cur, ps[lp + "norm1.weight"], ps[lp + "norm1.bias"], tape)
+        L.core_bwd = engine.flash_core(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], key_pad, B, S, S, H, L.ctx, p, seed_p)
+        L.ln1 = _ln_fwd(L.ctx, L.Wo, L.bo, cur, *L.norm1, tape)
         L.h = _ffn_fwd(tape, L.ln1.y, L.W1, L.b1)
-        L.ln2 = _ln_fwd(L.h, L.W2, L.b2, L.ln1.y, ps[lp + "norm2.weight"], ps[lp + "norm2.bias"], tape, add=pos if i + 1 < n_layers else None)
+        L.ln2 = _ln_fwd(L.h, L.W2, L.b2, L.ln1.y, *L.norm2, tape, add=pos if i + 1 < n_layers else None)
         cur, cur_e = L.ln2.y, L.ln2.y2
         layers.append(L)
     out = engine.Var(cur)
@@ -235,20 +226,14 @@ def _decoder_layers_xcd(tape, ps, Wself, Wcross, x0, qpos, kv, key_pad, tgt_stac
     out, part = xdec_fwd_buffers(B, Q, L_, x0.device, tgt_stack, H)
     recs, table = [], []
     for i in range(L_):
-        lp = f"layers.{i}."
-        L = SimpleNamespace(i=i, x_in=x0 if i == 0 else out["y4"][i - 1], xe_in=qpos if i == 0 else out["y4e"][i - 1])
-        L.Ws, L.bs = Wself[i]
-        L.Wc, L.bc = Wcross[i]
-        L.Wq, L.bq = L.Wc.rows(0, d), L.bc.rows(0, d)
-        L.Wos, L.bos = ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"]
-        L.Woc, L.boc = ps[lp + "cross_attn_image.out_proj.weight"], ps[lp + "cross_attn_image.out_proj.bias"]
-        L.W1, L.b1, L.W2, L.b2 = ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], ps[lp + "linear2.weight"], ps[lp + "linear2.bias"]
-        norms = [(ps[lp + f"norm{j}.weight"], ps[lp + f"norm{j}.bias"]) for j in (1, 3, 4)]
+        L = _dec_layer(ps, i, Wself, Wcross)
+        L.x_in, L.xe_in = (x0, qpos) if i == 0 else (out["y4"][i - 1], out["y4e"][i - 1])
+        norms = [L.norm1, L.norm3, L.norm4]
         seeds = [tape.next_seed() if p > 0 else 0 for _ in range(6)]      # self-attention, norm1, cross-attention, norm3, hidden, norm4
         qkv = out["qkv"][i]
-        L.ctx_s, L.ctx_c, L.h, L.col = out["ctx_s"][i], out["ctx_c"][i], out["h"][i], i * 2 * d
-        L.core_s = _core_bwd_of(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], None, B, Q, Q, H, L.ctx_s, p, seeds[0], out["lse_s"][i])
-        L.core_c = _core_bwd_of(out["qc"][i], kv[:, L.col:L.col + d], kv[:, L.col + d:L.col + 2 * d], key_pad, B, Q, S, H, L.ctx_c, p, seeds[2], out["lse_c"][i])
+        L.ctx_s, L.ctx_c, L.h = out["ctx_s"][i], out["ctx_c"][i], out["h"][i]
+        L.core_s = engine.flash_core_bwd(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], None, B, Q, Q, H, L.ctx_s, p, seeds[0], out["lse_s"][i])
+        L.core_c = engine.flash_core_bwd(out["qc"][i], kv[:, L.col:L.col + d], kv[:, L.col + d:L.col + 2 * d], key_pad, B, Q, S, H, L.ctx_c, p, seeds[2], out["lse_c"][i])
         last = i + 1 == L_
         L.ln1 = SimpleNamespace(seed=seeds[1], z=out["z1"][i], y=out["y1"][i], y2=out["y1e"][i], mean=out["mean1"][i], rstd=out["rstd1"][i], gamma=norms[0][0],
                                 beta=norms[0][1], dz=None, dzd=None)
@@ -334,31 +319,22 @@ def decoder_program(tape, ps, mem, qe, pos, key_pad, B, S, Q, H, n_layers):
     if fused:
         layers, fw = _decoder_layers_xcd(tape, ps, Wself, Wcross, cur, qpos, kv, key_pad, tgt_stack, B, S, Q, H, L_)
     for i in range(0 if not fused else L_, L_):
-        lp = f"layers.{i}."
-        L = SimpleNamespace(i=i, x_in=cur, xe_in=cur_e)
-        L.Ws, L.bs = Wself[i]
-        L.Wc, L.bc = Wcross[i]
-        L.Wq, L.bq = L.Wc.rows(0, d), L.bc.rows(0, d)
-        L.Wos, L.bos = ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"]
-        L.Woc, L.boc = ps[lp + "cross_attn_image.out_proj.weight"], ps[lp + "cross_attn_image.out_proj.bias"]
-        L.W1, L.b1, L.W2, L.b2 = ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], ps[lp + "linear2.weight"], ps[lp + "linear2.bias"]
+        L = _dec_layer(ps, i, Wself, Wcross)
+        L.x_in, L.xe_in = cur, cur_e
         # self-attention: q = k = tgt + query_pos, v = tgt
         qkv = _qkv(cur_e, cur, L.Ws, L.bs, M, d)
         seed_s = tape.next_seed() if p > 0 else 0
         L.ctx_s = torch.empty(M, d, dtype=BF16, device=dev)
-        L.core_s = _core(tape, qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], None, B, Q, Q, H, L.ctx_s, p, seed_s)
-        L.ln1 = _ln_fwd(L.ctx_s, L.Wos, L.bos, cur, ps[lp + "norm1.weight"], ps[lp + "norm1.bias"], tape, add=qpos)
+        L.core_s = engine.flash_core(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], None, B, Q, Q, H, L.ctx_s, p, seed_s)
+        L.ln1 = _ln_fwd(L.ctx_s, L.Wos, L.bos, cur, *L.norm1, tape, add=qpos)
         # cross-attention: q = t1 + query_pos, k = memory + pos, v = memory (k, v projected for all layers up front)
         qc = ops.linear(L.ln1.y2, L.Wq.w, L.bq.f32)
         seed_c = tape.next_seed() if p > 0 else 0
         L.ctx_c = torch.empty(M, d, dtype=BF16, device=dev)
-        col = i * 2 * d
-        L.col = col
-        L.core_c = _core(tape, qc, kv[:, col:col + d], kv[:, col + d:col + 2 * d], key_pad, B, Q, S, H, L.ctx_c, p, seed_c)
-        L.ln3 = _ln_fwd(L.ctx_c, L.Woc, L.boc, L.ln1.y, ps[lp + "norm3.weight"], ps[lp + "norm3.bias"], tape)
+        L.core_c = engine.flash_core(qc, kv[:, L.col:L.col + d], kv[:, L.col + d:L.col + 2 * d], key_pad, B, Q, S, H, L.ctx_c, p, seed_c)
+        L.ln3 = _ln_fwd(L.ctx_c, L.Woc, L.boc, L.ln1.y, *L.norm3, tape)
         L.h = _ffn_fwd(tape, L.ln3.y, L.W1, L.b1)
-        L.ln4 = _ln_fwd(L.h, L.W2, L.b2, L.ln3.y, ps[lp + "norm4.weight"], ps[lp + "norm4.bias"], tape, add=qpos if i + 1 < L_ else None,
-                        y=tgt_stack[i])
+        L.ln4 = _ln_fwd(L.h, L.W2, L.b2, L.ln3.y, *L.norm4, tape, add=qpos if i + 1 < L_ else None, y=tgt_stack[i])
         L.out = engine.Var(L.ln4.y)          # receives the gradient of the shared final norm (split_bwd below)
         cur, cur_e = L.ln4.y, L.ln4.y2
         layers.append(L)

@@ -228,6 +228,78 @@ class TokenizedText(dict):
         return type(self)({k_: (v.to(device) if torch.is_tensor(v) else v) for k_, v in self.items()})
 
 
+# ------------------------------------------------------------------------------------------ per-op programs
+# Encoder / decoder stacks for any d_model and head count, one engine op per reference op (engine.attention, layernorm, linear_chain).
+# The product shape (d_model 256, head dim 32) runs toist_amd.tlayer instead; these are what TOIST_ROWS=0 / engine.FUSED_BLOCKS = False select.
+def per_op_encoder_program(tape, ps, x, pos, key_pad, B, S, H, n_layers):
+    """post-norm encoder layers over batch-major tokens x [B*S, d]; pos = bf16 constant of the same shape (transformer.py:290-304)"""
+    d = ps["layers.0.self_attn.in_proj_weight"].w.shape[1]
+    for i in range(n_layers):
+        lp = f"layers.{i}."
+        Wi, bi = ps[lp + "self_attn.in_proj_weight"], ps[lp + "self_attn.in_proj_bias"]
+        qk = engine.add_const(tape, x, pos)
+        z = engine.attention(tape, qk, qk, x, None, None, (Wi.rows(2 * d, 3 * d), bi.rows(2 * d, 3 * d)),
+                             ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"], x, key_pad, B, S, S, H,
+                             packed_qk=(Wi.rows(0, 2 * d), bi.rows(0, 2 * d)))
+        x1 = engine.layernorm(tape, z, ps[lp + "norm1.weight"], ps[lp + "norm1.bias"], 1e-5)
+        z2 = engine.linear_chain(tape, x1, [(ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], k.ACT_RELU, True),
+                                            (ps[lp + "linear2.weight"], ps[lp + "linear2.bias"], k.ACT_NONE, False)],
+                                 res=x1, final_drop=True)
+        x = engine.layernorm(tape, z2, ps[lp + "norm2.weight"], ps[lp + "norm2.bias"], 1e-5)
+    return [x], None
+
+
+def per_op_decoder_program(tape, ps, mem, qe, pos, key_pad, B, S, Q, H, n_layers):
+    """decoder layers (self-attention over the queries, cross-attention into the encoder memory, FFN), each output through the shared final
+    LayerNorm; returns [hs] with hs [L, B*Q, d] bf16 (transformer.py:225-267, 362-408)"""
+    d = ps["layers.0.self_attn.in_proj_weight"].w.shape[1]
+    dev = mem.data.device
+    qpos_data = qe.data.to(BF16).unsqueeze(0).expand(B, Q, d).reshape(B * Q, d).contiguous()
+    qpos = engine.Var(qpos_data, needs_grad=qe.needs_grad)
+
+    def qpos_bwd():
+        g = qpos.take_grad()
+        if g is not None and qe.needs_grad:
+            gq = g.view(B, Q, d).float().sum(0)
+            qe.grad = gq if qe.grad is None else qe.grad + gq
+
+    tape.record(qpos_bwd)
+    mem_pos = engine.add_const(tape, mem, pos)
+    tgt = engine.Var(torch.zeros(B * Q, d, dtype=BF16, device=dev), needs_grad=False)
+    stack = torch.empty(n_layers, B * Q, d, dtype=BF16, device=dev)
+    inter = []
+    for i in range(n_layers):
+        lp = f"layers.{i}."
+        Ws, bs = ps[lp + "self_attn.in_proj_weight"], ps[lp + "self_attn.in_proj_bias"]
+        Wc, bc = ps[lp + "cross_attn_image.in_proj_weight"], ps[lp + "cross_attn_image.in_proj_bias"]
+        qk = engine.add_vars(tape, tgt, qpos)
+        z1 = engine.attention(tape, qk, qk, tgt, None, None, (Ws.rows(2 * d, 3 * d), bs.rows(2 * d, 3 * d)),
+                              ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"], tgt, None, B, Q, Q, H,
+                              packed_qk=(Ws.rows(0, 2 * d), bs.rows(0, 2 * d)))
+        t1 = engine.layernorm(tape, z1, ps[lp + "norm1.weight"], ps[lp + "norm1.bias"], 1e-5)
+        q2 = engine.add_vars(tape, t1, qpos)
+        z3 = engine.attention(tape, q2, mem_pos, mem, (Wc.rows(0, d), bc.rows(0, d)), (Wc.rows(d, 2 * d), bc.rows(d, 2 * d)),
+                              (Wc.rows(2 * d, 3 * d), bc.rows(2 * d, 3 * d)), ps[lp + "cross_attn_image.out_proj.weight"],
+                              ps[lp + "cross_attn_image.out_proj.bias"], t1, key_pad, B, Q, S, H)
+        t3 = engine.layernorm(tape, z3, ps[lp + "norm3.weight"], ps[lp + "norm3.bias"], 1e-5)
+        z4 = engine.linear_chain(tape, t3, [(ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], k.ACT_RELU, True),
+                                            (ps[lp + "linear2.weight"], ps[lp + "linear2.bias"], k.ACT_NONE, False)],
+                                 res=t3, final_drop=True)
+        tgt = engine.layernorm(tape, z4, ps[lp + "norm4.weight"], ps[lp + "norm4.bias"], 1e-5)
+        inter.append(engine.layernorm(tape, tgt, ps["norm.weight"], ps["norm.bias"], 1e-5, y=stack[i]))
+    hs = engine.Var(stack)
+
+    def split_bwd():
+        g = hs.take_grad()
+        if g is None:
+            return
+        for i, v in enumerate(inter):
+            v.grad = g[i]
+
+    tape.record(split_bwd)
+    return [hs], None
+
+
 # ------------------------------------------------------------------------------------------ the module
 class Transformer(nn.Module):
     def __init__(self, args=None, d_model=512, nhead=8, num_encoder_layers=6, num_decoder_layers=6, dim_feedforward=2048,
@@ -395,41 +467,9 @@ class Transformer(nn.Module):
         named = engine.named_cache(self, "encoder", lambda: OrderedDict(self.encoder.named_parameters()))
         n_layers = self.encoder.num_layers
 
-        def prog_fused(tape, ps, x):
-            # q = k = src + pos, v = src (transformer.py:293-297): the packed in_proj runs as one launch on both inputs; `src + pos` of
-            # layer i + 1 is a second output of layer i's last LayerNorm
-            xe = torch.empty_like(x.data)
-            k.add(x.data, pos, xe, b_period=pos.numel())
-            for i in range(n_layers):
-                lp = f"layers.{i}."
-                z = engine.self_attention_block(tape, x, xe, ps[lp + "self_attn.in_proj_weight"], ps[lp + "self_attn.in_proj_bias"],
-                                                ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"], key_pad, B, S, H)
-                x1 = engine.layernorm(tape, z, ps[lp + "norm1.weight"], ps[lp + "norm1.bias"], 1e-5)
-                z2 = engine.linear_chain(tape, x1, [(ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], k.ACT_RELU, True),
-                                                    (ps[lp + "linear2.weight"], ps[lp + "linear2.bias"], k.ACT_NONE, False)],
-                                         res=x1, final_drop=True)
-                x = engine.layernorm(tape, z2, ps[lp + "norm2.weight"], ps[lp + "norm2.bias"], 1e-5, add=pos if i + 1 < n_layers else None)
-                xe = x.plus
-            return [x], None
-
-        def prog(tape, ps, x):
-            if tlayer.supported(d, H, S):      # row-complete sub-layer kernels: LayerNorm fused into the GEMM that feeds it, both directions
-                return tlayer.encoder_program(tape, ps, x, pos, key_pad, B, S, H, n_layers)
-            if engine.FUSED_BLOCKS and d // H == 32 and S <= 480:
-                return prog_fused(tape, ps, x)
-            for i in range(n_layers):
-                lp = f"layers.{i}."
-                Wi, bi = ps[lp + "self_attn.in_proj_weight"], ps[lp + "self_attn.in_proj_bias"]
-                qk = engine.add_const(tape, x, pos)
-                z = engine.attention(tape, qk, qk, x, None, None, (Wi.rows(2 * d, 3 * d), bi.rows(2 * d, 3 * d)),
-                                     ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"], x, key_pad, B, S, S, H,
-                                     packed_qk=(Wi.rows(0, 2 * d), bi.rows(0, 2 * d)))
-                x1 = engine.layernorm(tape, z, ps[lp + "norm1.weight"], ps[lp + "norm1.bias"], 1e-5)
-                z2 = engine.linear_chain(tape, x1, [(ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], k.ACT_RELU, True),
-                                                    (ps[lp + "linear2.weight"], ps[lp + "linear2.bias"], k.ACT_NONE, False)],
-                                         res=x1, final_drop=True)
-                x = engine.layernorm(tape, z2, ps[lp + "norm2.weight"], ps[lp + "norm2.bias"], 1e-5)
-            return [x], None
+        def prog(tape, ps, x):      # tlayer: row-complete sub-layer kernels, LayerNorm fused into the GEMM that feeds it, both directions
+            program = tlayer.encoder_program if tlayer.supported(d, H, S) else per_op_encoder_program
+            return program(tape, ps, x, pos, key_pad, B, S, H, n_layers)
 
         (out,) = functions.run_program(prog, named, [tokens], cache=self._cache_enc, training=self.training, drop_p=self.dropout,
                                        seed=self._next_seed(), group_wgrads=True, store_once=lambda n, t: t.dim() == 2)
@@ -442,127 +482,10 @@ class Transformer(nn.Module):
         Q = query_embed.shape[0]
         named = engine.named_cache(self, "decoder", lambda: OrderedDict(self.decoder.named_parameters()))
         n_layers = self.decoder.num_layers
-        dev = memory.device
-
-        def prog_fused(tape, ps, mem, qe):
-            """Decoder with (a) the packed in_proj of every self-attention as one launch on (tgt + query_pos | tgt), (b) the K / V projections of
-            memory (+ pos) for all layers as ONE grouped launch up front and one dgrad at the end, (c) tgt + query_pos emitted by the
-            LayerNorm that produces tgt, (d) the shared final LayerNorm applied to all layer outputs in one launch, (e) the gradient
-            w.r.t. query_pos formed once: every block leaves its dq / dk in a column slice of one buffer that is multiplied by the stacked
-            projection weights at the end (transformer.py:362-408, 255-262)."""
-            qpos_data = qe.data.to(BF16).unsqueeze(0).expand(B, Q, d).reshape(B * Q, d).contiguous()
-            L = n_layers
-            need = qe.needs_grad or mem.needs_grad or ps["layers.0.self_attn.in_proj_weight"].g is not None
-            sink = torch.empty(B * Q, L * 4 * d, dtype=BF16, device=dev) if need else None    # per layer [dq_s | dk_s | dv_s | dq_c]
-            Wself = [(ps[f"layers.{i}.self_attn.in_proj_weight"], ps[f"layers.{i}.self_attn.in_proj_bias"]) for i in range(L)]
-            Wcross = [(ps[f"layers.{i}.cross_attn_image.in_proj_weight"], ps[f"layers.{i}.cross_attn_image.in_proj_bias"]) for i in range(L)]
-
-            def qpos_bwd():     # recorded first: runs after every layer has written its slice of `sink`
-                if not qe.needs_grad or sink is None:
-                    return
-                zero = torch.zeros(d, d, dtype=BF16, device=dev)
-                wst = torch.cat([t for i in range(L) for t in (Wself[i][0].w[:2 * d], zero, Wcross[i][0].w[:d])], dim=0)     # [L*4d, d]
-                gq = engine.ops.linear_dgrad(sink, wst).view(B, Q, d).float().sum(0)
-                qe.grad = gq if qe.grad is None else qe.grad + gq
-
-            tape.record(qpos_bwd)
-            mem_e = torch.empty_like(mem.data)
-            k.add(mem.data, pos, mem_e, b_period=pos.numel())
-            kv, dkv = engine.cross_kv_projections(tape, mem, mem_e, Wcross)
-            tgt = engine.Var(torch.zeros(B * Q, d, dtype=BF16, device=dev), needs_grad=False)
-            tgt_e = qpos_data
-            tgt_stack = torch.empty(L, B * Q, d, dtype=BF16, device=dev)
-            layer_out = []
-            for i in range(L):
-                lp = f"layers.{i}."
-                Ws, bs = Wself[i]
-                Wc, bc = Wcross[i]
-                z1 = engine.self_attention_block(tape, tgt, tgt_e, Ws, bs, ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"],
-                                                 None, B, Q, H, e_sink=(sink, i * 4 * d) if sink is not None else None)
-                t1 = engine.layernorm(tape, z1, ps[lp + "norm1.weight"], ps[lp + "norm1.bias"], 1e-5, add=qpos_data)
-                z3 = engine.cross_attention_block(tape, t1, t1.plus, Wc.rows(0, d), bc.rows(0, d), kv, dkv, i * 2 * d,
-                                                  ps[lp + "cross_attn_image.out_proj.weight"], ps[lp + "cross_attn_image.out_proj.bias"], key_pad, B, Q, S, H,
-                                                  e_sink=(sink, i * 4 * d + 3 * d) if sink is not None else None)
-                t3 = engine.layernorm(tape, z3, ps[lp + "norm3.weight"], ps[lp + "norm3.bias"], 1e-5)
-                z4 = engine.linear_chain(tape, t3, [(ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], k.ACT_RELU, True),
-                                                    (ps[lp + "linear2.weight"], ps[lp + "linear2.bias"], k.ACT_NONE, False)],
-                                         res=t3, final_drop=True)
-                tgt = engine.layernorm(tape, z4, ps[lp + "norm4.weight"], ps[lp + "norm4.bias"], 1e-5, y=tgt_stack[i],
-                                       add=qpos_data if i + 1 < L else None)
-                tgt_e = tgt.plus
-                layer_out.append(tgt)
-            allv = engine.Var(tgt_stack.view(L * B * Q, d))
-
-            def split_bwd():    # gradient of the shared final norm -> the layer outputs (before the layers' own backward steps run)
-                g = allv.take_grad()
-                if g is None:
-                    return
-                g = g.view(L, B * Q, d)
-                for i, v in enumerate(layer_out):
-                    engine.accumulate(v, g[i])
-
-            tape.record(split_bwd)
-            stack = torch.empty(L, B * Q, d, dtype=BF16, device=dev)
-            hs_flat = engine.layernorm(tape, allv, ps["norm.weight"], ps["norm.bias"], 1e-5, y=stack.view(L * B * Q, d))
-            hs = engine.Var(stack)
-
-            def hs_bwd():
-                g = hs.take_grad()
-                if g is not None:
-                    hs_flat.grad = g.reshape(L * B * Q, d)
-
-            tape.record(hs_bwd)
-            return [hs], None
 
         def prog(tape, ps, mem, qe):
-            if tlayer.supported(d, H, max(S, Q)):
-                return tlayer.decoder_program(tape, ps, mem, qe, pos, key_pad, B, S, Q, H, n_layers)
-            if engine.FUSED_BLOCKS and d // H == 32 and S <= 480 and Q <= 480:
-                return prog_fused(tape, ps, mem, qe)
-            qpos_data = qe.data.to(BF16).unsqueeze(0).expand(B, Q, d).reshape(B * Q, d).contiguous()
-            qpos = engine.Var(qpos_data, needs_grad=qe.needs_grad)
-
-            def qpos_bwd():
-                g = qpos.take_grad()
-                if g is not None and qe.needs_grad:
-                    gq = g.view(B, Q, d).float().sum(0)
-                    qe.grad = gq if qe.grad is None else qe.grad + gq
-
-            tape.record(qpos_bwd)
-            mem_pos = engine.add_const(tape, mem, pos)
-            tgt = engine.Var(torch.zeros(B * Q, d, dtype=BF16, device=dev), needs_grad=False)
-            stack = torch.empty(n_layers, B * Q, d, dtype=BF16, device=dev)
-            inter = []
-            for i in range(n_layers):
-                lp = f"layers.{i}."
-                Ws, bs = ps[lp + "self_attn.in_proj_weight"], ps[lp + "self_attn.in_proj_bias"]
-                Wc, bc = ps[lp + "cross_attn_image.in_proj_weight"], ps[lp + "cross_attn_image.in_proj_bias"]
-                qk = engine.add_vars(tape, tgt, qpos)
-                z1 = engine.attention(tape, qk, qk, tgt, None, None, (Ws.rows(2 * d, 3 * d), bs.rows(2 * d, 3 * d)),
-                                      ps[lp + "self_attn.out_proj.weight"], ps[lp + "self_attn.out_proj.bias"], tgt, None, B, Q, Q, H,
-                                      packed_qk=(Ws.rows(0, 2 * d), bs.rows(0, 2 * d)))
-                t1 = engine.layernorm(tape, z1, ps[lp + "norm1.weight"], ps[lp + "norm1.bias"], 1e-5)
-                q2 = engine.add_vars(tape, t1, qpos)
-                z3 = engine.attention(tape, q2, mem_pos, mem, (Wc.rows(0, d), bc.rows(0, d)), (Wc.rows(d, 2 * d), bc.rows(d, 2 * d)),
-                                      (Wc.rows(2 * d, 3 * d), bc.rows(2 * d, 3 * d)), ps[lp + "cross_attn_image.out_proj.weight"],
-                                      ps[lp + "cross_attn_image.out_proj.bias"], t1, key_pad, B, Q, S, H)
-                t3 = engine.layernorm(tape, z3, ps[lp + "norm3.weight"], ps[lp + "norm3.bias"], 1e-5)
-                z4 = engine.linear_chain(tape, t3, [(ps[lp + "linear1.weight"], ps[lp + "linear1.bias"], k.ACT_RELU, True),
-                                                    (ps[lp + "linear2.weight"], ps[lp + "linear2.bias"], k.ACT_NONE, False)],
-                                         res=t3, final_drop=True)
-                tgt = engine.layernorm(tape, z4, ps[lp + "norm4.weight"], ps[lp + "norm4.bias"], 1e-5)
-                inter.append(engine.layernorm(tape, tgt, ps["norm.weight"], ps["norm.bias"], 1e-5, y=stack[i]))
-            hs = engine.Var(stack)
-
-            def split_bwd():
-                g = hs.take_grad()
-                if g is None:
-                    return
-                for i, v in enumerate(inter):
-                    v.grad = g[i]
-
-            tape.record(split_bwd)
-            return [hs], None
+            program = tlayer.decoder_program if tlayer.supported(d, H, max(S, Q)) else per_op_decoder_program
+            return program(tape, ps, mem, qe, pos, key_pad, B, S, Q, H, n_layers)
 
         def run():
             (o,) = functions.run_program(prog, named, [memory, query_embed], cache=self._cache_dec, training=self.training,

@@ -1,16 +1,16 @@
 """MFMA utilisation of the encoder-decoder attention at batch 8 (BASELINE.json north_star target), measured on the product code
-path of round 2: the fused attention blocks of toist_amd.engine (packed in_proj as one launch on two inputs, flash-style core with
-row statistics only, out-proj + dropout + residual, grouped decoder K / V projections, merged data gradients; forward + backward,
-dropout 0.1) captured in a hipGraph and replayed.  GPU only.
+path (packed in_proj as one launch on two inputs, flash-style core with row statistics only, grouped decoder K / V projections;
+forward + backward, dropout 0.1) captured in a hipGraph and replayed.  GPU only.
 
 FLOP accounting: cores 4*Sq*Sk*d, projections 2*(2*Sq + 2*Sk)*d*d per image, x3 for forward + backward.
 Next to every case: the number of kernel launches of the replayed graph, the time the same number of EMPTY launches takes
 (the launch-latency floor of this launch count) and the utilisation that floor alone would allow.
 
-Round 4: the default path is the product path of toist_amd.tlayer -- attn2 cores (csrc/attn2.hip), out_proj + dropout + residual +
-LayerNorm as one row-complete launch, and in the backward pass [in_proj data gradient + fold of the key-split dQ shares + residual
-gradient + LayerNorm backward] as one launch (csrc/tlayer.hip).  A block here therefore ALSO contains one LayerNorm forward and one
-LayerNorm backward that the round-3 block (`--v1`: toist_amd.engine blocks) left to separate launches."""
+The path is the product path of toist_amd.tlayer -- attn2 cores (csrc/attn2.hip), out_proj + dropout + residual + LayerNorm as one
+row-complete launch, and in the backward pass [in_proj data gradient + fold of the key-split dQ shares + residual gradient +
+LayerNorm backward] as one launch (csrc/tlayer.hip).  A block here therefore ALSO contains one LayerNorm forward and one LayerNorm
+backward; the round-3 blocks of toist_amd.engine, which left those to separate launches, are gone (their numbers:
+profiles/r02_attention_utilisation.json, r03_attention_utilisation.json)."""
 import json
 import os
 import sys
@@ -22,7 +22,6 @@ from toist_amd import engine, kernels as k  # noqa: E402
 
 dev = torch.device("cuda")
 BF = torch.bfloat16
-V1 = "--v1" in sys.argv
 B, d, H, L = 8, 256, 8, 6
 PEAK = 2500.0
 
@@ -107,27 +106,7 @@ def run(name, Sq, Sk, kind):
     pos = torch.randn(B * Sk, d, device=dev).to(BF)
 
     def step():
-        tape = engine.Tape(training=True, drop_p=float(os.environ.get("TOIST_BENCH_ATTN_DROP", "0.1")), seed=1, group_wgrads=True)
-        outs = []
-        if kind == "cross":
-            m = engine.Var(mem)
-            mem_e = torch.empty_like(mem)
-            k.add(mem, pos, mem_e)
-            kv, dkv = engine.cross_kv_projections(tape, m, mem_e, [(p[0], p[1]) for p in P])
-        for i, (Wi, bi, Wo, bo) in enumerate(P):          # six independent blocks (one per layer), as a step runs them
-            xv = engine.Var(x)
-            xe = torch.empty_like(x)
-            k.add(x, e, xe)                                 # stands for the LayerNorm that emits x + pos in the model
-            if kind == "cross":
-                o = engine.cross_attention_block(tape, xv, xe, Wi.rows(0, d), bi.rows(0, d), kv, dkv, i * 2 * d, Wo, bo, key_pad, B, Sq, Sk, H)
-            else:
-                o = engine.self_attention_block(tape, xv, xe, Wi, bi, Wo, bo, key_pad if kind == "enc" else None, B, Sq, H)
-            o.grad = torch.ones_like(o.data)
-            outs.append(o)
-        tape.backward()
-
-    def step2():
-        """the same blocks on toist_amd.tlayer's kernels: [q|k|v GEMM] [attn2 forward] [out_proj + dropout + residual + LayerNorm] forward;
+        """six independent blocks (one per layer), as a step runs them, on toist_amd.tlayer's kernels: [q|k|v GEMM] [attn2 forward] [out_proj + dropout + residual + LayerNorm] forward;
         [out_proj dgrad] [attn2 backward] [in_proj dgrad + dQ fold + residual gradient + LayerNorm backward] + grouped weight gradients"""
         from toist_amd import ops, tlayer
         tape = engine.Tape(training=True, drop_p=float(os.environ.get("TOIST_BENCH_ATTN_DROP", "0.1")), seed=1, group_wgrads=True)
@@ -149,7 +128,7 @@ def run(name, Sq, Sk, kind):
                 qkv = tlayer._qkv(xe, x, Wi, bi, M, d)
                 qb, kb, vb = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
             ctx = torch.empty(M, d, dtype=BF, device=dev)
-            core = tlayer._core(tape, qb, kb, vb, key_pad if kind != "dec" else None, B, Sq, Sk, H, ctx, p, tape.next_seed())
+            core = engine.flash_core(qb, kb, vb, key_pad if kind != "dec" else None, B, Sq, Sk, H, ctx, p, tape.next_seed())
             ln = tlayer._ln_fwd(ctx, Wo, bo, x, LN[i][0], LN[i][1], tape)
             saved.append((xe, ctx, core, ln, Wi, bi, Wo, bo))
         prev = None
@@ -174,12 +153,10 @@ def run(name, Sq, Sk, kind):
             prev = ln
         tape.backward()
 
-    if not V1:
-        # one LayerNorm per block, as in the model (shared parameters would force a fold of the d gamma / d beta partials per block)
-        LN = [(engine.ParamView(None, torch.zeros(d, device=dev), torch.ones(d, device=dev)), engine.ParamView(None, torch.zeros(d, device=dev), torch.zeros(d, device=dev)))
-              for _ in range(L)]
-        ones = torch.ones(B * Sq, d, device=dev).to(BF)
-        step = step2
+    # one LayerNorm per block, as in the model (shared parameters would force a fold of the d gamma / d beta partials per block)
+    LN = [(engine.ParamView(None, torch.zeros(d, device=dev), torch.ones(d, device=dev)), engine.ParamView(None, torch.zeros(d, device=dev), torch.zeros(d, device=dev)))
+          for _ in range(L)]
+    ones = torch.ones(B * Sq, d, device=dev).to(BF)
     with Counter() as c:
         step()
     launches = c.n
@@ -195,7 +172,7 @@ rows = [run("encoder self-attention (S=416)", 416, 416, "enc"), run("decoder cro
         run("decoder self-attention (Q=100)", 100, 100, "dec")]
 tot_us = 6 * sum(r["us_fwd_bwd"] for r in rows)
 tot_fl = 6 * sum(r["gflop"] for r in rows)
-print(json.dumps({"batch": B, "layers": "6+6", "dropout": 0.1, "launch": "hipGraph replay", "path": "engine.self_attention_block / cross_attention_block / cross_kv_projections (round-3 blocks)" if V1 else
+print(json.dumps({"batch": B, "layers": "6+6", "dropout": 0.1, "launch": "hipGraph replay", "path":
                   "toist_amd.tlayer: attn2 cores + row-complete out_proj / in_proj-dgrad launches (each block also holds one LayerNorm forward + backward)",
                   "cases": rows, "all_attention_per_step": {"ms": round(tot_us / 1e3, 3), "tflops": round(tot_fl / tot_us * 1e3, 1),
                                                             "mfma_frac": round(tot_fl / tot_us * 1e3 / PEAK, 4)}}, indent=1))

@@ -615,6 +615,30 @@ TOIST_API int toist_kmeans(const float* banks, int64_t bank_stride, float* cente
                  const int32_t* group_off, const int32_t* members, int n_groups, const float* features, int N, int D, int K, float tol,
                  int max_iter, int32_t* pick, float* chosen_center, int32_t* iters, void* stream);
 
+/* ---- toist_kmeans with a start decided on the device (models/kmeans.py:8-18, `initialize`, and the `full_label == 0` test of kmeans.py:55-58):
+ * the same Lloyd body.  full_label f32 [T] is the criterion's buffer, init_rows i32 [*, K] holds, per SAMPLE, the bank rows the host drew with
+ * np.random.choice(N, K, replace=False) or -1.  Before a member's iterations: full_label[task] == 0 and init_rows[sample][0] >= 0 -> the centres are
+ * those K rows of banks[task] (every member restarts from its own rows; same-task members stay in batch order); full_label[task] != 0 and a negative
+ * row -> toist_kmeans' behaviour; the two disagree (or a row lies outside [0, N)) -> toist_kmeans' behaviour and bit 0 is OR-ed into *status (i32,
+ * never cleared here).  Nothing in the launch arguments depends on the batch or on the fill state: the launch can be captured. */
+TOIST_API int toist_kmeans_init(const float* banks, int64_t bank_stride, float* centers, int64_t centers_stride, const int32_t* group_task,
+                 const int32_t* group_off, const int32_t* members, int n_groups, const float* features, int N, int D, int K, float tol,
+                 int max_iter, int32_t* pick, float* chosen_center, int32_t* iters, const float* full_label, const int32_t* init_rows,
+                 int32_t* status, void* stream);
+
+/* ---- FIFO update of the memory banks with its bookkeeping on the device (mdetr.py:85-97; update_count / full_label: mdetr.py:90-92).  Group g =
+ * the n = group_off[g+1] - group_off[g] samples members[group_off[g] ..) of task t = group_task[g] (n_groups slots, n_groups <= B <= N), rows f32
+ * [B, D] the new features by sample.  With label = full_label[t] as the launch finds it:
+ *   label == 0 or fifo_when_full:  banks[t][:N-n] = banks[t][n:], banks[t][N-n:] = the group's rows in batch order, lsap_rows[g] = 0; and when
+ *                                  label == 0: full_label[t] = 1 if update_count[t] > N (looked at BEFORE the add), then update_count[t] += n;
+ *   otherwise:                     the bank stays, lsap_rows[g] = n (the nearest-replacement LSAP behind this launch takes the group);
+ *   an unused slot (n == 0):       lsap_rows[g] = 0.
+ * One workgroup owns a task's bank and counters; the overlapping move is ordered inside it (loads of a chunk, barrier, stores).  No host value in
+ * the launch arguments: the launch can be captured. */
+TOIST_API int toist_bank_fifo(float* banks, int64_t bank_stride, float* update_count, float* full_label, const int32_t* group_task,
+                 const int32_t* group_off, const int32_t* members, int n_groups, const float* rows, int T, int B, int N, int D,
+                 int fifo_when_full, int32_t* lsap_rows, void* stream);
+
 /* ---- whole-head self-attention for short sequences (S <= 64 keys, head dim <= 64, % 8 == 0): the text encoder's attention
  * (RoBERTa over a 16-token caption: transformer.py:129-130 via transformers.RobertaSelfAttention) as ONE launch each way instead of
  * batched 16 x 16 GEMMs + softmax kernels.  q / k / v / ctx / gradients are per-head column slices of [B*S, ld*] bf16 buffers

@@ -448,8 +448,16 @@ class CapturedDistillStep(_CapturedStep):
     step(batch) with batch = what util/misc.collate_fn delivers for (noun, pronoun) pairs (harness.synthetic_distill_batch): dict(samples=[..] * 2,
     tokenized=[..] * 2 (BatchEncodings with char_to_token), targets=[..] * 2, captions=[..] * 2, positive_map=[..] * 2) -> total loss (device scalar).
     The first step runs eagerly (a real training step) and is captured right after; later steps = the H2D copies of the inputs + one graph launch.
-    Requirements (checked): one process, every memory bank full, nearest-replacement bank updates, both sides with the same number of targets per
-    image (the reference's pairs share their boxes), images / captions of the constructor's shape.
+    Requirements (checked): one process, a batch no larger than a memory bank, both sides with the same number of targets per image (the reference's
+    pairs share their boxes), images / captions of the constructor's shape.
+
+    The memory state is the device's business: the same graph serves a fresh run (every bank filling, FIFO pushes, k-means from randomly drawn bank
+    rows), the step on which a task's full_label flips, the steady state (nearest replacement, k-means from the stored centres) and --fifo_memory.
+    toist_bank_fifo reads update_count / full_label and decides per task; toist_kmeans_init reads full_label and decides per sample.  The host's only
+    part is ClusterCriterion.plan_fill in step(): it advances the host mirror of the two counters and spends the np.random.choice draws the reference
+    would spend, in its order, into a distill.FillTables image (so np.random.seed pins a run as it pins the reference's).  pack() stays stateless.
+    After writing update_count / full_label directly, or loading a checkpoint, ClusterCriterion.sync_host_state() (load_state_dict calls it) re-reads
+    the mirror; a disagreement between mirror and device raises at a later step (ClusterCriterion.check_start_status).
 
     A bad step is handled as in CapturedTrainStep: fatal for both models' training state unless BOTH optimizers were built with skip_nonfinite=True;
     then the step is skipped on the device and resolve_skipped() reports it (the loss word and the decoder status word are shared by the two tails, so
@@ -460,7 +468,7 @@ class CapturedDistillStep(_CapturedStep):
         """stream: the HIP stream the steps run (and the graph is captured) on; pass the stream earlier eager steps of the same models ran on, if any -- the programs'
         reused gradient buffers and the launchers' per-stream scratch must not change streams between eager steps and the capture."""
         from . import engine
-        from .distill import DistillTables
+        from .distill import DistillTables, FillTables
         from .matcher import StaticTargets
         self.model, self.model_noun, self.criterion, self.cluster_criterion = model, model_noun, criterion, cluster_criterion
         self.optimizers, self.weight_dict = list(optimizers), weight_dict
@@ -475,6 +483,10 @@ class CapturedDistillStep(_CapturedStep):
             st.distill = DistillTables(self.B, self.L, dev, pronoun_side=pronoun)
             # (every batch has exactly this shape and overwrites the whole mask)
             self.sides.append({**static_inputs(self.B, *self.hw, self.L, _pad_id(model), dev, mask_fill=False), "targets": st})
+        self.fill = None                                   # (without a cluster criterion there is no memory to fill)
+        if cluster_criterion is not None:
+            self.fill = FillTables(self.B, cluster_criterion.cluster_num, cluster_criterion.memory_size, dev)
+            self.fill.attach(self.sides[0]["targets"].distill, self.sides[1]["targets"].distill)
         self._init_capture_state(side=stream if stream is not None else torch.cuda.Stream(device=dev))
         self._ent = self._buckets[(*self.hw, self.L)] = dict(_NO_GRAPH)        # the one bucket
         if kernels.SEED_DEV is None:
@@ -499,11 +511,21 @@ class CapturedDistillStep(_CapturedStep):
                         "tables": side["targets"].distill.pack(tok, host_t, batch["captions"][i])})
         return out
 
-    def _fill(self, packed):
+    def _plan(self, packed):
+        """The stateful host half of a step, once per step and in step order: the k-means starts of the samples whose bank is filling
+        (ClusterCriterion.plan_fill on the task columns of the packed tables)."""
+        if self.fill is None:
+            return None
+        tasks = [side["targets"].distill._views(pk["tables"])[4].tolist() for side, pk in zip(self.sides, packed)]
+        return self.cluster_criterion.plan_fill(*tasks)
+
+    def _fill(self, packed, starts):
         for side, pk in zip(self.sides, packed):
             upload(side, pk["samples"], pk["tok"])
             side["targets"].load_packed(pk["targets"])
             side["targets"].distill.load_packed(pk["tables"])
+        if starts is not None:
+            self.fill.load(*starts)
 
     def _fwd_bwd_opt(self):
         """One step.  The backward pass is issued in TWO calls -- the teacher's total (the noun_ keys) first, then everything else (sth_, softkd, nsthl2, cluster:
@@ -547,13 +569,19 @@ class CapturedDistillStep(_CapturedStep):
             raise RuntimeError("CapturedDistillStep is single-process (the memory-bank queue all_gathers rows across ranks: collectives are not captured)")
         self._void_graphs()
         ent = self._ent
+        starts = self._plan(batch)
         if ent["graph"] is None:
-            return self._eager_then_capture(ent, self._fwd_bwd_opt, reset=self._zero_grad, upload=lambda: self._fill(batch))
+            out = self._eager_then_capture(ent, self._fwd_bwd_opt, reset=self._zero_grad, upload=lambda: self._fill(batch, starts))
+            if self.fill is not None:
+                self.cluster_criterion.check_start_status(defer=True)
+            return out
         side = self._side                                  # (unlike the bucketed steps, upload and replay stay on the stream of the capture)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            self._fill(batch)
+            self._fill(batch, starts)
             ent["graph"].replay()
+            if self.fill is not None:
+                self.cluster_criterion.check_start_status(defer=True)
         torch.cuda.current_stream().wait_stream(side)
         self.replays += 1
         for o in self.optimizers:

@@ -7,17 +7,29 @@
 // workgroup -- one workgroup per distinct task of the batch, walking that task's samples in batch order so that a later sample
 // starts from the centres the earlier one left, exactly like the sequential reference -- and the host never looks.
 // Work per iteration: two passes over the 1 MB bank (L2-resident) = ~20 us on one CU; neither roofline applies to 1-8 workgroups.
+//
+// The same file holds what lets ONE captured graph serve a run from its first step: the start of models/kmeans.py:8-18 while a bank fills (the host
+// draws the rows, the device's own full_label decides whether they are used: toist_kmeans_init) and the FIFO branch of the bank update with its
+// update_count / full_label bookkeeping (mdetr.py:85-97: toist_bank_fifo), next to the masked row scatter of the nearest-replacement branch.
 #include "common.h"
 
 namespace toist {
 
 constexpr int KM_THREADS = 1024, KM_MAXK = 8, KM_MAXD = 256;
 
-__global__ __launch_bounds__(KM_THREADS) void kmeans_kernel(const float* __restrict__ banks, long long bank_stride, float* __restrict__ centers_all,
-                                                            long long centers_stride, const int* __restrict__ group_task,
-                                                            const int* __restrict__ group_off, const int* __restrict__ members,
-                                                            const float* __restrict__ features, int N, int D, int K, float tol, int max_iter,
-                                                            int* __restrict__ pick_out, float* __restrict__ center_out, int* __restrict__ iters_out) {
+constexpr int KM_START_MISMATCH = 1;   // status bit: full_label[task] and init_rows[sample] disagree about the start (toist_kmeans_init)
+
+// The Lloyd body of both entry points.  START = false: every member starts from the centres in LDS (the stored ones, or what the previous member of
+// the same task left).  START = true: the device's own full_label[task] decides -- 0 and init_rows[sample][0] >= 0: the centres are the bank rows
+// init_rows[sample][0..K) (models/kmeans.py:8-18 with the host's np.random.choice draw), for every member anew; 1 and a negative row: as START =
+// false; anything else: as START = false, and KM_START_MISMATCH is set in *status.
+template <bool START>
+__device__ __forceinline__ void kmeans_body(const float* __restrict__ banks, long long bank_stride, float* __restrict__ centers_all,
+                                            long long centers_stride, const int* __restrict__ group_task,
+                                            const int* __restrict__ group_off, const int* __restrict__ members,
+                                            const float* __restrict__ features, int N, int D, int K, float tol, int max_iter,
+                                            int* __restrict__ pick_out, float* __restrict__ center_out, int* __restrict__ iters_out,
+                                            const float* __restrict__ full_label, const int* __restrict__ init_rows, int* __restrict__ status) {
     __shared__ float c[KM_MAXK][KM_MAXD];            // current centres
     __shared__ float part[4][KM_MAXK][KM_MAXD];      // per-quarter member sums
     __shared__ int cnt_part[4][KM_MAXK];
@@ -33,6 +45,18 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_kernel(const float* __restr
     const int d_of = tid & 255, quarter = tid >> 8;  // update pass: thread = (feature, quarter of the points); needs D <= 256
     for (int mi = group_off[g]; mi < group_off[g + 1]; ++mi) {
         const int sample = members[mi];
+        if constexpr (START) {
+            const int* row = init_rows + (long long)sample * K;
+            const bool filling = full_label[task] == 0.f, drawn = row[0] >= 0;
+            bool use = filling && drawn;
+            for (int kk = 0; kk < K; ++kk) use = use && row[kk] >= 0 && row[kk] < N;     // (a row outside the bank is a mismatch too, never an address)
+            if (use) {
+                for (int i = tid; i < K * D; i += KM_THREADS) c[i / D][i % D] = X[(long long)row[i / D] * D + i % D];
+                __syncthreads();
+            } else if (filling || drawn) {
+                if (tid == 0) atomicOr(status, KM_START_MISMATCH);
+            }
+        }
         int it = 0;
         for (; it < max_iter; ++it) {
             // ---- assignment: one wavefront per point, lanes across the features ----
@@ -126,6 +150,85 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_kernel(const float* __restr
     }
 }
 
+__global__ __launch_bounds__(KM_THREADS) void kmeans_kernel(const float* __restrict__ banks, long long bank_stride, float* __restrict__ centers_all,
+                                                            long long centers_stride, const int* __restrict__ group_task,
+                                                            const int* __restrict__ group_off, const int* __restrict__ members,
+                                                            const float* __restrict__ features, int N, int D, int K, float tol, int max_iter,
+                                                            int* __restrict__ pick_out, float* __restrict__ center_out, int* __restrict__ iters_out) {
+    kmeans_body<false>(banks, bank_stride, centers_all, centers_stride, group_task, group_off, members, features, N, D, K, tol, max_iter, pick_out, center_out,
+                       iters_out, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(KM_THREADS) void kmeans_init_kernel(const float* __restrict__ banks, long long bank_stride, float* __restrict__ centers_all,
+                                                                 long long centers_stride, const int* __restrict__ group_task,
+                                                                 const int* __restrict__ group_off, const int* __restrict__ members,
+                                                                 const float* __restrict__ features, int N, int D, int K, float tol, int max_iter,
+                                                                 int* __restrict__ pick_out, float* __restrict__ center_out, int* __restrict__ iters_out,
+                                                                 const float* __restrict__ full_label, const int* __restrict__ init_rows,
+                                                                 int* __restrict__ status) {
+    kmeans_body<true>(banks, bank_stride, centers_all, centers_stride, group_task, group_off, members, features, N, D, K, tol, max_iter, pick_out, center_out,
+                      iters_out, full_label, init_rows, status);
+}
+
+// ---- FIFO update of the memory banks (mdetr.py:85-97) with its bookkeeping (mdetr.py:90-92), decided on the device ---------------------------------
+// One workgroup per group slot; a group is all images of one task, so the workgroup owns that task's bank and its two counters for the launch.
+constexpr int FIFO_THREADS = 1024, FIFO_U = 4;
+
+// a[i] = a[i + shift] for i in [0, count), shift > 0: an overlapping move made safe by construction.  Chunks of FIFO_THREADS * FIFO_U elements in
+// ascending order; every load of a chunk is in registers before the barrier, its stores come after, and a later chunk only reads elements that no
+// earlier chunk has written (stores end below base + chunk, later loads start at base + chunk + shift).
+template <typename V>
+__device__ __forceinline__ void fifo_shift(V* a, long long shift, long long count, int tid) {
+    for (long long base = 0; base < count; base += (long long)FIFO_THREADS * FIFO_U) {
+        V v[FIFO_U];
+#pragma unroll
+        for (int u = 0; u < FIFO_U; ++u) {
+            const long long i = base + (long long)u * FIFO_THREADS + tid;
+            if (i < count) v[u] = a[i + shift];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < FIFO_U; ++u) {
+            const long long i = base + (long long)u * FIFO_THREADS + tid;
+            if (i < count) a[i] = v[u];
+        }
+    }
+}
+
+__global__ __launch_bounds__(FIFO_THREADS) void bank_fifo_kernel(float* banks, long long bank_stride, float* update_count, float* full_label,
+                                                                 const int* __restrict__ group_task, const int* __restrict__ group_off,
+                                                                 const int* __restrict__ members, const float* __restrict__ rows, int T, int B, int N,
+                                                                 int D, int fifo_when_full, int vec4, int* __restrict__ lsap_rows) {
+    const int tid = threadIdx.x, g = blockIdx.x;
+    const int off0 = group_off[g], n = group_off[g + 1] - off0, task = group_task[g];
+    if (n <= 0 || n > N || off0 < 0 || off0 + n > B || task < 0 || task >= T) {      // unused slot (or a table no host packer writes): nothing moves
+        if (tid == 0) lsap_rows[g] = 0;
+        return;
+    }
+    const float label = full_label[task], count = update_count[task];                // read once; written by one lane after the last barrier
+    const bool filling = label == 0.f;
+    if (!filling && !fifo_when_full) {                                               // nearest replacement: the LSAP launch behind this one takes the group
+        if (tid == 0) lsap_rows[g] = n;
+        return;
+    }
+    float* bank = banks + (long long)task * bank_stride;
+    const long long keep = (long long)(N - n) * D, shift = (long long)n * D;
+    if (vec4) fifo_shift(reinterpret_cast<float4*>(bank), shift / 4, keep / 4, tid);
+    else fifo_shift(bank, shift, keep, tid);
+    __syncthreads();                                                                 // every old row has been read: the tail may be overwritten
+    for (long long i = tid; i < shift; i += FIFO_THREADS) {
+        const int j = (int)(i / D), m = members[off0 + j];
+        if (m >= 0 && m < B) bank[keep + i] = rows[(long long)m * D + (i - (long long)j * D)];
+    }
+    if (tid == 0) {
+        lsap_rows[g] = 0;
+        if (filling) {                                                               // mdetr.py:90-92: the label looks at the count BEFORE the add
+            if (count > (float)N) full_label[task] = 1.f;
+            update_count[task] = count + (float)n;
+        }
+    }
+}
+
 // dst[dst_row[i]] = src[src_row[i]] for the rows i with dst_row[i] >= 0 and src_row[i] >= 0 (rows of `d` floats; distinct live destinations).
 // The memory-bank replacement of the distillation step under hipGraph replay: which slots are live is decided on the device (an LSAP pair table of
 // fixed capacity, its status word), so the write must skip the dead ones instead of sending them to a scratch row the bank does not have.
@@ -157,4 +260,30 @@ extern "C" int toist_scatter_rows_f32(const float* src, const int64_t* src_row, 
     TOIST_REQUIRE(src && src_row && dst && dst_row && m > 0 && d > 0, "toist_scatter_rows_f32: bad arguments");
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream, src, (const long long*)src_row, dst, (const long long*)dst_row, m, d);
     return check_launch("toist_scatter_rows_f32");
+}
+
+extern "C" int toist_kmeans_init(const float* banks, int64_t bank_stride, float* centers, int64_t centers_stride, const int32_t* group_task,
+                                 const int32_t* group_off, const int32_t* members, int n_groups, const float* features, int N, int D, int K, float tol,
+                                 int max_iter, int32_t* pick, float* chosen_center, int32_t* iters, const float* full_label, const int32_t* init_rows,
+                                 int32_t* status, void* stream) {
+    TOIST_REQUIRE(banks && centers && group_task && group_off && members && features && pick && chosen_center && full_label && init_rows && status &&
+                      n_groups > 0, "toist_kmeans_init: bad args");
+    TOIST_REQUIRE(N > 0 && N <= 32768 && D > 0 && D <= KM_MAXD && K > 0 && K <= KM_MAXK && K * D <= KM_THREADS && max_iter > 0 && tol >= 0.f,
+                  "toist_kmeans_init: N <= 32768, D <= %d, K <= %d, K * D <= %d (N=%d D=%d K=%d)", KM_MAXD, KM_MAXK, KM_THREADS, N, D, K);
+    hipLaunchKernelGGL(kmeans_init_kernel, dim3(n_groups), dim3(KM_THREADS), (size_t)((N + 15) & ~15), (hipStream_t)stream, banks, (long long)bank_stride,
+                       centers, (long long)centers_stride, group_task, group_off, members, features, N, D, K, tol, max_iter, pick, chosen_center, iters,
+                       full_label, init_rows, status);
+    return check_launch("toist_kmeans_init");
+}
+
+extern "C" int toist_bank_fifo(float* banks, int64_t bank_stride, float* update_count, float* full_label, const int32_t* group_task,
+                               const int32_t* group_off, const int32_t* members, int n_groups, const float* rows, int T, int B, int N, int D,
+                               int fifo_when_full, int32_t* lsap_rows, void* stream) {
+    TOIST_REQUIRE(banks && update_count && full_label && group_task && group_off && members && rows && lsap_rows, "toist_bank_fifo: bad args");
+    TOIST_REQUIRE(n_groups > 0 && T > 0 && B > 0 && N > 0 && D > 0 && n_groups <= B && B <= N && bank_stride >= (int64_t)N * D,
+                  "toist_bank_fifo: 0 < n_groups <= B <= N, bank_stride >= N * D (n_groups=%d B=%d N=%d D=%d)", n_groups, B, N, D);
+    const int vec4 = D % 4 == 0 && bank_stride % 4 == 0 && (uintptr_t)banks % 16 == 0;
+    hipLaunchKernelGGL(bank_fifo_kernel, dim3(n_groups), dim3(FIFO_THREADS), 0, (hipStream_t)stream, banks, (long long)bank_stride, update_count, full_label,
+                       group_task, group_off, members, rows, T, B, N, D, fifo_when_full, vec4, lsap_rows);
+    return check_launch("toist_bank_fifo");
 }

@@ -8,6 +8,7 @@ is a handful of device tensor ops per iteration ([1024, 256] bank, 3 centres), a
 Buffer names and shapes equal the reference's, so a reference checkpoint of the criterion loads unchanged.
 """
 import collections
+import copy
 
 import numpy as np
 import torch
@@ -130,7 +131,9 @@ class DistillTables:
       sub_sth  u8 [L, B]   tokens of 'something'
       task    i32 [B]      task index of the image (dataset_name), -1 = the image takes no part (teacher side: no boxes)
       group_task i32 [B] | group_off i32 [B + 1] | members i32 [B]    the images grouped by task, in batch order inside a group (csrc/kmeans.hip, the
-                           per-task LSAP of the memory-bank update); unused groups are empty (group_off stays at the member count)."""
+                           per-task LSAP of the memory-bank update); unused groups are empty (group_off stays at the member count).
+    What depends on the fill state of the banks rather than on the batch -- the k-means start rows -- is not packed here (pack() stays stateless): a
+    FillTables image attached to the two sides adds `init_rows` i32 [B, K]."""
 
     def __init__(self, batch, tokens, device, pronoun_side):
         self.B, self.L, self.pronoun_side = int(batch), int(tokens), bool(pronoun_side)
@@ -244,6 +247,48 @@ class DistillTables:
         return self
 
 
+class FillTables:
+    """Fixed-address device image of one step's k-means starts, the sibling of DistillTables for what is NOT a function of the batch alone: the bank rows
+    ClusterCriterion.plan_fill drew for the samples whose task is still filling (the draws depend on the fill state and on the np.random stream, so
+    they are made in step(), never in a loader's pack()).  One pinned staging arena, one asynchronous copy per step, no host sync.
+
+    Arena: init i32 [2, B, K] -- side (0 = noun / teacher, 1 = pronoun / student), sample, centre; -1 rows = start from the stored centres.
+    `attach(noun_tables, sth_tables)` hands each side's DistillTables its [B, K] view as `.init_rows`; _cluster_static reads it from there."""
+
+    def __init__(self, batch, cluster_num, memory_size, device):
+        self.B, self.K = int(batch), int(cluster_num)
+        if self.B > int(memory_size):
+            raise ValueError(f"a batch of {self.B} images does not fit a memory bank of {int(memory_size)} rows")
+        self.device = torch.device(device)
+        self._host = torch.full((2, self.B, self.K), -1, dtype=torch.int32)
+        if self.device.type == "cuda":
+            self._host = self._host.pin_memory()
+        self.init = torch.full((2, self.B, self.K), -1, dtype=torch.int32, device=self.device)
+        self._event = None
+
+    def attach(self, noun_tables, sth_tables):
+        noun_tables.init_rows, sth_tables.init_rows = self.init[0], self.init[1]
+        return self
+
+    def pack(self, init_noun, init_sth, out=None):
+        host = out if out is not None else torch.empty((2, self.B, self.K), dtype=torch.int32)
+        for side, rows in enumerate((init_noun, init_sth)):
+            rows = np.asarray(rows, dtype=np.int32)
+            if rows.shape != (self.B, self.K):
+                raise ValueError(f"FillTables holds {self.B} x {self.K} start rows per side; got {rows.shape}")
+            host[side].copy_(torch.from_numpy(rows))
+        return host
+
+    def load(self, init_noun, init_sth):
+        if self._event is not None:
+            self._event.synchronize()          # the previous upload has left the staging buffer
+        self.init.copy_(self.pack(init_noun, init_sth, out=self._host), non_blocking=True)
+        if self.device.type == "cuda":
+            self._event = torch.cuda.Event()
+            self._event.record()
+        return self
+
+
 # ---- k-means (kmeans.py) ---------------------------------------------------------------------------------------
 def _sq_dist(x, centers):
     return ((x.unsqueeze(1) - centers.unsqueeze(0)) ** 2.0).sum(-1)
@@ -251,7 +296,8 @@ def _sq_dist(x, centers):
 
 def kmeans(X, init_cluster_centers, num_clusters, tol=1e-4, full_label=0):
     """Lloyd iterations until (sum_k |shift_k|)^2 < tol (kmeans.py:21-94).  With full_label == 0 the start is
-    `np.random.choice` rows of X (kmeans.py:8-18: parity with the reference is only defined once the bank is full)."""
+    `np.random.choice` rows of X (kmeans.py:8-18), drawn from the global np.random stream exactly as the reference draws them: under the same
+    np.random.seed the fill phase equals the reference's step by step (tests/golden/distill_fill.npz)."""
     X = X.float()
     if full_label == 0:
         centers = X[torch.as_tensor(np.random.choice(len(X), num_clusters, replace=False), device=X.device)].clone()
@@ -421,15 +467,89 @@ class ClusterCriterion(nn.Module):
     # ---- hipGraph replay for ANY batch: every per-batch index comes from a DistillTables image (fixed addresses) ----------------------------
     _CONST = {}
 
-    def _static_ok(self):
-        if self.args.fifo_memory or not all(self._full_host()) or self._world() > 1:
-            raise RuntimeError("ClusterCriterion on StaticTargets (a captured distillation step) needs the steady state of a single process: every task's "
+    def _static_ok(self, training=False):
+        """training: the captured distillation step, which serves a run from step 0 under either memory policy (toist_bank_fifo, toist_kmeans_init) and
+        only needs a single process.  Otherwise (captured evaluation): the steady state, as before."""
+        if self._world() > 1:
+            raise RuntimeError("ClusterCriterion on StaticTargets (a captured step) is single-process: the memory-bank queue all_gathers rows across ranks, "
+                               "and collectives are not captured; run the list-of-dicts path")
+        if not training and (self.args.fifo_memory or not all(self._full_host())):
+            raise RuntimeError("ClusterCriterion on StaticTargets (a captured evaluation step) needs the steady state of a single process: every task's "
                                "memory bank full, nearest-replacement updates (fifo_memory off); run the list-of-dicts path until then")
 
+    # ---- the fill phase and FIFO banks under capture: the host only plans the random draws ------------------------------------------------------
+    def plan_fill(self, tasks_noun, tasks_sth):
+        """Host half of one captured step while banks fill.  tasks_noun: task per image of the teacher side, -1 = no boxes; tasks_sth: task per image of
+        the student side.  Advances the host mirror of update_count / full_label exactly as toist_bank_fifo will advance the device buffers
+        (mdetr.py:85-92: the label looks at the count before the add), then draws np.random.choice(N, K, replace=False) from the global stream in
+        the reference's call order (kmeans.py:8-18 as mdetr.py:171-176 and :249-263 reach it): teacher images in batch order, skipping those without
+        boxes, whose task is still filling AFTER this step's queue update; then every student image in batch order whose task is filling.
+        -> (init_noun, init_sth): int32 [B, K] numpy, the drawn bank rows per sample, -1 rows where the stored centres are the start."""
+        tasks_noun, tasks_sth = [int(t) for t in tasks_noun], [int(t) for t in tasks_sth]
+        if max(len(tasks_noun), len(tasks_sth)) > self.memory_size:
+            raise ValueError(f"a batch of {max(len(tasks_noun), len(tasks_sth))} images does not fit a memory bank of {self.memory_size} rows")
+        full = self._full_host()
+        count = self.__dict__["_count_mirror"]
+        for t in sorted(set(tasks_noun) - {-1}):
+            if not full[t]:
+                if count[t] > self.memory_size:
+                    full[t] = True
+                count[t] += tasks_noun.count(t)
+        out = []
+        for tasks in (tasks_noun, tasks_sth):
+            init = np.full((len(tasks), self.cluster_num), -1, dtype=np.int32)
+            for i, t in enumerate(tasks):
+                if t >= 0 and not full[t]:
+                    init[i] = np.random.choice(self.memory_size, self.cluster_num, replace=False)
+            out.append(init)
+        return out[0], out[1]
+
+    def __deepcopy__(self, memo):
+        """(the status word and its pinned copies in flight belong to this object's launches: a copy starts without them)"""
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for key, val in self.__dict__.items():
+            if key not in ("_kmeans_status", "_kmeans_pending"):
+                new.__dict__[key] = copy.deepcopy(val, memo)
+        return new
+
+    def _start_status(self, device):
+        """the sticky i32 status word of toist_kmeans_init on `device` (allocated on first use: before any capture, in the eager pass)"""
+        st = self.__dict__.get("_kmeans_status")
+        if st is None or st.device != device:
+            st = self.__dict__["_kmeans_status"] = torch.zeros(1, dtype=torch.int32, device=device)
+            self.__dict__["_kmeans_pending"] = []
+        return st
+
+    def check_start_status(self, defer=True):
+        """Raise when a toist_kmeans_init launch found the device's full_label and the host's plan (plan_fill) in disagreement -- the buffers were written
+        without sync_host_state().  defer=True: the design of matcher.check_lsap_status(defer=True) -- the word is copied to pinned memory behind an
+        event and the copies of EARLIER calls that have arrived are looked at, so no step waits for the device; defer=False waits."""
+        st = self.__dict__.get("_kmeans_status")
+        if st is None or torch.cuda.is_current_stream_capturing():
+            return
+        pending = self.__dict__["_kmeans_pending"]
+        host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        host.copy_(st, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        pending.append((host, ev))
+        while pending and (not defer or pending[0][1].query()):
+            host, ev = pending.pop(0)
+            ev.synchronize()
+            if int(host[0]) != 0:
+                st.zero_()
+                pending.clear()
+                raise RuntimeError("ClusterCriterion: the device's full_label and the host's plan of the k-means start disagreed in a captured step (the "
+                                   "launch fell back to the stored centres); call sync_host_state() after writing update_count / full_label directly")
+
     def _replace_nearest_static(self, rows, tb):
-        """update_memory_queue's nearest-replacement branch (mdetr.py:98-103) with the grouping of the batch by task read from the device: one LSAP problem
-        per group slot (rows = the group's size, 0 for an unused slot), pair table of fixed capacity B per problem, and a bank write that skips the dead
-        slots and the problems whose status is not OK (toist_scatter_rows_f32).  rows [B, d] f32 (detached features)."""
+        """update_memory_queue (mdetr.py:79-103) with the grouping of the batch by task AND the choice of the branch read from the device.  toist_bank_fifo
+        goes first: the groups whose task is still filling (or every group under fifo_memory) are pushed into their banks there, with the update_count /
+        full_label bookkeeping, and it leaves in `lsap_rows` the row count of each group for the nearest-replacement branch (mdetr.py:98-103) -- the
+        group's size, or 0 for a group it has served and for an unused slot.  Then one LSAP problem per group slot (dead when its row count is 0), pair
+        table of fixed capacity B per problem, and a bank write that skips the dead slots and the problems whose status is not OK
+        (toist_scatter_rows_f32).  rows [B, d] f32 (detached features)."""
         from . import kernels as k
         from .matcher import check_lsap_status
         B, d = rows.shape
@@ -445,7 +565,8 @@ class ClusterCriterion(nn.Module):
         rs = rows.index_select(0, mem).contiguous()                                  # rows in group order
         trow = tb.task.to(torch.int64).clamp(min=0).index_select(0, mem)
         cost = torch.cdist(rs[:, None, :], self.feature_bank.index_select(0, trow), p=1).reshape(B, N).contiguous()
-        n_g = (off[1:] - off[:-1]).to(torch.int32)
+        n_g = torch.zeros(B, dtype=torch.int32, device=dev)
+        k.bank_fifo(self.feature_bank, self.update_count, self.full_label, tb.group_task, tb.group_off, tb.members, rows.contiguous(), self.args.fifo_memory, n_g)
         ri = torch.zeros(B * B, dtype=torch.int64, device=dev)
         ci = torch.zeros(B * B, dtype=torch.int64, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -457,16 +578,28 @@ class ClusterCriterion(nn.Module):
         check_lsap_status(status, defer=True)
 
     def _cluster_static(self, features, tb):
+        """memory_cluster for the whole batch.  A DistillTables image that carries `init_rows` (FillTables.attach: the captured distillation step) goes
+        through toist_kmeans_init, where the device's full_label decides per sample between the drawn bank rows and the stored centres; one without
+        (captured evaluation, which requires full banks) through toist_kmeans."""
         from . import kernels as k
         B, d = features.shape
         pick = torch.zeros(B, dtype=torch.int32, device=features.device)
         chosen = torch.zeros(B, d, dtype=torch.float32, device=features.device)
-        k.kmeans(self.feature_bank, self.cluster_centers, tb.group_task, tb.group_off, tb.members, features.detach().float().contiguous(), 1e-4, 10000, pick, chosen)
+        feats = features.detach().float().contiguous()
+        init_rows = getattr(tb, "init_rows", None)
+        if init_rows is None:
+            k.kmeans(self.feature_bank, self.cluster_centers, tb.group_task, tb.group_off, tb.members, feats, 1e-4, 10000, pick, chosen)
+        else:
+            k.kmeans_init(self.feature_bank, self.cluster_centers, tb.group_task, tb.group_off, tb.members, feats, 1e-4, 10000, pick, chosen,
+                          self.full_label, init_rows, self._start_status(features.device))
         return pick, chosen
 
     def update_memory_static(self, memory_cache_noun, tb):
         """update_memory on a DistillTables image (teacher side)."""
-        self._static_ok()
+        self._static_ok(training=True)
+        if getattr(tb, "init_rows", None) is None and not all(self._full_host()):
+            raise RuntimeError("ClusterCriterion.update_memory on StaticTargets while a memory bank fills needs the step's k-means "
+                               "starts: FillTables.attach() the DistillTables and load() what plan_fill returns (harness.CapturedDistillStep does)")
         text = memory_cache_noun["text_memory"].permute(1, 0, 2)
         B, L, d = text.shape
         feats = (tb.W_span.to(text.dtype).unsqueeze(-1) * text).sum(1)
@@ -480,7 +613,7 @@ class ClusterCriterion(nn.Module):
 
     def forward_static(self, memory_cache_sth, tb):
         """forward (student side) on a DistillTables image: ('something' -> prototype, loss_cluster_feature)."""
-        self._static_ok()
+        self._static_ok(training=True)
         text = memory_cache_sth["text_memory"].permute(1, 0, 2)
         B, L, _ = text.shape
         memory_cache_sth["img_memory_mod"] = memory_cache_sth["img_memory"].clone()

@@ -915,6 +915,30 @@ def kmeans(banks, centers, group_task, group_off, members, features, tol, max_it
                                        max_iter, _p(pick, torch.int32), _p(chosen_center, torch.float32), _p(iters, torch.int32), _stream()), "toist_kmeans")
 
 
+def kmeans_init(banks, centers, group_task, group_off, members, features, tol, max_iter, pick, chosen_center, full_label, init_rows, status, iters=None):
+    """kmeans() whose start the device decides per sample: full_label f32 [T], init_rows i32 [B, K] (bank rows drawn on the host, or -1), status i32 [1]
+    (bit 0 = the two disagreed); see toist_kmeans_init."""
+    T, N, D = banks.shape
+    K = centers.shape[1]
+    assert init_rows.is_contiguous() and init_rows.shape == (features.shape[0], K) and full_label.numel() == T and status.numel() == 1
+    _lib.check(_lib.lib().toist_kmeans_init(_p(banks, torch.float32), banks.stride(0), _p(centers, torch.float32), centers.stride(0), _p(group_task, torch.int32),
+                                            _p(group_off, torch.int32), _p(members, torch.int32), group_task.numel(), _p(features, torch.float32), N, D, K, tol,
+                                            max_iter, _p(pick, torch.int32), _p(chosen_center, torch.float32), _p(iters, torch.int32),
+                                            _p(full_label, torch.float32), _p(init_rows, torch.int32), _p(status, torch.int32), _stream()), "toist_kmeans_init")
+
+
+def bank_fifo(banks, update_count, full_label, group_task, group_off, members, rows, fifo_when_full, lsap_rows):
+    """FIFO memory-bank update + update_count / full_label bookkeeping for the groups whose task is still filling (or all, with fifo_when_full);
+    lsap_rows i32 [n_groups] receives the row counts left to the nearest-replacement LSAP; see toist_bank_fifo."""
+    T, N, D = banks.shape
+    B = rows.shape[0]
+    assert banks[0].is_contiguous() and rows.is_contiguous() and rows.shape[1] == D and update_count.numel() == T and full_label.numel() == T
+    assert group_off.numel() == group_task.numel() + 1 and members.numel() >= B and lsap_rows.numel() == group_task.numel()
+    _lib.check(_lib.lib().toist_bank_fifo(_p(banks, torch.float32), banks.stride(0), _p(update_count, torch.float32), _p(full_label, torch.float32),
+                                          _p(group_task, torch.int32), _p(group_off, torch.int32), _p(members, torch.int32), group_task.numel(),
+                                          _p(rows, torch.float32), T, B, N, D, int(bool(fifo_when_full)), _p(lsap_rows, torch.int32), _stream()), "toist_bank_fifo")
+
+
 def attn_small_fwd(q, kmat, v, key_pad, B, H, S, dh, scale, drop_p, seed, ctx, stats, bq=None, bk=None, bv=None):
     """Whole-head self-attention for S <= 64, dh <= 64 (csrc/attn_small.hip); column slices of packed buffers, optional projection biases."""
     _lib.check(_lib.lib().toist_attn_small_fwd(_p(q, torch.bfloat16), q.stride(0), _p(kmat, torch.bfloat16), kmat.stride(0), _p(v, torch.bfloat16), v.stride(0),

@@ -21,7 +21,7 @@ def __getattr__(name):
         "build_matcher": ("matcher", "build_matcher"), "PostProcess": ("postprocessors", "PostProcess"),
         "PostProcessSegm": ("postprocessors", "PostProcessSegm"), "build_postprocessors": ("postprocessors", "build_postprocessors"),
         "NestedTensor": ("misc", "NestedTensor"), "targets_to": ("misc", "targets_to"),
-        "TDODCocoEvaluator": ("coco_eval", "TDODCocoEvaluator"), "CocoGroundTruth": ("coco_eval", "CocoGroundTruth"),
+        "TDODCocoEvaluator": ("coco_eval", "TDODCocoEvaluator"), "CocoGroundTruth": ("coco_eval", "CocoGroundTruth"), "polygon_vertices": ("coco_eval", "polygon_vertices"),
         "DevicePreprocessor": ("preprocess", "DevicePreprocessor"), "PrepPlan": ("preprocess", "PrepPlan"), "val_plan": ("preprocess", "val_plan"),
         "sample_train_plan": ("preprocess", "sample_train_plan"), "transform_target": ("preprocess", "transform_target"),
         "resized_size": ("preprocess", "resized_size"), "resample_tables": ("preprocess", "resample_tables"),

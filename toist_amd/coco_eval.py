@@ -140,6 +140,27 @@ def convert_coco_poly_to_mask(segmentations, height, width):
     return torch.stack(masks, dim=0) if masks else torch.zeros((0, height, width), dtype=torch.uint8)
 
 
+def polygon_vertices(poly):
+    """One polygon of a "segmentation" (a flat x0, y0, x1, y1, ...) checked before it is rasterised: -> (float64 [n, 2] vertices, trace steps).  The
+    trace steps are the sum over the closed path's edges of max(|dx|, |dy|) on rleFrPoly's 5x grid, int(5 * c + .5): the iterations polygon_to_mask
+    spends on the polygon (its cost, about 5x the perimeter in pixels).  Raises ValueError for an empty or odd-length list, a non-finite coordinate
+    and a coordinate whose grid value leaves int32 (maskApi.c holds the grid in int)."""
+    try:
+        xy = np.asarray(poly, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"a polygon is a flat list of numbers x0, y0, x1, y1, ... ({e})") from None
+    if xy.size == 0 or xy.size % 2:
+        raise ValueError(f"a polygon is a non-empty flat list x0, y0, x1, y1, ... of even length (got {xy.size} numbers)")
+    if not np.isfinite(xy).all():
+        raise ValueError("a polygon holds a non-finite coordinate")
+    grid = 5.0 * xy + .5
+    if (np.abs(grid) >= 2.0 ** 31).any():
+        raise ValueError("a polygon holds a coordinate whose 5x grid value does not fit int32")
+    g = np.trunc(grid).astype(np.int64).reshape(-1, 2)
+    d = np.abs(np.roll(g, -1, axis=0) - g)
+    return xy.reshape(-1, 2), int(d.max(axis=1).sum())
+
+
 # ---- ground truth ----------------------------------------------------------------------------------------------
 class CocoGroundTruth:
     """The slice of pycocotools.coco.COCO the evaluator reads: a COCO-format dict {"images": [{"id","height","width"}],

@@ -148,8 +148,9 @@ def test_real_tokenizer_spans_match_reference():
 
 
 def test_distill_tables_pack_equals_the_per_batch_tables_on_a_real_tokenizer():
-    """distill.DistillTables.pack (the fixed-address image of a captured distillation step) holds exactly what the list path builds per batch
-    (noun_token_weights, span positions, task grouping) -- on real BatchEncodings with padding, None lookups and the reference's fallbacks."""
+    """distill.DistillTables.pack (the fixed-address image of a captured distillation step) and the tables the list path builds per batch
+    (noun_token_weights) come from one builder: both are held against the oracle (distill_ref.noun_features / positions), and the task
+    grouping against its expected lists -- on real BatchEncodings with padding, None lookups and the reference's fallbacks."""
     from toist_amd import distill
     tok = tiny_tokenizer.build()
     for tag, pronoun in (("noun", False), ("sth", True)):
@@ -159,10 +160,13 @@ def test_distill_tables_pack_equals_the_per_batch_tables_on_a_real_tokenizer():
         targets[1]["dataset_name"] = targets[2]["dataset_name"]             # two images in one task
         tb = distill.DistillTables(3, L, "cpu", pronoun_side=pronoun)
         W_span, W_sth, sub_span, sub_sth, task, group_task, group_off, members = tb._views(tb.pack(enc, targets, TK_CAPTIONS[tag]))
-        want = distill.noun_token_weights(enc, targets, L, "cpu")
-        assert torch.equal(W_span, want)
+        text = formula.tensor(f"dtk.{tag}.tables.text", (3, L, 16), 2.0)
+        want = distill_ref.noun_features(text, enc, targets)
+        for W in (W_span, distill.noun_token_weights(enc, targets, L, "cpu")):        # the captured step's image, the list path's table
+            np.testing.assert_allclose(((W[..., None] * text).sum(1)).numpy(), want.numpy(), rtol=1e-5, atol=1e-6)
         for i, t in enumerate(targets):
-            assert sub_span[:, i].nonzero().reshape(-1).tolist() == distill.span_positions(enc, i, [s for b_ in t["noun_tokens_positive"] for s in b_], L).tolist()
+            assert sub_span[:, i].nonzero().reshape(-1).tolist() == distill_ref.positions(enc, i, [s for b_ in t["noun_tokens_positive"] for s in b_], L).tolist()
+            assert distill._noun_tables(enc, targets, L, "cpu")[1][:, i].nonzero().reshape(-1).tolist() == sub_span[:, i].nonzero().reshape(-1).tolist()
         assert task.tolist() == [1, 7, 7] and group_task.tolist()[:2] == [1, 7] and group_off.tolist() == [0, 1, 3, 3] and members.tolist() == [0, 1, 2]
         if pronoun:
             for i, cap in enumerate(TK_CAPTIONS[tag]):

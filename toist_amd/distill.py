@@ -86,29 +86,76 @@ def _cached_table(kind, refs, extra, make):
     return val
 
 
-def noun_token_weights(tokenized, targets, L, device):
-    """fp32 [B, L]: w[i, l] = sum over the boxes of image i of [token l belongs to the box's noun spans] / (tokens of the box x boxes of the image), so that
-    w @ text_feature[i] is the reference's mean over boxes of the mean over each box's noun tokens (mdetr.py:112-145, 684-711).  A box without any token
-    makes the reference average an empty set: the row is NaN, as there."""
+def span_tables(tokenized, targets, L):
+    """Host tables of the noun spans of a batch -> (W f32 [B, L], sub u8 [L, B]).  W[i, l] = sum over the boxes of image i of [token l belongs to the box's
+    noun spans] / (tokens of the box x boxes of the image), so that W @ text_feature[i] is the reference's mean over boxes of the mean over each box's noun
+    tokens (mdetr.py:112-145, 684-711); a box without any token makes the reference average an empty set: the row is NaN, as there.  sub[l, i]: token l of
+    image i receives the prototype on the teacher side (images without boxes: none)."""
+    W = np.zeros((len(targets), L), dtype=np.float32)
+    sub = np.zeros((L, len(targets)), dtype=np.uint8)
+    for i, tgt in enumerate(targets):
+        boxes = tgt["noun_tokens_positive"]
+        for spans in boxes:
+            pos = span_positions(tokenized, i, spans, L).numpy()
+            if len(pos) == 0:
+                W[i, :] = np.nan
+            else:
+                W[i, pos] += np.float32(1.0 / (len(pos) * len(boxes)))
+        if len(tgt["boxes"]) != 0:
+            sub[span_positions(tokenized, i, [s_ for box in boxes for s_ in box], L).numpy(), i] = 1
+    return W, sub
+
+
+def something_tables(tokenized, captions, L):
+    """Host tables of the word 'something' of every caption (mdetr.py:240-260) -> (W f32 [B, L] mean weights of its tokens, sub u8 [L, B], the token
+    positions per caption)."""
+    W = np.zeros((len(captions), L), dtype=np.float32)
+    sub = np.zeros((L, len(captions)), dtype=np.uint8)
+    positions = []
+    for i, caption in enumerate(captions):
+        beg = caption.find("something")
+        first, last = (tokenized.char_to_token(i, beg), tokenized.char_to_token(i, beg + len("something") - 1)) if beg >= 0 else (None, None)
+        if first is None or last is None:      # (the reference fails here too: mdetr.py:240-246 indexes with the None it gets back)
+            raise ValueError(f"pronoun caption {i} ({caption!r}) has no token for the word 'something'")
+        pos = np.arange(first, last + 1)
+        positions.append(pos)
+        if len(pos) == 0:
+            W[i, :] = np.nan                   # the reference averages an empty set there
+        else:
+            W[i, pos] = np.float32(1.0 / len(pos))
+            sub[pos, i] = 1
+    return W, sub, positions
+
+
+def task_groups(tasks):
+    """The images grouped by task, in batch order inside a group; tasks: one index per image, -1 = the image takes no part.
+    -> (group_task, group_off, members) as lists (csrc/kmeans.hip, the per-task LSAP of the memory-bank update)."""
+    live = [(i, t) for i, t in enumerate(tasks) if t >= 0]
+    order = sorted(set(t for _, t in live))
+    members, off = [], [0]
+    for t in order:
+        members += [i for i, tt in live if tt == t]
+        off.append(len(members))
+    return order, off, members
+
+
+def _noun_tables(tokenized, targets, L, device):
+    """span_tables on the device (W f32, sub bool), cached while the batch's objects are alive."""
     def make():
-        W = np.zeros((len(targets), L), dtype=np.float32)
-        for i, tgt in enumerate(targets):
-            boxes = tgt["noun_tokens_positive"]
-            for spans in boxes:
-                pos = span_positions(tokenized, i, spans, L).numpy()
-                if len(pos) == 0:
-                    W[i, :] = np.nan
-                else:
-                    W[i, pos] += np.float32(1.0 / (len(pos) * len(boxes)))
-        return torch.from_numpy(W).to(device)
+        W, sub = span_tables(tokenized, targets, L)
+        return torch.from_numpy(W).to(device), torch.from_numpy(sub).bool().to(device)
     return _cached_table("noun_w", (_tok_ref(tokenized), *targets), (L, str(device)), make)
+
+
+def noun_token_weights(tokenized, targets, L, device):
+    """fp32 [B, L] device copy of span_tables' W."""
+    return _noun_tables(tokenized, targets, L, device)[0]
 
 
 def noun_token_features(text_feature, tokenized, targets):
     """[B, d]: per image, the mean over its boxes of the mean text feature of each box's noun tokens
     (mdetr.py:112-145, 684-711); zero rows for images without boxes.  One weighted sum over the tokens with host-built, device-cached weights."""
-    B, L, d = text_feature.shape
-    W = noun_token_weights(tokenized, targets, L, text_feature.device).to(text_feature.dtype)
+    W = noun_token_weights(tokenized, targets, text_feature.shape[1], text_feature.device).to(text_feature.dtype)
     return (W.unsqueeze(-1) * text_feature).sum(1)
 
 
@@ -159,33 +206,25 @@ class DistillTables:
         self.W_span, self.W_sth, self.sub_span, self.sub_sth, self.task, self.group_task, self.group_off, self.members = views(self._dev)
         self._event = None
 
-    def pack(self, tokenized, targets, captions=None, out=None):
-        """Host image of one batch.  tokenized: the side's BatchEncoding (needs char_to_token); targets: the side's list of dicts with `noun_tokens_positive`,
-        `dataset_name`, `boxes`; captions: list[str] (pronoun side: where the word 'something' sits)."""
-        B, L = self.B, self.L
-        if len(targets) != B:
-            raise ValueError(f"DistillTables holds {B} images; got {len(targets)}")
+    def _staging(self, out):
         host = out if out is not None else torch.zeros(self._host.numel(), dtype=torch.uint8)
         if out is None and self._pin:
             host = host.pin_memory()
         host.zero_()
-        W_span, W_sth, sub_span, sub_sth, task, group_task, group_off, members = (v.numpy() for v in self._views(host))
-        empty = [len(t["boxes"]) == 0 for t in targets]
-        for i, tgt in enumerate(targets):
-            boxes = tgt["noun_tokens_positive"]
-            for spans in boxes:
-                pos = span_positions(tokenized, i, spans, L).numpy()
-                if len(pos) == 0:
-                    W_span[i, :] = np.nan                      # the reference averages an empty set there
-                else:
-                    W_span[i, pos] += np.float32(1.0 / (len(pos) * len(boxes)))
-            if not empty[i]:
-                sub_span[span_positions(tokenized, i, [s_ for box in boxes for s_ in box], L).numpy(), i] = 1
+        return host, [v.numpy() for v in self._views(host)]
+
+    def pack(self, tokenized, targets, captions=None, out=None):
+        """Host image of one batch.  tokenized: the side's BatchEncoding (needs char_to_token); targets: the side's list of dicts with `noun_tokens_positive`,
+        `dataset_name`, `boxes`; captions: list[str] (pronoun side: where the word 'something' sits)."""
+        if len(targets) != self.B:
+            raise ValueError(f"DistillTables holds {self.B} images; got {len(targets)}")
+        host, (W_span, W_sth, sub_span, sub_sth, task, group_task, group_off, members) = self._staging(out)
+        W_span[:], sub_span[:] = span_tables(tokenized, targets, self.L)
         if self.pronoun_side:
-            self._pack_something(tokenized, captions, W_sth, sub_sth)
+            W_sth[:], sub_sth[:], _ = something_tables(tokenized, captions[:self.B], self.L)
             tasks = [task_index(t["dataset_name"]) for t in targets]               # the student clusters EVERY sample (mdetr.py:230-277)
         else:
-            tasks = [-1 if empty[i] else task_index(t["dataset_name"]) for i, t in enumerate(targets)]
+            tasks = [-1 if len(t["boxes"]) == 0 else task_index(t["dataset_name"]) for t in targets]
         self._pack_groups(tasks, task, group_task, group_off, members)
         return host
 
@@ -193,42 +232,20 @@ class DistillTables:
         """Host image of one EVALUATION batch (pronoun side): what the prototype choice of inference reads (mdetr.py:282-312) -- W_sth, sub_sth, task and
         the grouping by task -- from the tokenized captions (char_to_token), the caption strings and the dataset names alone.  No targets: W_span /
         sub_span stay zero (only the teacher's bank update reads them)."""
-        B = self.B
         if not self.pronoun_side:
             raise ValueError("pack_eval fills the pronoun side's tables")
-        if len(captions) != B or len(dataset_names) != B:
-            raise ValueError(f"DistillTables holds {B} images; got {len(captions)} captions and {len(dataset_names)} dataset names")
-        host = out if out is not None else torch.zeros(self._host.numel(), dtype=torch.uint8)
-        if out is None and self._pin:
-            host = host.pin_memory()
-        host.zero_()
-        _, W_sth, _, sub_sth, task, group_task, group_off, members = (v.numpy() for v in self._views(host))
-        self._pack_something(tokenized, captions, W_sth, sub_sth)
+        if len(captions) != self.B or len(dataset_names) != self.B:
+            raise ValueError(f"DistillTables holds {self.B} images; got {len(captions)} captions and {len(dataset_names)} dataset names")
+        host, (_, W_sth, _, sub_sth, task, group_task, group_off, members) = self._staging(out)
+        W_sth[:], sub_sth[:], _ = something_tables(tokenized, captions, self.L)
         self._pack_groups([task_index(n) for n in dataset_names], task, group_task, group_off, members)
         return host
 
-    def _pack_something(self, tokenized, captions, W_sth, sub_sth):
-        for i in range(self.B):
-            beg = captions[i].find("something")
-            first, last = (tokenized.char_to_token(i, beg), tokenized.char_to_token(i, beg + len("something") - 1)) if beg >= 0 else (None, None)
-            if first is None or last is None:      # (the reference fails here too: mdetr.py:240-246 indexes with the None it gets back)
-                raise ValueError(f"pronoun caption {i} ({captions[i]!r}) has no token for the word 'something'")
-            pos = np.arange(first, last + 1)
-            if len(pos) == 0:
-                W_sth[i, :] = np.nan
-            else:
-                W_sth[i, pos] = np.float32(1.0 / len(pos))
-                sub_sth[pos, i] = 1
-
     @staticmethod
     def _pack_groups(tasks, task, group_task, group_off, members):
+        """task_groups into the arena's views; unused groups are empty (group_off stays at the member count)."""
+        order, off, mem = task_groups(tasks)
         task[:] = np.asarray(tasks, dtype=np.int32)
-        live = [(i, t) for i, t in enumerate(tasks) if t >= 0]
-        order = sorted(set(t for _, t in live))
-        mem, off = [], [0]
-        for t in order:
-            mem += [i for i, tt in live if tt == t]
-            off.append(len(mem))
         group_task[:len(order)] = order
         group_off[:len(off)] = off
         group_off[len(off):] = len(mem)
@@ -414,13 +431,8 @@ class ClusterCriterion(nn.Module):
         if ent is None:
             if len(ClusterCriterion._INDEX_TABLES) > 256:
                 ClusterCriterion._INDEX_TABLES.clear()
-            order = sorted(set(t for _, t in live))
-            members, off = [], [0]
-            for t in order:
-                members += [i for i, tt in live if tt == t]
-                off.append(len(members))
-            mk = lambda v: torch.tensor(v, dtype=torch.int32, device=features.device)
-            ent = ClusterCriterion._INDEX_TABLES[key] = (mk(order), mk(off), mk(members))
+            ent = ClusterCriterion._INDEX_TABLES[key] = tuple(torch.tensor(v, dtype=torch.int32, device=features.device)
+                                                              for v in task_groups([-1 if t is None else t for t in tasks]))
         group_task, group_off, members = ent
         B, d = features.shape
         pick = torch.zeros(B, dtype=torch.int32, device=features.device)
@@ -594,34 +606,42 @@ class ClusterCriterion(nn.Module):
                           self.full_label, init_rows, self._start_status(features.device))
         return pick, chosen
 
+    def _substitute_batch(self, memory_cache, W, sub, cluster, with_loss=False, push=None):
+        """The steady-state arithmetic shared by the teacher and the student side, on list targets and on a DistillTables image: features = W @ text
+        memory [B, d]; push(features) (the teacher's bank update goes BEFORE the clustering, mdetr.py:105-205); img_memory_mod = a copy of img_memory;
+        cluster(features) -> (pick, chosen [B, d]) for the whole batch; the text rows marked in `sub` [L, B] are overwritten by the sample's prototype.
+        -> (features, loss_cluster_feature -- 0.0 without with_loss).  cluster() may return None (the list path while a bank fills): nothing is substituted then and the
+        second result is None -- the caller goes sample by sample."""
+        text = memory_cache["text_memory"].permute(1, 0, 2)
+        B, L, _ = text.shape
+        features = (W.to(text.dtype).unsqueeze(-1) * text).sum(1)
+        if push is not None:
+            push(features.detach().float())
+        memory_cache["img_memory_mod"] = memory_cache["img_memory"].clone()
+        batch = cluster(features)
+        if batch is None:
+            return features, None
+        chosen = batch[1]
+        mod = memory_cache["img_memory_mod"]
+        mod[-L:] = torch.where(sub.bool()[:, :, None], chosen[None].to(mod.dtype), mod[-L:])
+        if not with_loss:
+            return features, 0.0
+        return features, ((features - chosen.to(features.dtype)) ** 2).mean(1).sum() / max(B, 1)
+
     def update_memory_static(self, memory_cache_noun, tb):
         """update_memory on a DistillTables image (teacher side)."""
         self._static_ok(training=True)
         if getattr(tb, "init_rows", None) is None and not all(self._full_host()):
             raise RuntimeError("ClusterCriterion.update_memory on StaticTargets while a memory bank fills needs the step's k-means "
                                "starts: FillTables.attach() the DistillTables and load() what plan_fill returns (harness.CapturedDistillStep does)")
-        text = memory_cache_noun["text_memory"].permute(1, 0, 2)
-        B, L, d = text.shape
-        feats = (tb.W_span.to(text.dtype).unsqueeze(-1) * text).sum(1)
-        self._replace_nearest_static(feats.detach().float(), tb)
-        memory_cache_noun["img_memory_mod"] = memory_cache_noun["img_memory"].clone()
-        _, chosen = self._cluster_static(feats, tb)
-        mod = memory_cache_noun["img_memory_mod"]
-        mod[-L:] = torch.where(tb.sub_span.bool()[:, :, None], chosen[None].to(mod.dtype), mod[-L:])
+        self._substitute_batch(memory_cache_noun, tb.W_span, tb.sub_span, lambda f: self._cluster_static(f, tb), push=lambda rows: self._replace_nearest_static(rows, tb))
         memory_cache_noun["full_label"], memory_cache_noun["update_count"] = self.full_label, self.update_count
         return memory_cache_noun
 
     def forward_static(self, memory_cache_sth, tb):
         """forward (student side) on a DistillTables image: ('something' -> prototype, loss_cluster_feature)."""
         self._static_ok(training=True)
-        text = memory_cache_sth["text_memory"].permute(1, 0, 2)
-        B, L, _ = text.shape
-        memory_cache_sth["img_memory_mod"] = memory_cache_sth["img_memory"].clone()
-        features = (tb.W_sth.to(text.dtype).unsqueeze(-1) * text).sum(1)
-        _, chosen = self._cluster_static(features, tb)
-        mod = memory_cache_sth["img_memory_mod"]
-        mod[-L:] = torch.where(tb.sub_sth.bool()[:, :, None], chosen[None].to(mod.dtype), mod[-L:])
-        loss = ((features - chosen.to(features.dtype)) ** 2).mean(1).sum() / max(B, 1)
+        _, loss = self._substitute_batch(memory_cache_sth, tb.W_sth, tb.sub_sth, lambda f: self._cluster_static(f, tb), with_loss=True)
         return memory_cache_sth, {"loss_cluster_choice": torch.zeros((), device=loss.device), "loss_cluster_feature": loss}
 
     @torch.no_grad()
@@ -630,13 +650,7 @@ class ClusterCriterion(nn.Module):
         prototype closest to its own feature, with no host value in any launch (harness.CapturedEvalStep records it into its graphs).  k-means moves
         `cluster_centers` in place, as memory_cluster does."""
         self._static_ok()
-        text = memory_cache_sth["text_memory"].permute(1, 0, 2)
-        L = text.shape[1]
-        memory_cache_sth["img_memory_mod"] = memory_cache_sth["img_memory"].clone()
-        features = (tb.W_sth.to(text.dtype).unsqueeze(-1) * text).sum(1)
-        _, chosen = self._cluster_static(features, tb)
-        mod = memory_cache_sth["img_memory_mod"]
-        mod[-L:] = torch.where(tb.sub_sth.bool()[:, :, None], chosen[None].to(mod.dtype), mod[-L:])
+        self._substitute_batch(memory_cache_sth, tb.W_sth, tb.sub_sth, lambda f: self._cluster_static(f, tb))
         return memory_cache_sth
 
     def update_memory(self, memory_cache_noun, targets_noun, captions_noun):
@@ -645,75 +659,43 @@ class ClusterCriterion(nn.Module):
         tb = getattr(targets_noun, "distill", None)
         if tb is not None:                      # matcher.StaticTargets of a captured step
             return self.update_memory_static(memory_cache_noun, tb)
-        text = memory_cache_noun["text_memory"].permute(1, 0, 2)
-        B, L, d = text.shape
-        dev = text.device
+        L = len(memory_cache_noun["text_memory"])
+        dev = memory_cache_noun["text_memory"].device
         tokenized = memory_cache_noun["tokenized"]
-        feats = noun_token_features(text, tokenized, targets_noun)
-        empty = [len(t["boxes"]) == 0 for t in targets_noun]
-        tasks = [None if empty[i] else task_index(t["dataset_name"]) for i, t in enumerate(targets_noun)]
-
-        def make():     # task column of the queue rows and the [L, B] mask of the noun tokens that receive the prototype
-            col = torch.tensor([-1.0 if t is None else float(t) for t in tasks], dtype=torch.float32)
-            mask = torch.zeros(L, B, dtype=torch.bool)
+        W, sub = _noun_tables(tokenized, targets_noun, L, dev)
+        tasks = [None if len(t["boxes"]) == 0 else task_index(t["dataset_name"]) for t in targets_noun]
+        tasks_host = [-1 if t is None else t for t in tasks]
+        task_col = _cached_table("noun_meta", (_tok_ref(tokenized), *targets_noun), (L, str(dev)), lambda: torch.tensor(tasks_host, dtype=torch.float32).to(dev))
+        # queue rows: feature | task; rows of images without boxes: zero feature, task -1
+        feats, done = self._substitute_batch(memory_cache_noun, W, sub, lambda f: self.cluster_batch(f, tasks),
+                                             push=lambda rows: self.update_memory_queue(torch.cat([rows, task_col[:, None]], dim=1), tasks_host=tasks_host))
+        if done is None:        # a bank is filling: sample by sample on the host
             for i, tgt in enumerate(targets_noun):
-                if not empty[i]:
-                    mask[span_positions(tokenized, i, [s for box in tgt["noun_tokens_positive"] for s in box], L), i] = True
-            return col.to(dev), mask.to(dev)
-        task_col, sub_mask = _cached_table("noun_meta", (_tok_ref(tokenized), *targets_noun), (L, str(dev)), make)
-        rows = torch.cat([feats.detach().float(), task_col[:, None]], dim=1)          # rows of images without boxes: zero feature, task -1
-        self.update_memory_queue(rows, tasks_host=[-1 if t is None else t for t in tasks])
-        memory_cache_noun["img_memory_mod"] = memory_cache_noun["img_memory"].clone()
-        batch = self.cluster_batch(feats, tasks)
-        if batch is not None:
-            mod = memory_cache_noun["img_memory_mod"]
-            mod[-L:] = torch.where(sub_mask[:, :, None], batch[1][None].to(mod.dtype), mod[-L:])
-        else:
-            for i, tgt in enumerate(targets_noun):
-                if empty[i]:
-                    continue
-                spans = [s for box in tgt["noun_tokens_positive"] for s in box]
-                self._substitute(memory_cache_noun, i, span_positions(tokenized, i, spans, L), tasks[i], feats[i])
+                if tasks[i] is not None:
+                    spans = [s for box in tgt["noun_tokens_positive"] for s in box]
+                    self._substitute(memory_cache_noun, i, span_positions(tokenized, i, spans, L), tasks[i], feats[i])
         memory_cache_noun["full_label"], memory_cache_noun["update_count"] = self.full_label, self.update_count
         return memory_cache_noun
 
     def _something(self, memory_cache, names, captions, with_loss):
-        text = memory_cache["text_memory"].permute(1, 0, 2)
-        B, L, _ = text.shape
-        dev = text.device
+        L, B = memory_cache["text_memory"].shape[:2]
+        dev = memory_cache["text_memory"].device
         tokenized = memory_cache["tokenized"]
-        memory_cache["img_memory_mod"] = memory_cache["img_memory"].clone()
 
-        def make():     # tokens of the pronoun "something" per caption: mean weights [B, L], substitution mask [L, B], host positions
-            W = torch.zeros(B, L, dtype=torch.float32)
-            mask = torch.zeros(L, B, dtype=torch.bool)
-            positions = []
-            for i in range(B):
-                beg = captions[i].find("something")
-                pos = torch.arange(tokenized.char_to_token(i, beg), tokenized.char_to_token(i, beg + len("something") - 1) + 1)
-                positions.append(pos)
-                W[i, pos] = 1.0 / max(len(pos), 1) if len(pos) else float("nan")
-                mask[pos, i] = True
-            if any(len(p_) == 0 for p_ in positions):       # the reference averages an empty set there: NaN
-                for i, p_ in enumerate(positions):
-                    if len(p_) == 0:
-                        W[i, :] = float("nan")
-            return W.to(dev), mask.to(dev), positions
-        W, sub_mask, positions = _cached_table("sth_meta", (_tok_ref(tokenized),), (tuple(captions), L, str(dev)), make)
-        features = (W.to(text.dtype).unsqueeze(-1) * text).sum(1)                      # [B, d]: text[i][pos].mean(0)
+        def make():
+            W, sub, positions = something_tables(tokenized, captions, L)
+            return torch.from_numpy(W).to(dev), torch.from_numpy(sub).bool().to(dev), [torch.from_numpy(p_) for p_ in positions]
+        W, sub, positions = _cached_table("sth_meta", (_tok_ref(tokenized),), (tuple(captions), L, str(dev)), make)
         tasks = [task_index(n) for n in names]
-        batch = self.cluster_batch(features, tasks) if B else None
-        if batch is not None:
-            mod = memory_cache["img_memory_mod"]
-            mod[-L:] = torch.where(sub_mask[:, :, None], batch[1][None].to(mod.dtype), mod[-L:])
-            loss_feature = ((features - batch[1].to(features.dtype)) ** 2).mean(1).sum() if with_loss else torch.zeros((), device=dev)
-        else:
+        features, loss_feature = self._substitute_batch(memory_cache, W, sub, lambda f: self.cluster_batch(f, tasks), with_loss)
+        if loss_feature is None:        # a bank is filling: sample by sample on the host
             loss_feature = torch.zeros((), device=dev)
             for i in range(B):
                 center = self._substitute(memory_cache, i, positions[i], tasks[i], features[i])
                 if with_loss:
                     loss_feature = loss_feature + F.mse_loss(features[i], center)
-        return memory_cache, loss_feature / max(B, 1)
+            loss_feature = loss_feature / max(B, 1)
+        return memory_cache, loss_feature
 
     def forward(self, memory_cache_sth, targets_sth, captions_sth):
         """Student side (mdetr.py:230-277): the pronoun 'something' is replaced by the prototype closest to its own
@@ -726,5 +708,5 @@ class ClusterCriterion(nn.Module):
 
     @torch.no_grad()
     def infer_choice(self, memory_cache_sth, dataset_name_list, captions):
-        """mdetr.py:279-312"""
+        """mdetr.py:282-312"""
         return self._something(memory_cache_sth, dataset_name_list, captions, False)[0]

@@ -24,6 +24,10 @@ class MatchResult:
         self.match_off = [0]
         for c in self.counts:
             self.match_off.append(self.match_off[-1] + c)
+        if match_off_dev is None:       # a result built by hand: the losses decode their pair tables from the device offsets (pair_slots)
+            self.match_off_dev = torch.tensor(self.match_off, dtype=torch.int32, device=src.device)
+        if tgt_off is None:
+            self.tgt_off_dev = torch.tensor([sum(self.sizes[:i]) for i in range(len(self.sizes) + 1)], dtype=torch.int32, device=src.device)
 
     def check(self):
         """Raise like SciPy does for an invalid cost matrix (host sync)."""
@@ -37,6 +41,30 @@ class MatchResult:
         self.check()
         s, t = self.src[layer].cpu(), self.tgt[layer].cpu()
         return [(s[a:b].clone(), t[a:b].clone()) for a, b in zip(self.match_off[:-1], self.match_off[1:])]
+
+
+_ARANGES = {}
+
+
+def pair_slots(match_off, L, B, cap):
+    """The pair table of L layers x `cap` slots, decoded ON THE DEVICE from match_off (int32 [B + 1]): the matcher kernels pack layer l's pairs at
+    [l * match_off[B], (l + 1) * match_off[B]), whatever the capacity of the buffer.  -> (live bool, layer, position j inside the layer, image whose run
+    [match_off[i], match_off[i + 1]) holds j, match_off as int64), the first four [L * cap]; dead slots carry clamped, in-range values.  No shape or launch
+    parameter depends on the batch's counts, so the same launches serve a StaticTargets image (cap = its capacity) and a list-path MatchResult (cap = Mtot)."""
+    dev = match_off.device
+    p = _ARANGES.get((L * cap, str(dev)))
+    if p is None:
+        p = _ARANGES[(L * cap, str(dev))] = torch.arange(L * cap, dtype=torch.int64, device=dev)
+    mo = match_off.to(torch.int64)
+    mtot = mo[B]
+    if L == 1:
+        live, layer, j = p < mtot, 0, p
+    else:
+        live = p < L * mtot
+        layer = torch.div(p, mtot.clamp(min=1), rounding_mode="floor").clamp(max=L - 1)
+        j = p - layer * mtot
+    img = torch.bucketize(j, mo[1:], right=True).clamp(max=B - 1)
+    return live, layer, j, img, mo
 
 
 class StaticTargets:

@@ -6,15 +6,16 @@ forward signatures, output / loss dict keys and state_dict names, so engine.py /
 drivers run unchanged.
 """
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import dist, engine, functions
+from . import dist, engine, functions, matcher
 from . import kernels as k
 from .backbone import build_backbone, nearest_mask
-from .matcher import StaticTargets, build_matcher
+from .matcher import StaticTargets, build_matcher, pair_slots
 from .misc import NestedTensor
 from .transformer import build_transformer
 from .distill import ClusterCriterion, char_span_to_tokens, noun_token_features
@@ -315,29 +316,11 @@ class SetCriterion(nn.Module):
         self.losses = losses
         self.temperature = temperature
         self.last_match = None
-        self._maps, self._nb, self._nb_reduced = {}, {}, {}
+        self._nb, self._nb_reduced = {}, {}
         self._tokmask = None       # (member mask tensors, concatenated [sum T, 4] int64): spans of the last batch, uploaded once
         self._pending_status = []  # (pinned host copy, event) of matcher status words not yet looked at
 
     # -- helpers ------------------------------------------------------------------------------------------
-    def _slot_maps(self, match, device):
-        """Per matched slot: image index and offset of the image's first target, plus the per-image target
-        counts -- host arithmetic on shapes, cached per batch signature (no H2D copy in steady state)."""
-        key = (tuple(match.sizes), tuple(match.counts), str(device))
-        ent = self._maps.get(key)
-        if ent is None:
-            if len(self._maps) > 64:
-                self._maps.clear()
-            b_idx, t_base, acc = [], [], 0
-            for b, (cnt, size) in enumerate(zip(match.counts, match.sizes)):
-                b_idx += [b] * cnt
-                t_base += [acc] * cnt
-                acc += size
-            ent = (torch.tensor(b_idx, dtype=torch.int64, device=device), torch.tensor(t_base, dtype=torch.int64, device=device),
-                   torch.tensor(match.sizes, dtype=torch.float32, device=device))
-            self._maps[key] = ent
-        return ent
-
     def _num_boxes(self, targets, device):
         total = float(sum(len(t["labels"]) for t in targets))
         key = (total, str(device))
@@ -457,7 +440,7 @@ class SetCriterion(nn.Module):
         return cat
 
     # -- losses over all layers at once -------------------------------------------------------------------
-    def _detection_losses(self, logits, boxes, match, targets, positive_map, num_boxes):
+    def _detection_losses(self, logits, boxes, match, positive_map, num_boxes):
         """labels / boxes / cardinality for every decoder layer: one forward launch of the fused HIP
         criterion kernel (and one backward launch), see csrc/criterion.hip."""
         L = logits.shape[0]
@@ -466,35 +449,38 @@ class SetCriterion(nn.Module):
         self._note_status(match)
         out, index = LossDict(), {}
         for l in range(L):
-            sfx = "" if l == L - 1 else f"_{l}"
+            key = lambda name: _layer_key(name, l, L)
             if "labels" in self.losses:
-                out["loss_ce" + sfx], index["loss_ce" + sfx] = vals[l, 0], 4 * l
+                out[key("loss_ce")], index[key("loss_ce")] = vals[l, 0], 4 * l
             if "boxes" in self.losses:
-                out["loss_bbox" + sfx], index["loss_bbox" + sfx] = vals[l, 1], 4 * l + 1
-                out["loss_giou" + sfx], index["loss_giou" + sfx] = vals[l, 2], 4 * l + 2
+                out[key("loss_bbox")], index[key("loss_bbox")] = vals[l, 1], 4 * l + 1
+                out[key("loss_giou")], index[key("loss_giou")] = vals[l, 2], 4 * l + 2
             if "cardinality" in self.losses:
-                out["cardinality_error" + sfx] = vals[l, 3].detach()
+                out[key("cardinality_error")] = vals[l, 3].detach()
         out.groups.append((vals, index))
         return out
 
-    def _contrastive_align(self, outputs, match, targets, num_boxes, L):
+    def _contrastive_align(self, outputs, match, tok_mask, num_boxes, L):
         """loss_contrastive_align of the L visited layers (mdetr.py:601-666) -> LossDict: one launch of the device kernel
-        (csrc/contrastive.hip) each way; the token spans of the targets are uploaded once per batch."""
+        (csrc/contrastive.hip) each way.  tok_mask: int64 [sum T, TOKEN_MASK_WORDS] span bit masks of the targets, or None when the batch is
+        known on the host to hold no target: every term is masked out then (mdetr.py:655,662)."""
         pq = self._stack_proj(outputs, L)
         pt = outputs["proj_tokens"]
-        out, index = LossDict(), {}
-        if match.tgt_boxes is None:      # no target in the batch: every term is masked out (mdetr.py:655,662)
-            vals = (pq.sum() * 0 + pt.sum() * 0).expand(L)
-        else:
-            masks = self._token_masks(targets, outputs.get("tokenized"), pq.device)
-            vals = _ContrastiveFn.apply(pq.float().contiguous(), pt.float().contiguous(), match, masks,
-                                        num_boxes.reshape(1).float().contiguous(), float(self.temperature))
-        for l in range(L):
-            key = "loss_contrastive_align" + ("" if l == L - 1 else f"_{l}")
-            out[key], index[key] = vals[l], l
-        if match.tgt_boxes is not None:
-            out.groups.append((vals, index))
-        return out
+        if tok_mask is None:
+            return _per_layer("loss_contrastive_align", (pq.sum() * 0 + pt.sum() * 0).expand(L), group=False)
+        return _per_layer("loss_contrastive_align", _ContrastiveFn.apply(pq.float().contiguous(), pt.float().contiguous(), match, tok_mask,
+                                                                         num_boxes.reshape(1).float().contiguous(), float(self.temperature)))
+
+    def _side_losses(self, outputs, logits, boxes, match, positive_map, num_boxes, tok_mask, mask_losses):
+        """Every loss of ONE model on a device-resident assignment: labels / boxes / cardinality / contrastive_align / masks.  tok_mask() and
+        mask_losses() are the front end's: only what feeds them differs between the list-of-dicts targets and a StaticTargets image."""
+        self.last_match = match
+        losses = self._detection_losses(logits, boxes, match, positive_map, num_boxes)
+        if "contrastive_align" in self.losses:
+            losses.merge(self._contrastive_align(outputs, match, tok_mask(), num_boxes, logits.shape[0]))
+        if "masks" in self.losses:
+            losses.update(mask_losses())
+        return losses
 
     def forward(self, memory_cache, outputs, targets, positive_map, example_rel=None):
         if self._pending_status and not torch.cuda.is_current_stream_capturing():
@@ -504,95 +490,44 @@ class SetCriterion(nn.Module):
                 return self._forward_pair_static(memory_cache, outputs, targets)
             return self._forward_pair(memory_cache, outputs, targets, positive_map)
         logits, boxes = self._stack(outputs)
-        L = logits.shape[0]
         if isinstance(targets, StaticTargets):
-            return self._forward_static(outputs, logits, boxes, targets, L)
+            return self._forward_static(outputs, logits, boxes, targets)
+        return self._forward_list(outputs, logits, boxes, targets, positive_map)
+
+    def _forward_list(self, outputs, logits, boxes, targets, positive_map):
+        """The reference's targets (list of dicts): shapes follow the batch's target counts."""
+        from .segmentation import mask_losses
+        L = logits.shape[0]
         match = self.matcher.match_layers(logits.detach(), boxes.detach(), targets, positive_map)
-        self.last_match = match
         num_boxes = self._num_boxes(targets, logits.device)
-        losses = self._detection_losses(logits, boxes, match, targets, positive_map, num_boxes)
-        if "contrastive_align" in self.losses:
-            losses.merge(self._contrastive_align(outputs, match, targets, num_boxes, L))
-        if "masks" in self.losses:
-            from .segmentation import mask_losses
-            losses.update(mask_losses(outputs, targets, match, L - 1, num_boxes))
-        return losses
+        return self._side_losses(outputs, logits, boxes, match, positive_map, num_boxes,
+                                 lambda: None if match.tgt_boxes is None else self._token_masks(targets, outputs.get("tokenized"), logits.device),
+                                 lambda: mask_losses(outputs, targets, match, L - 1, num_boxes))
 
-
-    def _forward_static(self, outputs, logits, boxes, st, L):
+    def _forward_static(self, outputs, logits, boxes, st):
         """Detection losses on a StaticTargets image (matcher.StaticTargets): no shape, pointer or launch parameter depends on the
         batch's target counts -- the captured step is replayed for any batch after st.load(...).  labels / boxes / cardinality /
         contrastive_align / masks (StaticTargets(mask_hw=...) carries the ground-truth masks)."""
+        from .segmentation import mask_losses_static
+        L = logits.shape[0]
         match = self.matcher.match_layers_static(logits.detach(), boxes.detach(), st)
-        self.last_match = match
-        losses = self._detection_losses(logits, boxes, match, None, st.positive_map, st.num_boxes)
-        if "contrastive_align" in self.losses:
-            pq, pt = self._stack_proj(outputs, L), outputs["proj_tokens"]
-            vals = _ContrastiveFn.apply(pq.float().contiguous(), pt.float().contiguous(), match, st.tok_mask, st.num_boxes, float(self.temperature))
-            out, index = LossDict(), {}
-            for l in range(L):
-                key = "loss_contrastive_align" + ("" if l == L - 1 else f"_{l}")
-                out[key], index[key] = vals[l], l
-            out.groups.append((vals, index))
-            losses.merge(out)
-        if "masks" in self.losses:
-            from .segmentation import mask_losses_static
-            losses.update(mask_losses_static(outputs, st, match, L - 1, L))
-        return losses
+        return self._side_losses(outputs, logits, boxes, match, st.positive_map, st.num_boxes, lambda: st.tok_mask,
+                                 lambda: mask_losses_static(outputs, st, match, L - 1, L))
 
     # ---- distillation: [teacher (noun), student (pronoun)] -------------------------------------------------------
-    def _forward_pair(self, memory_cache, outputs, targets, positive_map):
-        """List branch of the reference (mdetr.py:887-987): every detection loss for both models under the prefixes
-        noun_ / sth_, then the cross losses nsthl2 (main layer) and softkd (every layer)."""
+    def _pair_losses(self, outputs, side_losses, features, softkd):
+        """List branch of the reference (mdetr.py:887-987): every detection loss for both models under the prefixes noun_ / sth_, then the cross
+        losses nsthl2 (main layer) and softkd (every layer).  The front end supplies side_losses(i, out, logits, boxes) -> LossDict (leaves the
+        assignment in self.last_match), features(i) -> [B, d] mean noun-token text feature of side i, softkd(noun, sth) -> [L]."""
         losses, sides = LossDict(), []
-        for prefix, out, tgt, pm in zip(("noun", "sth"), outputs, targets, positive_map):
+        for i, (prefix, out) in enumerate(zip(("noun", "sth"), outputs)):
             logits, boxes = self._stack(out)
-            L = logits.shape[0]
-            match = self.matcher.match_layers(logits.detach(), boxes.detach(), tgt, pm)
-            num_boxes = self._num_boxes(tgt, logits.device)
-            side = self._detection_losses(logits, boxes, match, tgt, pm, num_boxes)
-            if "contrastive_align" in self.losses:
-                side.merge(self._contrastive_align(out, match, tgt, num_boxes, L))
-            if "masks" in self.losses:
-                from .segmentation import mask_losses
-                side.update(mask_losses(out, tgt, match, L - 1, num_boxes))
-            losses.merge(side, prefix + "_")
-            sides.append((logits, boxes, match, L))
-        self.last_match = sides[1][2]
+            losses.merge(side_losses(i, out, logits, boxes), prefix + "_")
+            sides.append((logits, boxes, self.last_match, logits.shape[0]))
         if getattr(self.args, "nsthl2_loss", False):
-            losses["loss_nsthl2"] = self._loss_nsthl2(memory_cache, outputs, targets, sides[1][2])
+            mo = self.last_match.match_off_dev
+            losses["loss_nsthl2"] = _nsthl2(features(0), features(1), (mo[1:] - mo[:-1]) > 0)       # images in which the student's main layer matched a box
         if getattr(self.args, "softkd_loss", False):
-            L = sides[0][3]
-            per_layer = self._loss_softkd(sides[0], sides[1])
-            for l in range(L):
-                losses["loss_softkd" + ("" if l == L - 1 else f"_{l}")] = per_layer[l]
-            losses.groups.append((per_layer, {"loss_softkd" + ("" if l == L - 1 else f"_{l}"): l for l in range(L)}))
-        return losses
-
-    # ---- the same on StaticTargets (+ .distill tables): nothing depends on the batch's target counts, captions or tasks -> one hipGraph for any batch ----
-    def _forward_pair_static(self, memory_cache, outputs, sts):
-        """_forward_pair on two matcher.StaticTargets images (teacher, student), each carrying its distill.DistillTables: the step captured by
-        harness.CapturedDistillStep.  The two sides must hold the same number of targets per image (softkd pairs the matched queries through
-        their target, mdetr.py:543-599) -- as the reference's (noun, pronoun) pairs do."""
-        losses, sides = LossDict(), []
-        for prefix, out, st in zip(("noun", "sth"), outputs, sts):
-            logits, boxes = self._stack(out)
-            L = logits.shape[0]
-            side = self._forward_static(out, logits, boxes, st, L)
-            losses.merge(side, prefix + "_")
-            sides.append((logits, boxes, self.last_match, L))
-        self.last_match = sides[1][2]
-        if getattr(self.args, "nsthl2_loss", False):
-            feats = []
-            for mc, st in zip(memory_cache, sts):
-                text = mc["text_memory"].permute(1, 0, 2)
-                feats.append((st.distill.W_span.to(text.dtype).unsqueeze(-1) * text).sum(1))
-            mo = sts[1].match_off
-            keep = (mo[1:] - mo[:-1]) > 0                                          # images in which the student's main layer matched a box
-            per_image = ((feats[1] - feats[0].detach()) ** 2).mean(1)
-            losses["loss_nsthl2"] = torch.where(keep, per_image, torch.zeros_like(per_image)).sum() / keep.sum().clamp(min=1)
-        if getattr(self.args, "softkd_loss", False):
-            L = sides[0][3]
             if engine.overlap_enabled() and getattr(self, "defer_pair_join", False):
                 # (opt-in: the CALLER must wait for `losses.join` before it reads a softkd value -- harness.CapturedDistillStep sets defer_pair_join around its own call; any
                 # other caller gets the whole dict on its own stream)
@@ -603,153 +538,134 @@ class SetCriterion(nn.Module):
                 side = engine.side_stream(sides[0][0].device, "softkd")
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    per_layer = self._loss_softkd_static(sides[0], sides[1], sts[0], sts[1])
+                    per_layer = softkd(sides[0], sides[1])
                 losses.join = side
             else:
-                per_layer = self._loss_softkd_static(sides[0], sides[1], sts[0], sts[1])
-            for l in range(L):
-                losses["loss_softkd" + ("" if l == L - 1 else f"_{l}")] = per_layer[l]
-            losses.groups.append((per_layer, {"loss_softkd" + ("" if l == L - 1 else f"_{l}"): l for l in range(L)}))
+                per_layer = softkd(sides[0], sides[1])
+            losses.merge(_per_layer("loss_softkd", per_layer))
         return losses
 
-    def _loss_softkd_static(self, noun, sth, st_n, st_s):
-        """_loss_softkd with every index built on the device from the StaticTargets offsets: the pair tables have the fixed capacity st.cap (matched pairs)
-        and Q per (layer, image) LSAP problem (unmatched pairs); the problem sizes Q - c_i are device vectors that toist_lsap reads; dead slots are
-        masked.  Every image's row count c_i + (Q - c_i) is Q, so the batchmean / image-mean weights are the constant 1 / (Q B)."""
-        from . import kernels as k
-        from .matcher import check_lsap_status
-        (lg_n, bx_n, m_n, _), (lg_s, bx_s, m_s, _) = noun, sth
-        L, B, Q = lg_n.shape[0], lg_n.shape[1], lg_n.shape[2]
-        dev, cap = lg_n.device, st_n.cap
+    def _forward_pair(self, memory_cache, outputs, targets, positive_map):
+        """_pair_losses on the reference's targets: two lists of dicts."""
+        def softkd(noun, sth):
+            m_n, m_s = noun[2], sth[2]
+            if m_n.counts != m_s.counts:
+                raise ValueError("softkd needs the same number of targets on the noun and the pronoun side of every pair")
+            if m_n.match_off[-1] == 0:
+                # no pair in the batch: the [L, 0] views are shorter than the L * cap slots the core addresses -- hand it zero tables (every slot is dead)
+                idle = torch.zeros(noun[0].shape[0], 1, dtype=torch.int64, device=noun[0].device)
+                m_n = m_s = SimpleNamespace(src=idle, tgt=idle, match_off=[0])
+            # the problem sizes Q - c are known on the host here: the launch goes through matcher.lsap_blocks, which packs the pairs back to back -- problem
+            # (l, i) starts at l * (B Q - Mtot) + i Q - match_off[i]; the core reads Q slots per problem
+            L, B, Q = noun[0].shape[:3]
+            shapes = [(Q - c, Q - c) for _ in range(L) for c in noun[2].counts]
+            offsets = [(l * B + i) * Q * Q for l in range(L) for i in range(B)]
 
-        def make():
-            p = torch.arange(L * cap, dtype=torch.int64, device=dev)
-            s = torch.arange(L * B * Q, dtype=torch.int64, device=dev)
-            prob = s // Q
-            return (p, s % Q, prob // B, prob % B, torch.arange(L * B, dtype=torch.int64, device=dev) * (Q * Q), torch.arange(L * B, dtype=torch.int64, device=dev) * Q)
-        p, slot_s, slot_l, slot_b, offsets, out_off = _cached(("softkd_static", L, B, Q, cap, str(dev)), make)
-        mo = st_n.match_off.to(torch.int64)                                       # [B + 1] (the student's must be equal: same targets per image)
-        mtot = mo[B]
-        live = p < L * mtot
-        l_of = torch.div(p, mtot.clamp(min=1), rounding_mode="floor").clamp(max=L - 1)
-        j = p - l_of * mtot
-        img = torch.bucketize(j, mo[1:], right=True).clamp(max=B - 1)
+            def solve(cost):
+                ri, ci, _, _, status = matcher.lsap_blocks(cost, shapes, offsets, Q)
+                slot_s, slot_l, slot_b = _softkd_tables(L, B, Q, cost.device)[:3]
+                mo = noun[2].match_off_dev.to(torch.int64)
+                dense = (slot_l * (B * Q - mo[B]) + slot_b * Q - mo[slot_b] + slot_s).clamp(max=ri.numel() - 1)
+                return ri[dense], ci[dense], status
+            return _softkd(noun[:2] + (m_n,), sth[:2] + (m_s,), noun[2].match_off_dev, max(m_n.match_off[-1], 1), solve)
 
-        def binarise(lg):
-            pr = lg.float().softmax(-1)
-            return torch.cat([pr[..., :-1].sum(-1, keepdim=True), pr[..., -1:]], dim=-1)                  # [L,B,Q,2]
+        return self._pair_losses(
+            outputs, lambda i, out, logits, boxes: self._forward_list(out, logits, boxes, targets[i], positive_map[i]),
+            lambda i: noun_token_features(memory_cache[i]["text_memory"].permute(1, 0, 2), outputs[i].get("tokenized", memory_cache[i].get("tokenized")), targets[i]),
+            softkd)
 
-        def unmatched_first(m):
-            """[L,B,Q] query order with the unmatched queries first (ascending), the matched ones after."""
-            free = torch.ones(L * B * Q + 1, dtype=torch.int8, device=dev)
-            free.scatter_(0, torch.where(live, (l_of * B + img) * Q + m.src.reshape(-1)[:L * cap], torch.full_like(p, L * B * Q)), 0)
-            return torch.sort(free[:L * B * Q].view(L, B, Q), dim=-1, descending=True, stable=True).indices
+    def _forward_pair_static(self, memory_cache, outputs, sts):
+        """_pair_losses on two matcher.StaticTargets images (teacher, student), each carrying its distill.DistillTables: nothing depends on the batch's
+        target counts, captions or tasks -> one hipGraph for any batch, the step captured by harness.CapturedDistillStep.  The two sides must hold the
+        same number of targets per image (softkd pairs the matched queries through their target, mdetr.py:543-599) -- as the reference's (noun,
+        pronoun) pairs do."""
+        def softkd(noun, sth):
+            per_layer = _softkd(noun, sth, sts[0].match_off, sts[0].cap)
+            # the list path raises when the two sides of a pair hold different numbers of targets; here the counts live on the device: poison instead (NaN losses trip
+            # the loop's finite-loss guard, engine.py:212-215) -- harness.CapturedDistillStep.pack() already refuses such a batch on the host
+            same = (sts[0].match_off == sts[1].match_off).all()
+            return torch.where(same, per_layer, torch.full_like(per_layer, float("nan")))
 
-        p_n, p_s = binarise(lg_n).detach(), binarise(lg_s)
-        ord_n, ord_s = unmatched_first(m_n), unmatched_first(m_s)
-        take = lambda t, order: torch.gather(t, 2, order[..., None].expand(-1, -1, -1, t.shape[-1]))
-        fp_n, fp_s = take(p_n, ord_n), take(p_s, ord_s)                                                 # unmatched first
-        with torch.no_grad():
-            fb_n, fb_s = take(bx_n.float(), ord_n), take(bx_s.float(), ord_s)
-            cost_class = (fp_n[:, :, None, :, :] * (fp_n.log()[:, :, None, :, :] - fp_s.log()[:, :, :, None, :])).sum(-1)   # [L,B,S,T]
-            cost = (torch.cdist(fb_s, fb_n, p=1) + cost_class - _paired_giou_matrix(fb_s, fb_n)).contiguous()
-            n_b = (Q - (mo[1:] - mo[:-1])).to(torch.int32).repeat(L).contiguous()                       # [L*B] problem sizes, layer-major
+        def features(i):
+            text = memory_cache[i]["text_memory"].permute(1, 0, 2)
+            return (sts[i].distill.W_span.to(text.dtype).unsqueeze(-1) * text).sum(1)
+
+        return self._pair_losses(outputs, lambda i, out, logits, boxes: self._forward_static(out, logits, boxes, sts[i]), features, softkd)
+
+
+def _nsthl2(feats_noun, feats_sth, keep):
+    """mdetr.py:668-781: MSE between the student's and the (detached) teacher's mean noun-token text feature [B, d], over the images `keep` (bool [B],
+    device).  The rows left out are masked BEFORE the arithmetic, so a non-finite feature of theirs reaches neither the value nor a gradient -- what
+    indexing the kept rows gives."""
+    diff = torch.where(keep[:, None], feats_sth - feats_noun.detach(), torch.zeros_like(feats_sth))
+    return (diff ** 2).mean(1).sum() / keep.sum().clamp(min=1)
+
+
+def _softkd_tables(L, B, Q, dev):
+    """Constant tables of the L * B LSAP problems with Q pair slots each: slot, layer and image of every slot; cost offset and first slot of every problem."""
+    def make():
+        s = torch.arange(L * B * Q, dtype=torch.int64, device=dev)
+        prob = s // Q
+        return (s % Q, prob // B, prob % B, torch.arange(L * B, dtype=torch.int64, device=dev) * (Q * Q), torch.arange(L * B, dtype=torch.int64, device=dev) * Q)
+    return _cached(("softkd", L, B, Q, str(dev)), make)
+
+
+def _softkd(noun, sth, match_off, cap, solve=None):
+    """mdetr.py:543-599 for every decoder layer at once -> [L]: KL(student || teacher) on the binarised (object, no-object) probabilities -- matched
+    queries paired through their target, unmatched ones through an LSAP on a KL + L1 + GIoU cost (mdetr.py:520-541).  All layers x images are one
+    launch of the device LSAP kernel on blocks of one [L,B,Q,Q] cost tensor; no per-image Python work, no host sync.
+    noun, sth: (logits [L,B,Q,K], boxes [L,B,Q,4], assignment with .src / .tgt of >= L * cap elements) of the teacher and the student; match_off:
+    device int32 [B + 1], the same on both sides.  Every index is built on the device from match_off: the pair tables have the fixed capacity `cap`
+    (matched pairs) and Q per (layer, image) LSAP problem (unmatched pairs); the problem sizes Q - c_i are device vectors that toist_lsap reads;
+    dead slots are masked.  Every image's row count c_i + (Q - c_i) is Q, so the batchmean / image-mean weights are the constant 1 / (Q B)."""
+    from .matcher import check_lsap_status
+    (lg_n, bx_n, m_n), (lg_s, bx_s, m_s) = noun[:3], sth[:3]
+    L, B, Q = lg_n.shape[0], lg_n.shape[1], lg_n.shape[2]
+    dev = lg_n.device
+
+    slot_s, slot_l, slot_b, offsets, out_off = _softkd_tables(L, B, Q, dev)
+    live, l_of, _, img, mo = pair_slots(match_off, L, B, cap)
+
+    def binarise(lg):
+        pr = lg.float().softmax(-1)
+        return torch.cat([pr[..., :-1].sum(-1, keepdim=True), pr[..., -1:]], dim=-1)                  # [L,B,Q,2]
+
+    def unmatched_first(m):
+        """[L,B,Q] query order with the unmatched queries first (ascending), the matched ones after."""
+        free = torch.ones(L * B * Q + 1, dtype=torch.int8, device=dev)
+        free.scatter_(0, torch.where(live, (l_of * B + img) * Q + m.src.reshape(-1)[:L * cap], torch.full_like(img, L * B * Q)), 0)
+        return torch.sort(free[:L * B * Q].view(L, B, Q), dim=-1, descending=True, stable=True).indices
+
+    p_n, p_s = binarise(lg_n).detach(), binarise(lg_s)
+    ord_n, ord_s = unmatched_first(m_n), unmatched_first(m_s)
+    take = lambda t, order: torch.gather(t, 2, order[..., None].expand(-1, -1, -1, t.shape[-1]))
+    fp_n, fp_s = take(p_n, ord_n), take(p_s, ord_s)                                                 # unmatched first
+    with torch.no_grad():
+        fb_n, fb_s = take(bx_n.float(), ord_n), take(bx_s.float(), ord_s)
+        cost_class = (fp_n[:, :, None, :, :] * (fp_n.log()[:, :, None, :, :] - fp_s.log()[:, :, :, None, :])).sum(-1)   # [L,B,S,T]
+        cost = (torch.cdist(fb_s, fb_n, p=1) + cost_class - _paired_giou_matrix(fb_s, fb_n)).contiguous()
+        n_b = (Q - (mo[1:] - mo[:-1])).to(torch.int32).repeat(L).contiguous()                       # [L*B] problem sizes, layer-major
+        if solve is not None:       # a front end that knows the problem sizes on the host: solve(cost) -> (rows, cols, status), Q slots per problem
+            rows, cols, status = solve(cost)
+        else:
             rows = torch.zeros(L * B * Q, dtype=torch.int64, device=dev)
             cols = torch.zeros(L * B * Q, dtype=torch.int64, device=dev)
             status = torch.zeros(L * B, dtype=torch.int32, device=dev)
             k.lsap(cost, offsets, n_b, n_b, L * B, Q, Q, Q * Q, out_off, rows, cols, status, ld=Q)
-            valid = slot_s < n_b.to(torch.int64)[slot_l * B + slot_b]
-        kl_fp = _kl_rows(fp_n[slot_l, slot_b, cols], fp_s[slot_l, slot_b, rows])                       # [L*B*Q]; dead slots read row 0 and are masked
-        kl_fp = torch.where(valid, kl_fp, torch.zeros_like(kl_fp))
+        valid = slot_s < n_b.to(torch.int64)[slot_l * B + slot_b]
+    kl_fp = _kl_rows(fp_n[slot_l, slot_b, cols], fp_s[slot_l, slot_b, rows])                       # [L*B*Q]; dead slots read row 0 and are masked
+    kl_fp = torch.where(valid, kl_fp, torch.zeros_like(kl_fp))
 
-        def by_target(pr, m):
-            """[L, cap, 2]: the probabilities of the query matched to target t of image i at position match_off[i] + t; dead rows (0.5, 0.5) on both sides: KL 0"""
-            vals = pr.reshape(L * B * Q, 2)[torch.where(live, (l_of * B + img) * Q + m.src.reshape(-1)[:L * cap], torch.zeros_like(p))]
-            dst = torch.where(live, l_of * cap + mo[img] + m.tgt.reshape(-1)[:L * cap], torch.full_like(p, L * cap))
-            out = torch.full((L * cap + 1, 2), 0.5, device=dev, dtype=pr.dtype)
-            return out.index_copy(0, dst, vals)[:L * cap].view(L, cap, 2)
-        kl_tp = _kl_rows(by_target(p_n, m_n), by_target(p_s, m_s))                                      # [L, cap]
-        per_layer = (kl_tp.sum(1) + kl_fp.view(L, B * Q).sum(1)) / float(Q * B)
-        # the list path raises when the two sides of a pair hold different numbers of targets; here the counts live on the device: poison instead (NaN losses trip
-        # the loop's finite-loss guard, engine.py:212-215) -- harness.CapturedDistillStep.pack() already refuses such a batch on the host
-        same = (st_n.match_off == st_s.match_off).all()
-        per_layer = torch.where(same, per_layer, torch.full_like(per_layer, float("nan")))
-        check_lsap_status(status, defer=True)
-        return per_layer
-
-    def _loss_nsthl2(self, memory_cache, outputs, targets, match_sth):
-        """mdetr.py:668-781: MSE between the student's and the (detached) teacher's mean noun-token text feature, over
-        the images in which the student's main layer matched at least one box."""
-        feats = []
-        for mc, out, tgt in zip(memory_cache, outputs, targets):
-            feats.append(noun_token_features(mc["text_memory"].permute(1, 0, 2), out.get("tokenized", mc.get("tokenized")), tgt))
-        keep = [i for i, c in enumerate(match_sth.counts) if c > 0]
-        if not keep:
-            return torch.zeros((), device=feats[0].device)
-        idx = _cached(("keep", tuple(keep), str(feats[0].device)), lambda: torch.as_tensor(keep, device=feats[0].device))
-        per_image = ((feats[1][idx] - feats[0][idx].detach()) ** 2).mean(1)     # F.mse_loss per image
-        return per_image.sum() / len(keep)
-
-    def _loss_softkd(self, noun, sth):
-        """mdetr.py:543-599 for every decoder layer at once -> [L]: KL(student || teacher) on the binarised (object,
-        no-object) probabilities -- matched queries paired through their target, unmatched ones through an LSAP on a
-        KL + L1 + GIoU cost (mdetr.py:520-541).  All layers x images are one launch of the device LSAP kernel on blocks
-        of one [L,B,Q,Q] cost tensor; no per-image Python work, no host sync except the final status check."""
-        from .matcher import check_lsap_status, lsap_blocks
-        (lg_n, bx_n, m_n, _), (lg_s, bx_s, m_s, _) = noun, sth
-        L, B, Q = lg_n.shape[0], lg_n.shape[1], lg_n.shape[2]
-        dev = lg_n.device
-        if m_n.counts != m_s.counts:
-            raise ValueError("softkd needs the same number of targets on the noun and the pronoun side of every pair")
-
-        def binarise(lg):
-            p = lg.float().softmax(-1)
-            return torch.cat([p[..., :-1].sum(-1, keepdim=True), p[..., -1:]], dim=-1)                  # [L,B,Q,2]
-
-        def unmatched_first(m):
-            """[L,B,Q] query order with the unmatched queries first (ascending), the matched ones after."""
-            free = torch.ones(L, B, Q, dtype=torch.int8, device=dev)
-            if m.src.shape[1]:
-                b_of = _pair_image_index(tuple(m.counts), dev)                                         # [Mtot]
-                free.view(L, B * Q).scatter_(1, b_of[None, :] * Q + m.src, 0)        # (scatter: advanced-index assignment synchronises the host)
-            return torch.sort(free, dim=-1, descending=True, stable=True).indices
-
-        p_n, p_s = binarise(lg_n).detach(), binarise(lg_s)
-        ord_n, ord_s = unmatched_first(m_n), unmatched_first(m_s)
-        take = lambda t, order: torch.gather(t, 2, order[..., None].expand(-1, -1, -1, t.shape[-1]))
-        fp_n, fp_s = take(p_n, ord_n), take(p_s, ord_s)                                                 # unmatched first
-        with torch.no_grad():
-            fb_n, fb_s = take(bx_n.float(), ord_n), take(bx_s.float(), ord_s)
-            cost_class = (fp_n[:, :, None, :, :] * (fp_n.log()[:, :, None, :, :] - fp_s.log()[:, :, :, None, :])).sum(-1)   # [L,B,S,T]
-            cost = (torch.cdist(fb_s, fb_n, p=1) + cost_class - _paired_giou_matrix(fb_s, fb_n)).contiguous()
-        shapes = [(Q - c, Q - c) for _ in range(L) for c in m_n.counts]
-        offsets = [(l * B + i) * Q * Q for l in range(L) for i in range(B)]
-        rows, cols, out_off, pairs, status = lsap_blocks(cost, shapes, offsets, Q)
-        # unmatched pairs: student row `rows`, teacher row `cols` of problem (l, i)
-        pl, pb = _problem_index(L, tuple(pairs), dev)
-        kl_fp = _kl_rows(fp_n[pl, pb, cols], fp_s[pl, pb, rows])                                        # [sum pairs]
-        # matched pairs: both sides indexed by target -> position match_off[i] + tgt inside the image's run
-        def by_target(p, m):
-            out = torch.zeros(L, max(m.src.shape[1], 1), 2, device=dev, dtype=p.dtype)
-            if m.src.shape[1]:
-                b_of = _pair_image_index(tuple(m.counts), dev)
-                base = _pair_image_offset(tuple(m.counts), dev)
-                lidx = torch.arange(L, device=dev)[:, None].expand_as(m.src)
-                out = out.index_put((lidx, base[None, :] + m.tgt), p[lidx, b_of[None, :].expand_as(m.src), m.src])
-            return out
-        kl_tp = _kl_rows(by_target(p_n, m_n), by_target(p_s, m_s))                                      # [L, Mtot]
-        # per image: batchmean over its (matched + assigned unmatched) rows; then mean over images
-        n_rows = [c + (Q - c) for c in m_n.counts]
-        counts = tuple(m_n.counts)
-        w_tp = _cached(("w_tp", counts, Q, B, str(dev)),
-                       lambda: torch.tensor([1.0 / (n_rows[i] * B) for i, c in enumerate(counts) for _ in range(c)] or [0.0], device=dev))
-        w_fp = _cached(("w_fp", counts, L, Q, B, str(dev)),
-                       lambda: torch.tensor([1.0 / (n_rows[i] * B) for _ in range(L) for i, c in enumerate(counts) for _ in range(Q - c)] or [0.0], device=dev))
-        per_layer = (kl_tp * w_tp[None, :kl_tp.shape[1]]).sum(1) if m_n.src.shape[1] else torch.zeros(L, device=dev)
-        per_layer = per_layer + (kl_fp * w_fp[:kl_fp.shape[0]]).view(L, -1).sum(1)
-        check_lsap_status(status, defer=True)      # an invalid cost block raises at the next call (no host sync inside the step)
-        return per_layer
-
+    def by_target(pr, m):
+        """[L, cap, 2]: the probabilities of the query matched to target t of image i at position match_off[i] + t; dead rows (0.5, 0.5) on both sides: KL 0"""
+        vals = pr.reshape(L * B * Q, 2)[torch.where(live, (l_of * B + img) * Q + m.src.reshape(-1)[:L * cap], torch.zeros_like(img))]
+        dst = torch.where(live, l_of * cap + mo[img] + m.tgt.reshape(-1)[:L * cap], torch.full_like(img, L * cap))
+        out = torch.full((L * cap + 1, 2), 0.5, device=dev, dtype=pr.dtype)
+        return out.index_copy(0, dst, vals)[:L * cap].view(L, cap, 2)
+    kl_tp = _kl_rows(by_target(p_n, m_n), by_target(p_s, m_s))                                      # [L, cap]
+    per_layer = (kl_tp.sum(1) + kl_fp.view(L, B * Q).sum(1)) / float(Q * B)
+    check_lsap_status(status, defer=True)      # an invalid cost block raises at the next call (no host sync inside the step)
+    return per_layer
 
 def _kl_rows(teacher, student):
     """sum_c t * (log t - log s) per row, with F.kl_div's 0 * log 0 = 0 convention."""
@@ -782,6 +698,7 @@ _INDEX_CACHE = {}
 
 
 def _cached(key, make):
+    """Constant index tables (functions of shapes alone), kept on the device."""
     ent = _INDEX_CACHE.get(key)
     if ent is None:
         if len(_INDEX_CACHE) > 128:
@@ -790,25 +707,19 @@ def _cached(key, make):
     return ent
 
 
-def _pair_image_index(counts, dev):
-    """[Mtot] image index of every matched pair."""
-    return _cached(("img", counts, str(dev)), lambda: torch.tensor([i for i, c in enumerate(counts) for _ in range(c)], dtype=torch.int64, device=dev))
+def _layer_key(name, l, L):
+    """The reference's key of decoder layer l of L: the main (last) layer keeps the bare name, auxiliary layer l gets the suffix _l (mdetr.py:1009-1019)."""
+    return name if l == L - 1 else f"{name}_{l}"
 
 
-def _pair_image_offset(counts, dev):
-    """[Mtot] first position of the pair's image inside the [Mtot] run."""
-    offs = [sum(counts[:i]) for i in range(len(counts))]
-    return _cached(("off", counts, str(dev)), lambda: torch.tensor([offs[i] for i, c in enumerate(counts) for _ in range(c)], dtype=torch.int64, device=dev))
-
-
-def _problem_index(L, pairs, dev):
-    """(layer, image) of every LSAP output pair; problems are ordered layer-major."""
-    B = len(pairs) // L
-    def make():
-        pl = [l for l in range(L) for i in range(B) for _ in range(pairs[l * B + i])]
-        pb = [i for l in range(L) for i in range(B) for _ in range(pairs[l * B + i])]
-        return torch.tensor(pl, dtype=torch.int64, device=dev), torch.tensor(pb, dtype=torch.int64, device=dev)
-    return _cached(("prob", L, pairs, str(dev)), make)
+def _per_layer(name, vals, group=True):
+    """[L] stacked per-layer values -> LossDict {name_0, .., name}: the scalars are views of `vals`, which travels as one group (weighted_total)."""
+    L = vals.shape[0]
+    index = {_layer_key(name, l, L): l for l in range(L)}
+    out = LossDict((key, vals[l]) for key, l in index.items())
+    if group:
+        out.groups.append((vals, index))
+    return out
 
 
 class LossDict(dict):

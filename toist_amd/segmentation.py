@@ -20,6 +20,7 @@ from . import engine, functions
 from . import kernels as k
 from . import ops
 from .backbone import nearest_mask
+from .matcher import pair_slots
 from .misc import NestedTensor
 
 BF16 = torch.bfloat16
@@ -522,64 +523,38 @@ class _MaskLossFn(torch.autograd.Function):
         return (dpred,) + none
 
 
-_OFFSETS = {}
-_SEG = {}
-
-
-def _match_offsets(counts, sizes, dev):
-    """Per matched pair: image index and first target row of that image (device int64, cached per batch signature so
-    a steady-state step does no host-to-device copy -- needed for hipGraph capture)."""
-    key = (counts, sizes, str(dev))
-    ent = _OFFSETS.get(key)
-    if ent is None:
-        if len(_OFFSETS) > 64:
-            _OFFSETS.clear()
-        b_idx = torch.cat([torch.full((c,), i, dtype=torch.int64) for i, c in enumerate(counts)]).to(dev)
-        t_base = torch.cat([torch.full((c,), sum(sizes[:i]), dtype=torch.int64) for i, c in enumerate(counts)]).to(dev)
-        ent = _OFFSETS[key] = (b_idx, t_base)
-    return ent
-
-
-_ARANGE = {}
-
-
-def mask_losses_static(outputs, st, match, layer, L):
-    """mask_losses on a matcher.StaticTargets image: the pair table has the fixed capacity st.cap; which slots are live, which image a
-    pair belongs to and where layer `layer`'s pairs start (the matcher packs the layers with stride match_off[B]) are all computed ON THE
-    DEVICE from st.match_off / st.tgt_off, so the launches are the same for every batch (hipGraph replay)."""
-    pred = outputs["pred_masks"].float().contiguous()                      # [B,Q,hm,wm]
+def _mask_losses(pred_masks, match, layer, L, cap, match_off, tgt_off, gt, num_boxes, TH, TW, valid_hw=None):
+    """SetCriterion.loss_masks (mdetr.py:827-853) on the device-resident assignment of `layer`.  The pair table has the capacity `cap`; which slots
+    are live, which image a pair belongs to and where layer `layer`'s pairs start (the matcher packs the layers with stride match_off[B]) are all
+    computed ON THE DEVICE from match_off / tgt_off, so the launches are the same for every batch (hipGraph replay)."""
+    pred = pred_masks.float().contiguous()                                  # [B,Q,hm,wm]
     B, Q = pred.shape[:2]
-    dev = pred.device
-    cap = st.cap
-    if st.masks is None:
-        raise ValueError("mask losses on StaticTargets need StaticTargets(mask_hw=(H, W))")
-    TH, TW = st.mask_hw
-    j = _ARANGE.get((cap, str(dev)))
-    if j is None:
-        j = _ARANGE[(cap, str(dev))] = torch.arange(cap, dtype=torch.int64, device=dev)
-    mo = st.match_off.to(torch.int64)
-    mtot = mo[B]
-    live = j < mtot
-    pos = (layer * mtot + j).clamp(max=L * cap - 1)
+    live, _, j, img, mo = pair_slots(match_off, 1, B, cap)
+    pos = (layer * mo[B] + j).clamp(max=L * cap - 1)
     src = match.src.reshape(-1).gather(0, pos)
     tgt = match.tgt.reshape(-1).gather(0, pos)
-    img = torch.bucketize(j, mo[1:], right=True).clamp(max=B - 1)        # pair j belongs to the image whose run [match_off[i], match_off[i+1]) holds it
     pred_row = torch.where(live, img * Q + src, torch.full_like(src, -1)).to(torch.int32)
-    gt_row = torch.where(live, st.tgt_off.to(torch.int64)[img] + tgt, torch.zeros_like(tgt)).to(torch.int32)
-    sink = getattr(outputs["pred_masks"], "toist_matched_rows", None)
+    gt_row = torch.where(live, tgt_off.to(torch.int64)[img] + tgt, torch.zeros_like(tgt)).to(torch.int32)
+    sink = getattr(pred_masks, "toist_matched_rows", None)
     seg = mo[:B + 1].to(torch.int32).contiguous() if sink is not None else None      # slots [match_off[i], match_off[i+1]) belong to image i
-    vals = _MaskLossFn.apply(pred.view(B * Q, pred.shape[-2], pred.shape[-1]), pred_row.contiguous(), st.masks, gt_row.contiguous(), st.num_boxes.reshape(()).float(), TH, TW,
-                             sink, seg, getattr(st, "valid_hw", None))
+    vals = _MaskLossFn.apply(pred.view(B * Q, pred.shape[-2], pred.shape[-1]), pred_row.contiguous(), gt, gt_row.contiguous(), num_boxes, TH, TW, sink, seg, valid_hw)
     return {"loss_mask": vals[0], "loss_dice": vals[1]}
 
 
+def mask_losses_static(outputs, st, match, layer, L):
+    """The mask losses on a matcher.StaticTargets image: fixed capacity st.cap, ground truth and its valid corner from the image."""
+    if st.masks is None:
+        raise ValueError("mask losses on StaticTargets need StaticTargets(mask_hw=(H, W))")
+    TH, TW = st.mask_hw
+    return _mask_losses(outputs["pred_masks"], match, layer, L, st.cap, st.match_off, st.tgt_off, st.masks, st.num_boxes.reshape(()).float(), TH, TW,
+                        getattr(st, "valid_hw", None))
+
+
 def mask_losses(outputs, targets, match, layer, num_boxes):
-    """SetCriterion.loss_masks (mdetr.py:827-853) on the device-resident assignment of `layer`."""
-    pred = outputs["pred_masks"].float().contiguous()                      # [B,Q,hm,wm]
-    B, Q = pred.shape[:2]
-    dev = pred.device
+    """The mask losses on the reference's targets (list of dicts with `masks`): the pair table is exactly the batch's Mtot pairs."""
+    pred = outputs["pred_masks"]
     if match.src.shape[1] == 0:
-        z = pred.sum() * 0
+        z = pred.float().sum() * 0
         return {"loss_mask": z, "loss_dice": z}
     TH = max(int(t["masks"].shape[-2]) for t in targets)
     TW = max(int(t["masks"].shape[-1]) for t in targets)
@@ -589,19 +564,5 @@ def mask_losses(outputs, targets, match, layer, num_boxes):
         if m.shape[-2:] != (TH, TW):
             m = torch.nn.functional.pad(m, (0, TW - m.shape[-1], 0, TH - m.shape[-2]))
         rows.append(m)
-    gt = torch.cat(rows).contiguous()
-    b_idx, t_base = _match_offsets(tuple(match.counts), tuple(match.sizes), dev)
-    pred_row = (b_idx * Q + match.src[layer]).to(torch.int32)
-    gt_row = (t_base + match.tgt[layer]).to(torch.int32)
-    nb = num_boxes.reshape(()).float() if torch.is_tensor(num_boxes) else torch.tensor(float(num_boxes), device=dev)
-    sink = getattr(outputs["pred_masks"], "toist_matched_rows", None)
-    seg = None
-    if sink is not None:
-        counts = tuple(match.counts)
-        seg = _SEG.get((counts, str(dev)))
-        if seg is None:
-            if len(_SEG) > 64:
-                _SEG.clear()
-            seg = _SEG[(counts, str(dev))] = torch.tensor([sum(counts[:i]) for i in range(len(counts) + 1)], dtype=torch.int32, device=dev)
-    vals = _MaskLossFn.apply(pred.view(B * Q, pred.shape[-2], pred.shape[-1]), pred_row.contiguous(), gt, gt_row.contiguous(), nb, TH, TW, sink, seg)
-    return {"loss_mask": vals[0], "loss_dice": vals[1]}
+    nb = num_boxes.reshape(()).float() if torch.is_tensor(num_boxes) else torch.tensor(float(num_boxes), device=pred.device)
+    return _mask_losses(pred, match, layer, match.src.shape[0], match.src.shape[1], match.match_off_dev, match.tgt_off_dev, torch.cat(rows).contiguous(), nb, TH, TW)

@@ -293,6 +293,18 @@ TOIST_API int toist_contrastive_bwd_ws(const float* proj_queries, const float* p
                           const int32_t* match_off, const int64_t* src_idx, const int64_t* tgt_idx, const float* num_boxes, int L,
                           int B, int Q, int T, int D, float temperature, const float* upstream, float* dproj_queries,
                           float* dproj_tokens, float* workspace, void* stream);
+/* toist_contrastive_fwd / _bwd_ws for a replayed graph whose captions are padded to T tokens (mdetr.py:601-666 takes its log-sum-exp over every
+ * token column, :646-663, so a padded column would change the loss): live_tokens = one int32 in DEVICE memory, read by the kernel, refilled
+ * between replays.  Tl = clamp(*live_tokens, 0, T) columns are live: the launch equals the launch on proj_tokens[:, :Tl] with T = Tl --
+ * columns t >= Tl form no logit, enter no log-sum-exp, column term or positive count and give nothing to dproj_queries; their rows of
+ * dproj_tokens and of the workspace are written as zeros (dproj_tokens: live rows +=, caller zeroes; dead rows = 0). */
+TOIST_API int toist_contrastive_fwd_live(const float* proj_queries, const float* proj_tokens, const uint64_t* tok_mask, const int32_t* tgt_off,
+                          const int32_t* match_off, const int64_t* src_idx, const int64_t* tgt_idx, const float* num_boxes, int L,
+                          int B, int Q, int T, int D, float temperature, const int32_t* live_tokens, float* losses, void* stream);
+TOIST_API int toist_contrastive_bwd_ws_live(const float* proj_queries, const float* proj_tokens, const uint64_t* tok_mask, const int32_t* tgt_off,
+                          const int32_t* match_off, const int64_t* src_idx, const int64_t* tgt_idx, const float* num_boxes, int L,
+                          int B, int Q, int T, int D, float temperature, const int32_t* live_tokens, const float* upstream,
+                          float* dproj_queries, float* dproj_tokens, float* workspace, void* stream);
 TOIST_API int toist_l2norm_fwd(const float* x, int rows, int D, float* y, void* stream);
 TOIST_API int toist_l2norm_bwd(const float* x, const float* dy, int rows, int D, float* dx, void* stream);
 

@@ -437,7 +437,8 @@ class CapturedEvalStep(_CapturedStep):
 class CapturedDistillStep(_CapturedStep):
     """The reference's distillation step (engine.py:152-204: teacher encode -> memory-bank update + prototypes -> teacher decode -> student encode ->
     prototype of 'something' -> student decode -> paired SetCriterion with softkd / nsthl2 + cluster losses -> backward -> clip + AdamW + EMA of both
-    models) replayed from ONE hipGraph for ANY batch of a fixed shape (round 6).
+    models) replayed from ONE hipGraph for ANY batch of a fixed shape (round 6) -- or, built without image_hw / tokens, from one
+    hipGraph per input-shape BUCKET for the batches of a real loader.
 
     What used to tie a captured graph to its batch -- per-image target counts (LSAP problem sizes (Q - c)^2, pair tables), the grouping of the images by
     task (k-means groups, one memory-bank LSAP per task), the token tables of the captions (noun spans, the word 'something') -- now lives in
@@ -449,7 +450,18 @@ class CapturedDistillStep(_CapturedStep):
     tokenized=[..] * 2 (BatchEncodings with char_to_token), targets=[..] * 2, captions=[..] * 2, positive_map=[..] * 2) -> total loss (device scalar).
     The first step runs eagerly (a real training step) and is captured right after; later steps = the H2D copies of the inputs + one graph launch.
     Requirements (checked): one process, a batch no larger than a memory bank, both sides with the same number of targets per image (the reference's
-    pairs share their boxes), images / captions of the constructor's shape.
+    pairs share their boxes), images / captions of the constructor's shape when it was given one.
+
+    Shape buckets: the reference resizes and crops every image at random, pads a batch to its largest image and tokenises the noun and the pronoun
+    caption separately (datasets/tdod.py:301-325), so no two batches of a real loader share a shape and the two sides of a batch differ in caption
+    length.  The bucket of a batch is (Hp, Wp, Lp): the pair's padded image size rounded up to `pad_hw` (the extra pixels are masked, as in
+    CapturedTrainStep) and the LONGER caption length of the two sides rounded up to `pad_tokens`.  Padded token positions are masked in every
+    attention and carry zero weights in the caption tables; loss_contrastive_align, which has no attention mask (mdetr.py:646-663), reads each
+    side's OWN token count from the live-token word of that side's matcher.LiveStaticTargets (toist_contrastive_fwd_live), so a bucket gives the losses of the
+    unpadded batch.  Each bucket holds both sides' static inputs, StaticTargets and DistillTables and its graph, built on first use and kept in an
+    LRU of `max_graphs`; what is NOT per bucket: the memory banks, cluster centres and plan_fill's host mirror (one ClusterCriterion), the FillTables
+    image (attached to every bucket's tables), the optimizers, the guard words and the programs' reused gradient buffers.  plan_fill runs once per
+    step in step order, whichever bucket serves the step.
 
     The memory state is the device's business: the same graph serves a fresh run (every bank filling, FIFO pushes, k-means from randomly drawn bank
     rows), the step on which a task's full_label flips, the steady state (nearest replacement, k-means from the stored centres) and --fifo_memory.
@@ -463,79 +475,129 @@ class CapturedDistillStep(_CapturedStep):
     then the step is skipped on the device and resolve_skipped() reports it (the loss word and the decoder status word are shared by the two tails, so
     they skip together; a gradient norm that is not finite in one model only skips that model's update)."""
 
-    def __init__(self, model, model_noun, criterion, cluster_criterion, optimizers, weight_dict, *, batch, image_hw, tokens, max_targets_per_image=16, device=None,
-                 stream=None):
-        """stream: the HIP stream the steps run (and the graph is captured) on; pass the stream earlier eager steps of the same models ran on, if any -- the programs'
+    def __init__(self, model, model_noun, criterion, cluster_criterion, optimizers, weight_dict, *, batch, image_hw=None, tokens=None,
+                 max_targets_per_image=16, pad_hw=64, pad_tokens=8, max_graphs=4, device=None, stream=None):
+        """image_hw + tokens: the one shape the step serves (one graph).  Neither: the step is BUCKETED (class docstring) -- pad_hw, pad_tokens and
+        max_graphs are CapturedTrainStep's.
+        stream: the HIP stream the steps run (and the graph is captured) on; pass the stream earlier eager steps of the same models ran on, if any -- the programs'
         reused gradient buffers and the launchers' per-stream scratch must not change streams between eager steps and the capture."""
+        if (image_hw is None) != (tokens is None):
+            raise ValueError("CapturedDistillStep: pass image_hw AND tokens (one fixed shape, one graph) or neither (shape buckets)")
         from . import engine
-        from .distill import DistillTables, FillTables
-        from .matcher import StaticTargets
+        from .distill import FillTables
+        from .matcher import LiveStaticTargets
         self.model, self.model_noun, self.criterion, self.cluster_criterion = model, model_noun, criterion, cluster_criterion
         self.optimizers, self.weight_dict = list(optimizers), weight_dict
-        self.B, self.hw, self.L = int(batch), (int(image_hw[0]), int(image_hw[1])), int(tokens)
+        self.B, self.max_t, self.bucketed = int(batch), int(max_targets_per_image), image_hw is None
+        self.pad_hw, self.pad_tokens, self.max_graphs = (int(pad_hw), int(pad_tokens), int(max_graphs)) if self.bucketed else (1, 1, 1)
         dev = self.device = torch.device(device) if device is not None else next(model.parameters()).device
         det = getattr(model, "detr", model)
-        Q = det.query_embed.weight.shape[0]
+        self.num_queries = det.query_embed.weight.shape[0]
         self.contrastive = bool(getattr(det, "contrastive_align_loss", False))
-        self.sides = []
-        for pronoun in (False, True):
-            st = StaticTargets(self.B, int(max_targets_per_image), Q, 256, dev)
-            st.distill = DistillTables(self.B, self.L, dev, pronoun_side=pronoun)
-            # (every batch has exactly this shape and overwrites the whole mask)
-            self.sides.append({**static_inputs(self.B, *self.hw, self.L, _pad_id(model), dev, mask_fill=False), "targets": st})
         self.fill = None                                   # (without a cluster criterion there is no memory to fill)
-        if cluster_criterion is not None:
+        if cluster_criterion is not None:                  # ONE image of the k-means starts (a function of B and K alone), attached to every bucket's pair of tables
             self.fill = FillTables(self.B, cluster_criterion.cluster_num, cluster_criterion.memory_size, dev)
-            self.fill.attach(self.sides[0]["targets"].distill, self.sides[1]["targets"].distill)
         self._init_capture_state(side=stream if stream is not None else torch.cuda.Stream(device=dev))
-        self._ent = self._buckets[(*self.hw, self.L)] = dict(_NO_GRAPH)        # the one bucket
+        self._pack_tb = {}                                 # Lp -> the (noun, pronoun) DistillTables whose pack() builds the host images of that caption length
+        if self.bucketed:
+            self.hw = self.L = self.sides = None
+            # pack() must not depend on which buckets exist (it may run ahead of step(), in a loader): the targets' host image has one layout for every
+            # bucket, so one StaticTargets packs both sides of all of them; the caption tables depend on Lp and get host-only packers on first use
+            self._pack_st = [LiveStaticTargets(self.B, self.max_t, self.num_queries, 256, dev)] * 2
+        else:
+            self.hw, self.L = (int(image_hw[0]), int(image_hw[1])), int(tokens)
+            self._ent = self._entry((*self.hw, self.L))    # the one bucket
+            self.sides = self._ent["sides"]
+            self._pack_st = [side["targets"] for side in self.sides]
+            self._pack_tb[self.L] = [side["targets"].distill for side in self.sides]
         if kernels.SEED_DEV is None:
             kernels.SEED_DEV = torch.zeros(1, dtype=torch.int64, device=dev)
         engine.REUSE_GRAD_BUFFERS = True
         self._init_guard(self.optimizers)
 
+    def _static_inputs(self, key):
+        """Both sides' static inputs of one bucket.  Fixed shape: every batch overwrites the whole mask (mask_fill=False) and no caption is padded.
+        Bucketed: the usual blank-is-padding inputs, and each side's targets are a LiveStaticTargets, whose live-token word keeps the padded token columns
+        out of loss_contrastive_align."""
+        from .distill import DistillTables
+        from .matcher import LiveStaticTargets, StaticTargets
+        Hp, Wp, Lp = key
+        sides = []
+        for pronoun in (False, True):
+            st = (LiveStaticTargets if self.bucketed else StaticTargets)(self.B, self.max_t, self.num_queries, 256, self.device)
+            st.distill = DistillTables(self.B, Lp, self.device, pronoun_side=pronoun)
+            sides.append({**static_inputs(self.B, Hp, Wp, Lp, _pad_id(self.model), self.device, mask_fill=self.bucketed), "targets": st})
+        if self.fill is not None:
+            self.fill.attach(sides[0]["targets"].distill, sides[1]["targets"].distill)
+        return {"sides": sides, **_NO_GRAPH}
+
+    def bucket_of_pair(self, batch):
+        """(Hp, Wp, Lp) of a pair batch (host logic only): the pair's padded image size rounded up to pad_hw -- the two sides are the same images --,
+        the LONGER of the two sides' captions rounded up to pad_tokens."""
+        shapes = [tuple(s.tensors.shape) for s in batch["samples"]]
+        if shapes[0] != shapes[1]:
+            raise ValueError(f"CapturedDistillStep: the two sides of a pair are the same images, got {shapes[0]} (noun) and {shapes[1]} (pronoun)")
+        if shapes[0][0] != self.B or any(int(t["input_ids"].shape[0]) != self.B for t in batch["tokenized"]):
+            raise ValueError(f"CapturedDistillStep was built for batches of {self.B} pairs (got {shapes[0][0]} images, "
+                             f"{[int(t['input_ids'].shape[0]) for t in batch['tokenized']]} captions)")
+        up = lambda v, m: (int(v) + m - 1) // m * m
+        return up(shapes[0][2], self.pad_hw), up(shapes[0][3], self.pad_hw), up(max(int(t["input_ids"].shape[1]) for t in batch["tokenized"]), self.pad_tokens)
+
+    def _table_packers(self, Lp):
+        tb = self._pack_tb.get(Lp)
+        if tb is None:
+            from .distill import DistillTables
+            tb = self._pack_tb[Lp] = [DistillTables(self.B, Lp, "cpu", pronoun_side=pronoun) for pronoun in (False, True)]
+            for t in tb:
+                t._pin = self.device.type == "cuda"        # (host-only instances: their pack() results are what step() copies to the bucket's tables)
+        return tb
+
     def pack(self, batch):
         """Host half of a step (no device work, no synchronisation when the batch's targets are host tensors: run it in the loader): the pinned images of both
-        sides' StaticTargets and DistillTables, next to the batch's image / token tensors.  step(packed=...) consumes it."""
+        sides' StaticTargets and DistillTables, next to the batch's image / token tensors and the batch's bucket ("key").  step(packed=...) consumes it."""
         if [len(t["boxes"]) for t in batch["targets"][0]] != [len(t["boxes"]) for t in batch["targets"][1]]:
             raise ValueError("softkd needs the same number of targets on the noun and the pronoun side of every pair")
+        key = self.bucket_of_pair(batch) if self.bucketed else (*self.hw, self.L)
+        tables = self._table_packers(key[2])
         out = []
-        for i, side in enumerate(self.sides):
+        for i in range(2):
             samples, tok, targets = batch["samples"][i], batch["tokenized"][i], batch["targets"][i]
-            if tuple(samples.tensors.shape) != (self.B, 3, *self.hw) or tuple(tok["input_ids"].shape) != (self.B, self.L):
+            if not self.bucketed and (tuple(samples.tensors.shape) != (self.B, 3, *self.hw) or tuple(tok["input_ids"].shape) != (self.B, self.L)):
                 raise ValueError(f"CapturedDistillStep was built for {self.B} x 3 x {self.hw[0]} x {self.hw[1]} images and {self.L}-token captions")
             host_t = [{k_: (v.cpu() if torch.is_tensor(v) else v) for k_, v in t.items()} for t in targets]
             pm = batch["positive_map"][i]
             masks = self.criterion.token_masks_host(host_t, tok) if self.contrastive else None
-            out.append({"samples": samples, "tok": tok, "targets": side["targets"].pack(host_t, pm.cpu() if torch.is_tensor(pm) else pm, masks),
-                        "tables": side["targets"].distill.pack(tok, host_t, batch["captions"][i])})
+            live = {"live_tokens": int(tok["input_ids"].shape[1])} if self.bucketed else {}       # each side's OWN caption length
+            out.append({"samples": samples, "tok": tok, "key": key,
+                        "targets": self._pack_st[i].pack(host_t, pm.cpu() if torch.is_tensor(pm) else pm, masks, **live),
+                        "tables": tables[i].pack(tok, host_t, batch["captions"][i])})
         return out
 
     def _plan(self, packed):
-        """The stateful host half of a step, once per step and in step order: the k-means starts of the samples whose bank is filling
-        (ClusterCriterion.plan_fill on the task columns of the packed tables)."""
+        """The stateful host half of a step, once per step and in step order, whichever bucket serves the step: the k-means starts of the samples whose
+        bank is filling (ClusterCriterion.plan_fill on the task columns of the packed tables)."""
         if self.fill is None:
             return None
-        tasks = [side["targets"].distill._views(pk["tables"])[4].tolist() for side, pk in zip(self.sides, packed)]
+        tasks = [tb._views(pk["tables"])[4].tolist() for tb, pk in zip(self._table_packers(packed[0]["key"][2]), packed)]
         return self.cluster_criterion.plan_fill(*tasks)
 
-    def _fill(self, packed, starts):
-        for side, pk in zip(self.sides, packed):
+    def _fill(self, ent, packed, starts):
+        for side, pk in zip(ent["sides"], packed):
             upload(side, pk["samples"], pk["tok"])
             side["targets"].load_packed(pk["targets"])
             side["targets"].distill.load_packed(pk["tables"])
         if starts is not None:
             self.fill.load(*starts)
 
-    def _fwd_bwd_opt(self):
-        """One step.  The backward pass is issued in TWO calls -- the teacher's total (the noun_ keys) first, then everything else (sth_, softkd, nsthl2, cluster:
+    def _fwd_bwd_opt(self, ent):
+        """One step on the static inputs of `ent`.  The backward pass is issued in TWO calls -- the teacher's total (the noun_ keys) first, then everything else (sth_, softkd, nsthl2, cluster:
         the student's) -- which changes no gradient (the two models' graphs are disjoint: the teacher enters the cross losses detached, mdetr.py:520-599, 668-781)
         but lets a captured step run the teacher's backward beside the softkd assignment problems, which occupy 24 CUs for ~3.6 ms on a side stream
         (SetCriterion._forward_pair_static)."""
         from .harness import distillation_losses
         from .mdetr import weighted_total
         kernels.SEED_DEV.add_(1000003)
-        noun, sth = self.sides
+        noun, sth = ent["sides"]
         static = {"samples": [noun["samples"], sth["samples"]], "targets": [noun["targets"], sth["targets"]], "captions": [None, None],
                   "tokenized": [noun["tok"], sth["tok"]], "positive_map": [None, None]}
         self.criterion.defer_pair_join = True          # the softkd block may go to a side stream: this method joins it (below) before the student's total
@@ -567,18 +629,17 @@ class CapturedDistillStep(_CapturedStep):
         batch = packed if packed is not None else self.pack(batch)
         if _is_distributed():
             raise RuntimeError("CapturedDistillStep is single-process (the memory-bank queue all_gathers rows across ranks: collectives are not captured)")
-        self._void_graphs()
-        ent = self._ent
+        ent = self._entry(batch[0]["key"])
         starts = self._plan(batch)
         if ent["graph"] is None:
-            out = self._eager_then_capture(ent, self._fwd_bwd_opt, reset=self._zero_grad, upload=lambda: self._fill(batch, starts))
+            out = self._eager_then_capture(ent, lambda: self._fwd_bwd_opt(ent), reset=self._zero_grad, upload=lambda: self._fill(ent, batch, starts))
             if self.fill is not None:
                 self.cluster_criterion.check_start_status(defer=True)
             return out
-        side = self._side                                  # (unlike the bucketed steps, upload and replay stay on the stream of the capture)
+        side = self._side                                  # (unlike CapturedTrainStep / CapturedEvalStep, upload and replay stay on the stream of the capture)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            self._fill(batch, starts)
+            self._fill(ent, batch, starts)
             ent["graph"].replay()
             if self.fill is not None:
                 self.cluster_criterion.check_start_status(defer=True)

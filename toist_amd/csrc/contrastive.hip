@@ -35,37 +35,43 @@ __device__ __forceinline__ float ca_block_sum(float v, float* red) {
     return t;
 }
 
-template <int MODE>
+// LIVE: the launch sits in a replayed graph whose captions are padded to Tpad tokens; *live_tokens (a device word refilled between replays) says how many
+// of them the batch really has.  T = clamp(*live_tokens, 0, Tpad) then takes the place of the token count in every loop below -- the launch computes
+// what the launch on proj_tokens[:, :T] computes, in the same order -- and the dead rows of the token gradient are written as zeros.  The LDS layout
+// stays a function of Tpad (the host sizes it at capture time).  LIVE = false is the kernel as it was: T = Tpad at compile time.
+template <int MODE, bool LIVE>
 __global__ __launch_bounds__(CA_THREADS) void contrastive_kernel(
     const float* __restrict__ pq,            // [L,B,Q,D] normalised query projections
     const float* __restrict__ pt,            // [B,T,D]   normalised token projections
     const unsigned long long* __restrict__ tok_mask,   // [sum targets, CA_MW] token bits of every target row
     const int* __restrict__ tgt_off, const int* __restrict__ match_off, const long long* __restrict__ src_idx,
-    const long long* __restrict__ tgt_idx, const float* __restrict__ num_boxes, int L, int B, int Q, int T, int D,
+    const long long* __restrict__ tgt_idx, const float* __restrict__ num_boxes, int L, int B, int Q, int Tpad, int D,
     float inv_temp,
     float* __restrict__ losses,              // MODE 0: [L] (+=)
     const float* __restrict__ upstream,      // MODE 1: [L]
     float* __restrict__ dpq,                 // MODE 1: [L,B,Q,D] fully written
     float* __restrict__ dpt,                 // MODE 1: [B,T,D] (+=, caller zeroes)
-    float* __restrict__ dpt_layers) {        // MODE 1, optional: [L,B,T,D] each layer's share, fully written (folded in layer order later)
+    float* __restrict__ dpt_layers,          // MODE 1, optional: [L,B,T,D] each layer's share, fully written (folded in layer order later)
+    const int* __restrict__ live_tokens) {   // LIVE: one device word, the live token columns of the Tpad
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int DP = D + 1;
-    const bool staged = T <= CA_STAGE_TOK;
+    const bool staged = Tpad <= CA_STAGE_TOK;
+    const int T = LIVE ? min(max(live_tokens[0], 0), Tpad) : Tpad;
     const int TP = staged ? DP : D;          // row pitch of the token projections as read below
     unsigned long long* qm = reinterpret_cast<unsigned long long*>(sm);   // [Q][CA_MW] token bits of the target matched to query q (0 = unmatched)
     float* sq = sm + 2 * CA_MW * Q;          // [Q][DP]
     float* st_lds = sq + Q * DP;             // [T][DP] when staged
-    float* lg = st_lds + (staged ? T * DP : 0);   // [Q][T]  logits, then d(logits)
-    float* row_lse = lg + Q * T;             // [Q]
+    float* lg = st_lds + (staged ? Tpad * DP : 0);   // [Q][T]  logits, then d(logits)
+    float* row_lse = lg + Q * Tpad;          // [Q]
     float* col_lse = row_lse + Q;            // [T]
-    float* col_np = col_lse + T;             // [T] positives per token
+    float* col_np = col_lse + Tpad;          // [T] positives per token
     __shared__ float red[CA_THREADS / 64];
     const int lb = blockIdx.x, l = lb / B, b = lb - l * B, tid = threadIdx.x;
     const int Mtot = match_off[B];
 
     for (int i = tid; i < CA_MW * Q; i += CA_THREADS) qm[i] = 0ull;
     const float* gq = pq + (size_t)(l * B + b) * Q * D;
-    const float* gt = pt + (size_t)b * T * D;
+    const float* gt = pt + (size_t)b * Tpad * D;
     for (int i = tid; i < Q * D; i += CA_THREADS) sq[(i / D) * DP + (i % D)] = gq[i];
     if (staged)
         for (int i = tid; i < T * D; i += CA_THREADS) st_lds[(i / D) * DP + (i % D)] = gt[i];
@@ -75,7 +81,11 @@ __global__ __launch_bounds__(CA_THREADS) void contrastive_kernel(
         const int q = (int)src_idx[(size_t)l * Mtot + m];
         const size_t t = (size_t)tgt_off[b] + (size_t)tgt_idx[(size_t)l * Mtot + m];
 #pragma unroll
-        for (int w = 0; w < CA_MW; ++w) qm[CA_MW * q + w] = tok_mask[CA_MW * t + w];          // a query is matched to at most one target
+        for (int w = 0; w < CA_MW; ++w) {                                                     // a query is matched to at most one target
+            unsigned long long bits = tok_mask[CA_MW * t + w];
+            if (LIVE) bits &= T >= 64 * (w + 1) ? ~0ull : T <= 64 * w ? 0ull : (1ull << (T - 64 * w)) - 1ull;       // a dead column is no positive
+            qm[CA_MW * q + w] = bits;
+        }
     }
     for (int i = tid; i < Q * T; i += CA_THREADS) {
         const int q = i / T, t = i - q * T;
@@ -149,14 +159,16 @@ __global__ __launch_bounds__(CA_THREADS) void contrastive_kernel(
         for (int t = 0; t < T; ++t) acc += lg[q * T + t] * st[t * TP + d];
         oq[i] = acc;
     }
-    float* ot = dpt + (size_t)b * T * D;
+    float* ot = dpt + (size_t)b * Tpad * D;
     for (int i = tid; i < T * D; i += CA_THREADS) {
         const int t = i / D, d = i - t * D;
         float acc = 0.f;
         for (int q = 0; q < Q; ++q) acc += lg[q * T + t] * sq[q * DP + d];
-        if (dpt_layers) dpt_layers[(size_t)(l * B + b) * T * D + i] = acc;
+        if (dpt_layers) dpt_layers[(size_t)(l * B + b) * Tpad * D + i] = acc;
         else atomicAdd(ot + i, acc);
     }
+    if (LIVE && dpt_layers)                  // the dead rows of this layer's share: written, the fold does not read them but nothing is left as found
+        for (int i = T * D + tid; i < Tpad * D; i += CA_THREADS) dpt_layers[(size_t)(l * B + b) * Tpad * D + i] = 0.f;
 }
 
 static size_t contrastive_lds(int Q, int T, int D) {
@@ -199,8 +211,10 @@ static int contrastive_launch_ok(int L, int B, int Q, int T, int D, size_t* lds)
     if (*lds > 64 * 1024) {
         static std::atomic<unsigned long long> done{0};     // one bit per device
         if (!lds_attr_once_flag(done, [] {
-                return hipFuncSetAttribute((const void*)contrastive_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, CA_LDS_MAX) == hipSuccess &&
-                       hipFuncSetAttribute((const void*)contrastive_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CA_LDS_MAX) == hipSuccess;
+                for (const void* fn : {(const void*)contrastive_kernel<0, false>, (const void*)contrastive_kernel<1, false>,
+                                       (const void*)contrastive_kernel<0, true>, (const void*)contrastive_kernel<1, true>})
+                    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, CA_LDS_MAX) != hipSuccess) return false;
+                return true;
             })) {
             set_last_error("toist_contrastive: cannot enable %d bytes of LDS", CA_LDS_MAX);
             return TOIST_EHIP;
@@ -215,9 +229,9 @@ extern "C" int toist_contrastive_fwd(const float* proj_queries, const float* pro
     size_t lds;
     if (int rc = contrastive_launch_ok(L, B, Q, T, D, &lds)) return rc;
     TOIST_REQUIRE(temperature > 0.f, "toist_contrastive_fwd: temperature must be positive");
-    hipLaunchKernelGGL(contrastive_kernel<0>, dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
+    hipLaunchKernelGGL((contrastive_kernel<0, false>), dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
                        (const unsigned long long*)tok_mask, tgt_off, match_off, (const long long*)src_idx, (const long long*)tgt_idx, num_boxes, L, B,
-                       Q, T, D, 1.f / temperature, losses, (const float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+                       Q, T, D, 1.f / temperature, losses, (const float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (const int*)nullptr);
     return check_launch("toist_contrastive_fwd");
 }
 
@@ -228,9 +242,9 @@ extern "C" int toist_contrastive_bwd(const float* proj_queries, const float* pro
     size_t lds;
     if (int rc = contrastive_launch_ok(L, B, Q, T, D, &lds)) return rc;
     TOIST_REQUIRE(temperature > 0.f, "toist_contrastive_bwd: temperature must be positive");
-    hipLaunchKernelGGL(contrastive_kernel<1>, dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
+    hipLaunchKernelGGL((contrastive_kernel<1, false>), dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
                        (const unsigned long long*)tok_mask, tgt_off, match_off, (const long long*)src_idx, (const long long*)tgt_idx, num_boxes, L, B,
-                       Q, T, D, 1.f / temperature, (float*)nullptr, upstream, dproj_queries, dproj_tokens, (float*)nullptr);
+                       Q, T, D, 1.f / temperature, (float*)nullptr, upstream, dproj_queries, dproj_tokens, (float*)nullptr, (const int*)nullptr);
     return check_launch("toist_contrastive_bwd");
 }
 
@@ -250,15 +264,63 @@ extern "C" int toist_contrastive_bwd_ws(const float* proj_queries, const float* 
     size_t lds;
     if (int rc = contrastive_launch_ok(L, B, Q, T, D, &lds)) return rc;
     TOIST_REQUIRE(temperature > 0.f && workspace != nullptr, "toist_contrastive_bwd_ws: temperature must be positive, workspace given");
-    hipLaunchKernelGGL(contrastive_kernel<1>, dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
+    hipLaunchKernelGGL((contrastive_kernel<1, false>), dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
                        (const unsigned long long*)tok_mask, tgt_off, match_off, (const long long*)src_idx, (const long long*)tgt_idx, num_boxes, L, B,
-                       Q, T, D, 1.f / temperature, (float*)nullptr, upstream, dproj_queries, dproj_tokens, workspace);
+                       Q, T, D, 1.f / temperature, (float*)nullptr, upstream, dproj_queries, dproj_tokens, workspace, (const int*)nullptr);
     if (int rc = check_launch("toist_contrastive_bwd_ws")) return rc;
     const long long n = (long long)B * T * D;
     const long long blocks = (n + 255) / 256;
     hipLaunchKernelGGL(fold_layers_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, L, n,
                        dproj_tokens);
     return check_launch("toist_contrastive_bwd_ws(fold)");
+}
+
+// The two entry points of a replayed graph whose captions are padded (contrastive_kernel<., true>): T is the padded token count, *live_tokens the batch's own.
+extern "C" int toist_contrastive_fwd_live(const float* proj_queries, const float* proj_tokens, const uint64_t* tok_mask, const int32_t* tgt_off,
+                                          const int32_t* match_off, const int64_t* src_idx, const int64_t* tgt_idx, const float* num_boxes, int L,
+                                          int B, int Q, int T, int D, float temperature, const int32_t* live_tokens, float* losses, void* stream) {
+    size_t lds;
+    if (int rc = contrastive_launch_ok(L, B, Q, T, D, &lds)) return rc;
+    TOIST_REQUIRE(temperature > 0.f && live_tokens != nullptr, "toist_contrastive_fwd_live: temperature must be positive, live_tokens given");
+    hipLaunchKernelGGL((contrastive_kernel<0, true>), dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
+                       (const unsigned long long*)tok_mask, tgt_off, match_off, (const long long*)src_idx, (const long long*)tgt_idx, num_boxes, L, B,
+                       Q, T, D, 1.f / temperature, losses, (const float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       (const int*)live_tokens);
+    return check_launch("toist_contrastive_fwd_live");
+}
+
+// dpt[i] += sum_l part[l][i] on the live token rows, the layers in order; the dead rows of dpt are set to zero
+__global__ __launch_bounds__(256) void fold_layers_live_kernel(const float* __restrict__ part, int L, long long n, int Tpad, int D,
+                                                               const int* __restrict__ live_tokens, float* __restrict__ out) {
+    const int T = min(max(live_tokens[0], 0), Tpad);
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        if ((int)((i / D) % Tpad) >= T) {
+            out[i] = 0.f;
+            continue;
+        }
+        float s = 0.f;
+        for (int l = 0; l < L; ++l) s += part[(size_t)l * n + i];
+        out[i] += s;
+    }
+}
+
+extern "C" int toist_contrastive_bwd_ws_live(const float* proj_queries, const float* proj_tokens, const uint64_t* tok_mask, const int32_t* tgt_off,
+                                             const int32_t* match_off, const int64_t* src_idx, const int64_t* tgt_idx, const float* num_boxes,
+                                             int L, int B, int Q, int T, int D, float temperature, const int32_t* live_tokens,
+                                             const float* upstream, float* dproj_queries, float* dproj_tokens, float* workspace, void* stream) {
+    size_t lds;
+    if (int rc = contrastive_launch_ok(L, B, Q, T, D, &lds)) return rc;
+    TOIST_REQUIRE(temperature > 0.f && workspace != nullptr && live_tokens != nullptr,
+                  "toist_contrastive_bwd_ws_live: temperature must be positive, workspace and live_tokens given");
+    hipLaunchKernelGGL((contrastive_kernel<1, true>), dim3(L * B), dim3(CA_THREADS), lds, (hipStream_t)stream, proj_queries, proj_tokens,
+                       (const unsigned long long*)tok_mask, tgt_off, match_off, (const long long*)src_idx, (const long long*)tgt_idx, num_boxes, L, B,
+                       Q, T, D, 1.f / temperature, (float*)nullptr, upstream, dproj_queries, dproj_tokens, workspace, (const int*)live_tokens);
+    if (int rc = check_launch("toist_contrastive_bwd_ws_live")) return rc;
+    const long long n = (long long)B * T * D;
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(fold_layers_live_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)workspace, L, n, T, D, (const int*)live_tokens, dproj_tokens);
+    return check_launch("toist_contrastive_bwd_ws_live(fold)");
 }
 
 extern "C" int toist_l2norm_fwd(const float* x, int rows, int D, float* y, void* stream) {

@@ -95,18 +95,31 @@ class SyntheticCaptions(TokenizedText):
         return t if 0 <= c and t < self["input_ids"].shape[1] - 1 else None
 
 
-def synthetic_distill_batch(batch, height=640, width=640, tokens=16, seed=1000, device="cpu", max_targets=10):
+def synthetic_distill_batch(batch, height=640, width=640, tokens=16, seed=1000, device="cpu", max_targets=10, tokens_pronoun=None):
     """What collate_fn (util/misc.py:40-91) delivers for `batch` (noun, pronoun) pairs: the two sides share image and
     boxes; the noun caption names the object (characters 8..15 -> tokens 3..4), the pronoun caption says 'something'
-    at the same place.  Returns dict(samples, targets, positive_map, captions, tokenized) with two-element lists."""
+    at the same place.  Returns dict(samples, targets, positive_map, captions, tokenized) with two-element lists.
+    tokens_pronoun: the pronoun caption's own token count (the reference tokenises the two captions separately, so they differ): that side
+    then has its own ids, positive map and token spans, of the same form as the noun side's."""
     samples, tok, targets, pmap = synthetic_batch(batch, height, width, tokens=tokens, seed=seed, device=device, max_targets=max_targets)
     out = {"samples": [samples, samples], "positive_map": [pmap, pmap], "example_rel": list(range(batch)), "targets": [], "captions": [], "tokenized": []}
     for side, word in enumerate(("scissors", "something")):
-        caption = ("use the " + word + " to cut the paper up")[:4 * (tokens - 2)]
+        n_tok = tokens if side == 0 or tokens_pronoun is None else int(tokens_pronoun)
+        caption = ("use the " + word + " to cut the paper up")[:4 * (n_tok - 2)]
         out["captions"].append([caption] * batch)
+        if n_tok != tokens:
+            ids = torch.randint(3, 50265, (batch, n_tok), generator=torch.Generator().manual_seed(seed + 7919))
+            ids[:, 0], ids[:, -1] = 0, 2
+            tok = TokenizedText({"input_ids": ids, "attention_mask": torch.ones(batch, n_tok, dtype=torch.int64)}).to(device)
+            pmap = torch.zeros_like(pmap)
+            pmap[:, 1:n_tok - 1] = 1.0 / (n_tok - 2)
+            out["positive_map"][side] = pmap
         tg = []
         for i, t in enumerate(targets):
             t = dict(t)
+            if n_tok != tokens:
+                n = len(t["boxes"])
+                t["positive_map"], t["token_spans"] = pmap[:n].clone(), [[(1, n_tok - 2)] for _ in range(n)]
             t["noun_tokens_positive"] = [[(8, 8 + len(word))] for _ in range(len(t["boxes"]))]
             t["dataset_name"] = f"task_{1 + (i + side * 0) % 14}_train.json"
             tg.append(t)

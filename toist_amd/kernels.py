@@ -505,21 +505,40 @@ def criterion_bwd(logits, boxes, tgt_boxes, pos_map, tgt_off, match_off, src_idx
                                               _stream()), "toist_criterion_bwd")
 
 
-def contrastive_fwd(pq, pt, tok_mask, tgt_off, match_off, src_idx, tgt_idx, num_boxes, temperature, losses):
+def contrastive_fwd(pq, pt, tok_mask, tgt_off, match_off, src_idx, tgt_idx, num_boxes, temperature, losses, live_tokens=None):
+    """live_tokens: device int32 [1] = how many of pt's T token columns are live (the rest is caption padding of a bucket); None = all of them."""
     L, B, Q, D = pq.shape
-    _lib.check(_lib.lib().toist_contrastive_fwd(_p(pq, torch.float32), _p(pt, torch.float32), _p(tok_mask, torch.int64), _p(tgt_off, torch.int32),
-                                                _p(match_off, torch.int32), _p(src_idx, torch.int64), _p(tgt_idx, torch.int64),
-                                                _p(num_boxes, torch.float32), L, B, Q, pt.shape[1], D, temperature, _p(losses, torch.float32),
-                                                _stream()), "toist_contrastive_fwd")
+    if live_tokens is None:
+        _lib.check(_lib.lib().toist_contrastive_fwd(_p(pq, torch.float32), _p(pt, torch.float32), _p(tok_mask, torch.int64), _p(tgt_off, torch.int32),
+                                                    _p(match_off, torch.int32), _p(src_idx, torch.int64), _p(tgt_idx, torch.int64),
+                                                    _p(num_boxes, torch.float32), L, B, Q, pt.shape[1], D, temperature, _p(losses, torch.float32),
+                                                    _stream()), "toist_contrastive_fwd")
+        return
+    _lib.check(_lib.lib().toist_contrastive_fwd_live(_p(pq, torch.float32), _p(pt, torch.float32), _p(tok_mask, torch.int64), _p(tgt_off, torch.int32),
+                                                     _p(match_off, torch.int32), _p(src_idx, torch.int64), _p(tgt_idx, torch.int64),
+                                                     _p(num_boxes, torch.float32), L, B, Q, pt.shape[1], D, temperature, _p(live_tokens, torch.int32),
+                                                     _p(losses, torch.float32), _stream()), "toist_contrastive_fwd_live")
 
 
-def contrastive_bwd(pq, pt, tok_mask, tgt_off, match_off, src_idx, tgt_idx, num_boxes, temperature, upstream, dpq, dpt):
+def contrastive_bwd(pq, pt, tok_mask, tgt_off, match_off, src_idx, tgt_idx, num_boxes, temperature, upstream, dpq, dpt, live_tokens=None, workspace=None):
+    """dpt +=: the caller zeroes it; with live_tokens (see contrastive_fwd) its dead rows are set to zero whatever they held.  workspace: fp32
+    [L * B * T * D] scratch of the caller's, allocated here when None."""
     L, B, Q, D = pq.shape
-    ws = torch.empty(L * B * pt.shape[1] * D, dtype=torch.float32, device=pq.device)     # each layer's token gradient, folded in layer order
-    _lib.check(_lib.lib().toist_contrastive_bwd_ws(_p(pq, torch.float32), _p(pt, torch.float32), _p(tok_mask, torch.int64), _p(tgt_off, torch.int32),
-                                                   _p(match_off, torch.int32), _p(src_idx, torch.int64), _p(tgt_idx, torch.int64),
-                                                   _p(num_boxes, torch.float32), L, B, Q, pt.shape[1], D, temperature, _p(upstream, torch.float32),
-                                                   _p(dpq, torch.float32), _p(dpt, torch.float32), _p(ws, torch.float32), _stream()), "toist_contrastive_bwd_ws")
+    ws = workspace if workspace is not None else \
+        torch.empty(L * B * pt.shape[1] * D, dtype=torch.float32, device=pq.device)     # each layer's token gradient, folded in layer order
+    if ws.numel() < L * B * pt.shape[1] * D:
+        raise ValueError(f"contrastive_bwd: the workspace holds {ws.numel()} floats, L * B * T * D = {L * B * pt.shape[1] * D}")
+    if live_tokens is None:
+        _lib.check(_lib.lib().toist_contrastive_bwd_ws(_p(pq, torch.float32), _p(pt, torch.float32), _p(tok_mask, torch.int64), _p(tgt_off, torch.int32),
+                                                       _p(match_off, torch.int32), _p(src_idx, torch.int64), _p(tgt_idx, torch.int64),
+                                                       _p(num_boxes, torch.float32), L, B, Q, pt.shape[1], D, temperature, _p(upstream, torch.float32),
+                                                       _p(dpq, torch.float32), _p(dpt, torch.float32), _p(ws, torch.float32), _stream()), "toist_contrastive_bwd_ws")
+        return
+    _lib.check(_lib.lib().toist_contrastive_bwd_ws_live(_p(pq, torch.float32), _p(pt, torch.float32), _p(tok_mask, torch.int64), _p(tgt_off, torch.int32),
+                                                        _p(match_off, torch.int32), _p(src_idx, torch.int64), _p(tgt_idx, torch.int64),
+                                                        _p(num_boxes, torch.float32), L, B, Q, pt.shape[1], D, temperature,
+                                                        _p(live_tokens, torch.int32), _p(upstream, torch.float32), _p(dpq, torch.float32),
+                                                        _p(dpt, torch.float32), _p(ws, torch.float32), _stream()), "toist_contrastive_bwd_ws_live")
 
 
 def l2norm_fwd(x, y):

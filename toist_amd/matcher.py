@@ -220,6 +220,45 @@ class StaticTargets:
         return MatchResult(flat(src), flat(tgt), status, self.sizes, self.Q, self.tgt_off, self.match_off, self.boxes)
 
 
+class LiveStaticTargets(StaticTargets):
+    """StaticTargets with one more device word, `live_tokens` (int32 [1], fixed address): the batch's own caption length in a bucket whose captions
+    are padded further.  The contrastive-alignment kernels read it (toist_contrastive_fwd_live, include/toist_hip.h) and leave the padded token
+    columns out, so the bucket gives the loss of the unpadded batch -- loss_contrastive_align has no attention mask (mdetr.py:646-663).  The word is
+    one more 16-byte segment BEHIND the arena of StaticTargets, whose seven views keep their offsets; pack(..., live_tokens=L) writes it and
+    load_packed() carries it in the same single copy.  SetCriterion finds it as `tok_mask.live_tokens`."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._live_off = self._host.numel()
+        self._host = torch.zeros(self._live_off + 16, dtype=torch.uint8).pin_memory()
+        self._dev = torch.zeros(self._live_off + 16, dtype=torch.uint8, device=self.device)
+        self.boxes, self.positive_map, self.tok_mask, self.tgt_off, self.match_off, self._nb_local, valid_hw = self._views(self._dev)
+        if self.mask_hw is not None:
+            self.valid_hw = valid_hw
+        self.live_tokens = self._live_word(self._dev)
+        self.tok_mask.live_tokens = self.live_tokens
+
+    def _live_word(self, buf):
+        return buf[self._live_off:self._live_off + 4].view(torch.int32)
+
+    def pack(self, targets, positive_map, token_masks=None, out=None, live_tokens=None):
+        """StaticTargets.pack + the word.  live_tokens: the batch's caption length (required)."""
+        if live_tokens is None:
+            raise ValueError("LiveStaticTargets: pack(live_tokens=the batch's caption length)")
+        packed = super().pack(targets, positive_map, token_masks, out=out)
+        self._live_word(packed[0])[0] = int(live_tokens)
+        return packed
+
+    def load(self, targets, positive_map, token_masks=None, live_tokens=None):
+        """pack() into the internal staging buffer + load_packed()."""
+        if self._event is not None:
+            self._event.synchronize()          # the previous upload has left the staging buffer
+        self.load_packed(self.pack(targets, positive_map, token_masks, out=self._host, live_tokens=live_tokens))
+        self._event = torch.cuda.Event()
+        self._event.record()
+        return self
+
+
 class HungarianMatcher(nn.Module):
     def __init__(self, cost_class: float = 1, cost_bbox: float = 1, cost_giou: float = 1):
         super().__init__()

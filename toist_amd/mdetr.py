@@ -468,8 +468,11 @@ class SetCriterion(nn.Module):
         pt = outputs["proj_tokens"]
         if tok_mask is None:
             return _per_layer("loss_contrastive_align", (pq.sum() * 0 + pt.sum() * 0).expand(L), group=False)
+        # (the token masks of a matcher.LiveStaticTargets carry the device word with the batch's own caption length: the bucket's padded token columns
+        # then stay out of the loss, which has no attention mask)
         return _per_layer("loss_contrastive_align", _ContrastiveFn.apply(pq.float().contiguous(), pt.float().contiguous(), match, tok_mask,
-                                                                         num_boxes.reshape(1).float().contiguous(), float(self.temperature)))
+                                                                         num_boxes.reshape(1).float().contiguous(), float(self.temperature),
+                                                                         getattr(tok_mask, "live_tokens", None)))
 
     def _side_losses(self, outputs, logits, boxes, match, positive_map, num_boxes, tok_mask, mask_losses):
         """Every loss of ONE model on a device-resident assignment: labels / boxes / cardinality / contrastive_align / masks.  tok_mask() and
@@ -793,12 +796,14 @@ class _ContrastiveFn(torch.autograd.Function):
     """losses [L] = loss_contrastive_align per visited decoder layer (csrc/contrastive.hip)."""
 
     @staticmethod
-    def forward(ctx, pq, pt, match, tok_mask, num_boxes, temperature):
+    def forward(ctx, pq, pt, match, tok_mask, num_boxes, temperature, live_tokens=None):
+        """live_tokens: device int32 [1], how many of pt's token columns are live (None: all of them)."""
         L = pq.shape[0]
         losses = torch.zeros(L, dtype=torch.float32, device=pq.device)
-        k.contrastive_fwd(pq, pt, tok_mask, match.tgt_off_dev, match.match_off_dev, match.src[-L:], match.tgt[-L:], num_boxes, temperature, losses)
+        k.contrastive_fwd(pq, pt, tok_mask, match.tgt_off_dev, match.match_off_dev, match.src[-L:], match.tgt[-L:], num_boxes, temperature, losses,
+                          live_tokens=live_tokens)
         ctx.save_for_backward(pq, pt, tok_mask, num_boxes)
-        ctx.match, ctx.temperature = match, temperature
+        ctx.match, ctx.temperature, ctx.live_tokens = match, temperature, live_tokens
         return losses
 
     @staticmethod
@@ -807,8 +812,8 @@ class _ContrastiveFn(torch.autograd.Function):
         m, L = ctx.match, pq.shape[0]
         dpq, dpt = torch.empty_like(pq), torch.zeros_like(pt)
         k.contrastive_bwd(pq, pt, tok_mask, m.tgt_off_dev, m.match_off_dev, m.src[-L:], m.tgt[-L:], num_boxes, ctx.temperature,
-                          g.float().contiguous(), dpq, dpt)
-        return dpq, dpt, None, None, None, None
+                          g.float().contiguous(), dpq, dpt, live_tokens=ctx.live_tokens)
+        return dpq, dpt, None, None, None, None, None
 
 
 class _L2NormFn(torch.autograd.Function):

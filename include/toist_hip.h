@@ -849,6 +849,31 @@ TOIST_API int toist_image_prep(const uint8_t* src, long long src_bytes, const in
 TOIST_API int toist_target_masks(const uint8_t* src, long long src_bytes, const int32_t* desc, const int32_t* arena, long long arena_words, int slots,
                      int cap_h, int cap_w, uint8_t* dst, void* stream);
 
+/* ---- polygon annotations on the device (replaces the host's rasteriser of an object's polygons: datasets/tdod.py:133-147 convert_coco_poly_to_mask =
+ * pycocotools frPyObjects + decode + any(dim=2), i.e. maskApi.c rleFrPoly per polygon and the union per object).  The masks EQUAL the host's
+ * (toist_amd/coco_eval.py: polygon_to_mask) bit for bit: the same fp64 operations in the same order, no fused multiply-add.  One launch per batch;
+ * every size comes from the device, so the launch can sit in a captured hipGraph.  Three tables of int32 words:
+ *   desc  [slots, TOIST_POLY_DESC_WORDS], one row per object slot:
+ *      0 dst_off (bytes from `dst`, a multiple of 4; packed mode)   1 h   2 w   3 stride_words (32-bit words per packed row, >= ceil(w / 32))
+ *      4 poly_first   5 poly_count   (records of `polys`)      6, 7 reserved
+ *   polys [poly_cap, TOIST_POLY_REC_WORDS]: first vertex, vertex count of one polygon
+ *   verts [vert_cap, 2]: x, y on rleFrPoly's 5x grid, int(5.0 * c + .5) computed by the host in float64 (the device never sees the coordinates)
+ * The grid covers [slots, ceil(cap_w / TOIST_POLY_STRIP)]: a workgroup owns TOIST_POLY_STRIP columns of one object and holds them for up to
+ * TOIST_POLY_MAX_ROWS rows in LDS; cap_h <= TOIST_POLY_MAX_ROWS.  A row with h = 0 is a DEAD slot: nothing of it is written.  A row that does not fit
+ * the capacities (cap_h, cap_w, poly_cap, vert_cap, dst_bytes, the stride the grid covers) writes nothing either: the caller checks its sizes -- and
+ * the trace steps of the batch, sum over the edges of max(|dx|, |dy|) on the grid, which is the launch's work -- on the host before the launch.
+ *   TOIST_POLY_PACKED: the object's h rows of stride_words words at dst + dst_off, pixel x of a row = bit (x & 31) of little-endian word (x >> 5)
+ *                      (the source format of toist_target_masks).  EVERY word of every row is written, pad bits as zeros; nothing else is.
+ *   TOIST_POLY_DENSE : dst = uint8 [slots, cap_h, cap_w], values 0 / 1; the live h x w region of a slot is written completely, the rest is left alone. */
+#define TOIST_POLY_DESC_WORDS 8
+#define TOIST_POLY_REC_WORDS 2
+#define TOIST_POLY_STRIP 64
+#define TOIST_POLY_MAX_ROWS 2048
+#define TOIST_POLY_PACKED 0
+#define TOIST_POLY_DENSE 1
+TOIST_API int toist_polygon_masks(const int32_t* desc, int slots, const int32_t* polys, int poly_cap, const int32_t* verts, int vert_cap, int cap_h,
+                     int cap_w, uint8_t* dst, long long dst_bytes, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,8 @@ def __getattr__(name):
         "DeviceTargetMasks": ("preprocess", "DeviceTargetMasks"), "PackedTargetMasks": ("preprocess", "PackedTargetMasks"),
         "nearest_table": ("preprocess", "nearest_table"), "mask_index_tables": ("preprocess", "mask_index_tables"),
         "pack_mask_bits": ("preprocess", "pack_mask_bits"), "unpack_mask_bits": ("preprocess", "unpack_mask_bits"),
+        "DevicePolygonMasks": ("preprocess", "DevicePolygonMasks"), "polygon_tables": ("preprocess", "polygon_tables"),
+        "convert_coco_poly_to_mask": ("coco_eval", "convert_coco_poly_to_mask"),
     }
     if name in table:
         mod, attr = table[name]

@@ -97,6 +97,9 @@ ROW_PLAIN, ROW_LN_FWD, ROW_LN_BWD = _consts("ROW_PLAIN ROW_LN_FWD ROW_LN_BWD")
 XDEC_MAX_LAYERS, XDEC_CTL_WORDS = _consts("XDEC_MAX_LAYERS XDEC_CTL_WORDS")
 PREP_DESC_WORDS = CONSTANTS["TOIST_PREP_DESC_WORDS"]        # int32 words of one image's row in toist_image_prep's descriptor table
 TMASK_DESC_WORDS = CONSTANTS["TOIST_TMASK_DESC_WORDS"]      # int32 words of one slot's row in toist_target_masks' descriptor table
+# toist_polygon_masks: int32 words of an object's row and of a polygon's record, the columns of a workgroup's strip, the rows of its LDS plane, the modes
+POLY_DESC_WORDS, POLY_REC_WORDS, POLY_STRIP, POLY_MAX_ROWS, POLY_PACKED, POLY_DENSE = _consts(
+    "POLY_DESC_WORDS POLY_REC_WORDS POLY_STRIP POLY_MAX_ROWS POLY_PACKED POLY_DENSE")
 
 
 class Operand(Structure):

@@ -128,9 +128,37 @@ def polygon_to_mask(xy, h, w):
     return counts_to_mask(counts, h, w)
 
 
-def convert_coco_poly_to_mask(segmentations, height, width):
+DEVICE_TRACE_STEPS = 1 << 22       # trace steps one device call of convert_coco_poly_to_mask accepts: 5 per pixel of perimeter, i.e. 840 k pixels
+_RASTERISERS = {}                  # device -> DevicePolygonMasks, regrown when a call needs more
+
+
+def _device_poly_masks(segmentations, height, width, device):
+    """bool [n, height, width] on `device` from csrc/poly.hip: one launch for all objects."""
+    from .preprocess import DevicePolygonMasks, polygon_tables
+    device = torch.device(device)
+    segmentations = [list(polygons) for polygons in segmentations]
+    sizes = [(height, width)] * len(segmentations)
+    verts, polys, desc, steps = polygon_tables(segmentations, sizes)              # every check before a buffer is made
+    if steps > DEVICE_TRACE_STEPS:
+        raise ValueError(f"convert_coco_poly_to_mask: {steps} trace steps exceed coco_eval.DEVICE_TRACE_STEPS = {DEVICE_TRACE_STEPS}: rasterise these on the host")
+    need = (desc.shape[0], max(polys.shape[0], 1), max(verts.shape[0], 1), height, width)
+    r = _RASTERISERS.get(device)
+    have = (0,) * 5 if r is None else (r.max_objects, r.max_polygons, r.max_vertices, *r.max_hw)
+    if any(n > c for n, c in zip(need, have)):
+        cap = [max(n, c) for n, c in zip(need, have)]
+        r = _RASTERISERS[device] = DevicePolygonMasks(device, cap[0], cap[1], cap[2], (cap[3], cap[4]), DEVICE_TRACE_STEPS)
+    with torch.cuda.device(device):
+        return torch.stack(r.dense(r.pack(segmentations, sizes)), dim=0)
+
+
+def convert_coco_poly_to_mask(segmentations, height, width, device=None):
     """datasets/tdod.py:133-147 (and datasets/coco.py:66-80): one bool mask per object, the union of its polygons
-    (coco_mask.frPyObjects + decode + any(dim=2) in the reference)."""
+    (coco_mask.frPyObjects + decode + any(dim=2) in the reference).  device = a GPU: the same masks as a bool device tensor, rasterised there
+    (csrc/poly.hip through preprocess.DevicePolygonMasks; at most kernels.POLYGON_MAX_ROWS rows and DEVICE_TRACE_STEPS trace steps per call)."""
+    if device is not None:
+        if not segmentations:
+            return torch.zeros((0, height, width), dtype=torch.uint8, device=device)
+        return _device_poly_masks(segmentations, height, width, device)
     masks = []
     for polygons in segmentations:
         m = np.zeros((height, width), dtype=bool)
@@ -165,10 +193,13 @@ def polygon_vertices(poly):
 class CocoGroundTruth:
     """The slice of pycocotools.coco.COCO the evaluator reads: a COCO-format dict {"images": [{"id","height","width"}],
     "annotations": [{"id","image_id","category_id","bbox" [x,y,w,h],"area","iscrowd","segmentation"}]}.
-    A segmentation is a list of polygons, an RLE dict {"size": [h, w], "counts": list | str} or a dense [h, w] array."""
+    A segmentation is a list of polygons, an RLE dict {"size": [h, w], "counts": list | str} or a dense [h, w] array.
+    polygons_on_device: planes() rasterises an image's polygon annotations on the device (convert_coco_poly_to_mask(device=)), the same bits; RLE and
+    dense segmentations keep the host path."""
 
-    def __init__(self, dataset):
+    def __init__(self, dataset, polygons_on_device=False):
         self.dataset = dataset
+        self.polygons_on_device = bool(polygons_on_device)
         self.imgs = {im["id"]: im for im in dataset.get("images", [])}
         self.img_anns = {i: [] for i in self.imgs}
         for ann in dataset.get("annotations", []):
@@ -195,11 +226,26 @@ class CocoGroundTruth:
             return out
         return np.asarray(seg).astype(bool)
 
+    def _dense_on_device(self, anns, device):
+        """bool [n, h, w] on the device: the polygon annotations in one rasterise launch, every other kind through dense_mask."""
+        im = self.imgs[anns[0]["image_id"]]
+        poly = [i for i, a in enumerate(anns) if isinstance(a["segmentation"], (list, tuple))]
+        dense = torch.zeros((len(anns), im["height"], im["width"]), dtype=torch.bool, device=device)
+        if poly:
+            dense[poly] = convert_coco_poly_to_mask([anns[i]["segmentation"] for i in poly], im["height"], im["width"], device=device)
+        for i, a in enumerate(anns):
+            if i not in poly:
+                dense[i] = torch.from_numpy(np.ascontiguousarray(self.dense_mask(a))).to(device)
+        return dense
+
     def planes(self, img_id, cat_ids, device):
         """Bit planes of an image's ground-truth masks (packed once, kept on the device)."""
         key = (img_id, None if cat_ids is None else tuple(cat_ids))
         if key not in self._planes:
             anns = self.annotations(img_id, cat_ids)
+            if anns and self.polygons_on_device:
+                self._planes[key] = k.mask_pack(self._dense_on_device(anns, device))
+                return self._planes[key]
             dense = np.stack([self.dense_mask(a) for a in anns]) if anns else None
             self._planes[key] = None if dense is None else k.mask_pack(torch.from_numpy(dense).to(device))
         return self._planes[key]

@@ -1054,6 +1054,37 @@ def target_masks(src, desc, arena, out):
     return out
 
 
+POLYGON_STRIP, POLYGON_MAX_ROWS = _lib.POLY_STRIP, _lib.POLY_MAX_ROWS      # columns of a workgroup's strip, rows of its LDS plane (the tallest image)
+
+
+def polygon_masks(desc, polys, verts, dst, cap_hw=None):
+    """The masks of a batch's polygon annotations in one launch that reads every size from the device (include/toist_hip.h: toist_polygon_masks), bit
+    for bit what coco_eval.polygon_to_mask / convert_coco_poly_to_mask give on the host.  desc int32 [slots, POLY_DESC_WORDS], polys int32 [polygon
+    capacity, POLY_REC_WORDS], verts int32 [vertex capacity, 2]: fixed-address device buffers that toist_amd.preprocess.DevicePolygonMasks fills.
+    dst uint8 [bytes] + cap_hw = the largest (h, w) the grid has to cover: packed bits (pack_mask_bits' layout) at every row's dst_off; dst uint8 (or
+    bool) [slots, cap_h, cap_w]: dense bytes, the live h x w region of every slot.  A slot whose row has h = 0 is left as it is.  No host read, no
+    allocation: graph-capturable."""
+    if desc.dim() != 2 or desc.shape[1] != _lib.POLY_DESC_WORDS or polys.dim() != 2 or polys.shape[1] != _lib.POLY_REC_WORDS or verts.dim() != 2 or \
+            verts.shape[1] != 2 or not (desc.is_contiguous() and polys.is_contiguous() and verts.is_contiguous() and dst.is_contiguous()):
+        raise ValueError(f"polygon_masks: contiguous int32 tables [slots, {_lib.POLY_DESC_WORDS}], [polygons, {_lib.POLY_REC_WORDS}], [vertices, 2] and a contiguous output")
+    S = desc.shape[0]
+    if dst.dim() == 3:
+        if dst.shape[0] != S or cap_hw is not None and tuple(cap_hw) != tuple(dst.shape[1:]):
+            raise ValueError(f"polygon_masks: a dense output is [{S}, cap_h, cap_w] (got {tuple(dst.shape)}, cap_hw {cap_hw})")
+        if dst.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"polygon_masks: the output holds bytes (uint8 or bool), got {dst.dtype}")
+        mode, (cap_h, cap_w) = _lib.POLY_DENSE, (int(dst.shape[1]), int(dst.shape[2]))
+    elif dst.dim() == 1 and cap_hw is not None and dst.dtype == torch.uint8:
+        mode, (cap_h, cap_w) = _lib.POLY_PACKED, (int(cap_hw[0]), int(cap_hw[1]))
+    else:
+        raise ValueError("polygon_masks: the output is uint8 [bytes] with cap_hw (packed bits) or [slots, cap_h, cap_w] (dense bytes)")
+    if not 0 < cap_h <= POLYGON_MAX_ROWS or cap_w <= 0:
+        raise ValueError(f"polygon_masks: a capacity of {cap_h} x {cap_w}: at most {POLYGON_MAX_ROWS} rows fit the kernel's plane")
+    _lib.check(_lib.lib().toist_polygon_masks(_p(desc, torch.int32), S, _p(polys, torch.int32), polys.shape[0], _p(verts, torch.int32), verts.shape[0],
+                                              cap_h, cap_w, _p(dst), dst.numel(), mode, _stream()), "toist_polygon_masks")
+    return dst
+
+
 def postprocess(pred_logits, pred_boxes, sizes_dev, pred_isfinal=None, out=None):
     """PostProcess in one launch (include/toist_hip.h: toist_postprocess).  pred_logits [B, Q, C] and pred_boxes [B, Q, 4] in bf16 or f32, pred_isfinal
     [B, Q] (or [B, Q, 1]) optional, sizes_dev int64 [B, 2] = (h, w) ON THE DEVICE.  -> dict(scores f32 [B, Q], boxes f32 [B, Q, 4] (+ scores_refexp));

@@ -11,7 +11,11 @@ The masks of the targets (configs[2]) go the same way: flip, nearest resize and 
 table per image (mask_index_tables); DeviceTargetMasks sends the masks at their original size with one bit per pixel and ONE launch
 (csrc/tmask.hip: toist_target_masks) gathers them into the bytes the mask losses read -- the bytes transform_target's torch ops produce.
 
-There is no CPU path: DevicePreprocessor and DeviceTargetMasks on a CPU device raise, like misc.DeviceStager."""
+Those source masks are rasterised polygon annotations (datasets/tdod.py:133-147).  DevicePolygonMasks does that on the device as well: the host sends
+the vertices on rleFrPoly's 5x grid (polygon_tables) and ONE launch (csrc/poly.hip: toist_polygon_masks) writes the bits coco_eval.polygon_to_mask
+computes, an object's polygons merged by union -- DeviceTargetMasks.pack_polygons puts them where toist_target_masks reads its source.
+
+There is no CPU path: DevicePreprocessor, DeviceTargetMasks and DevicePolygonMasks on a CPU device raise, like misc.DeviceStager."""
 import functools
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -283,6 +287,9 @@ def _mask_array(masks):
     if a.dtype not in (np.bool_, np.uint8) or a.ndim != 3:
         raise ValueError(f"target masks are bool or uint8 [n, h, w] (got {a.dtype} {a.shape})")
     return a
+
+
+_NO_MASK = np.zeros((1, 1, 1), dtype=np.bool_)          # broadcast to [n, h, w]: a mask stack that has a shape and no pixels (pack_polygons)
 
 
 def _pack_bits(a):
@@ -695,6 +702,49 @@ class DeviceTargetMasks:
         self.last = packed
         return packed
 
+    def pack_polygons(self, segmentations_per_image, plans, rows_per_image=None, *, polygons):
+        """pack() for targets that still are polygon annotations: segmentations_per_image[i] = one list of flat polygons per target of image i, at the
+        size (plans[i].height, plans[i].width).  The descriptors and index tables are pack()'s; the source-bit area of the blob is filled by the
+        rasterise launch of `polygons` (a DevicePolygonMasks) on the current stream, behind the copies, instead of by host bits, so write_into() and
+        dense() work unchanged.  rows_per_image as in pack().  -> PackedTargetMasks whose link_bytes count the descriptors, the tables and the
+        polygons' tables.  Every capacity of both objects is checked before anything is copied or launched."""
+        if len(segmentations_per_image) != len(plans):
+            raise ValueError(f"DeviceTargetMasks: {len(segmentations_per_image)} segmentation lists for {len(plans)} plans (at least one)")
+        if rows_per_image is not None and len(rows_per_image) != len(plans):
+            raise ValueError(f"DeviceTargetMasks: {len(rows_per_image)} row lists for {len(plans)} plans")
+        objects, shapes = [], []
+        for i, (segs, p) in enumerate(zip(segmentations_per_image, plans)):
+            segs = list(segs)
+            if rows_per_image is not None:
+                rows = np.asarray(rows_per_image[i].cpu() if torch.is_tensor(rows_per_image[i]) else rows_per_image[i], dtype=np.int64).reshape(-1)
+                if rows.size and (rows.min() < 0 or rows.max() >= len(segs)):
+                    raise ValueError(f"DeviceTargetMasks: mask rows {rows.tolist()} of an image with {len(segs)} segmentations")
+                segs = [segs[r] for r in rows.tolist()]
+            objects.append(segs)
+            shapes.append(np.broadcast_to(_NO_MASK, (len(segs), int(p.height), int(p.width))))          # pack()'s placement reads the shapes only
+        packed, rows, tables, bits, used = self._layout(shapes, plans)
+        assert used <= self._blob_bytes and packed.slots <= self.max_slots
+        flat = [seg for segs in objects for seg in segs]
+        layout = polygons._layout(flat, [(r["src_h"], r["src_w"]) for r in rows], [r["src_off"] for r in rows])
+        if self._event is not None:
+            self._event.synchronize()
+        host = self._host_np
+        desc = host[:self._desc_bytes].view(np.int32).reshape(self.max_slots, _lib.TMASK_DESC_WORDS)
+        desc[:] = 0
+        for i, r in enumerate(rows):
+            desc[i] = [r[name] for name in TMASK_DESC_FIELDS]
+        words = host.view(np.int32)
+        for at, table in tables:
+            words[at:at + table.size] = table
+        head = min((at for at, _ in bits), default=used)       # the descriptors and the tables: the bits behind them are written on the device
+        self.blob[:head].copy_(self._host[:head], non_blocking=True)
+        self._event = torch.cuda.Event()
+        self._event.record()
+        placed = polygons.pack(flat, None, _layout=layout)
+        polygons.rasterise(self.blob)
+        self.last = PackedTargetMasks(packed.slots, packed.counts, packed.sizes, head + placed.link_bytes)
+        return self.last
+
     # -- device side --------------------------------------------------------------------------------------------------------------------
     def write_into(self, static_targets):
         """One launch of the batch that pack() placed into static_targets.masks (matcher.StaticTargets(mask_hw=...)): its first PackedTargetMasks.slots
@@ -728,3 +778,197 @@ class DeviceTargetMasks:
             res.append(self._dense[at:at + n, :h, :w].to(torch.bool))
             at += n
         return res
+
+
+# ---- polygon annotations on the device -----------------------------------------------------------------------------------------------------------
+POLY_DESC_FIELDS = ("dst_off", "h", "w", "stride_words", "poly_first", "poly_count", "reserved0", "reserved1")
+assert len(POLY_DESC_FIELDS) == _lib.POLY_DESC_WORDS and _lib.POLY_REC_WORDS == 2
+
+
+def polygon_tables(segmentations, sizes, offsets=None):
+    """The three int32 tables toist_polygon_masks reads (include/toist_hip.h), in plain numpy: segmentations[i] = the list of flat polygons (x0, y0, x1,
+    y1, ...) of object i, sizes[i] = its (h, w); offsets[i] = the byte offset of its packed rows in the destination (default: one object behind the
+    other, each h rows of ceil(w / 32) words).  -> (verts int32 [V, 2] on rleFrPoly's 5x grid, int(5.0 * c + .5) in float64 as polygon_to_mask computes
+    it; polys int32 [P, 2] = first vertex, vertex count; desc int32 [N, POLY_DESC_WORDS]; trace steps summed over every polygon).  An object of size
+    (0, 0) is a dead slot: an all-zero row, nothing is written for it.  Every polygon passes coco_eval.polygon_vertices; raises ValueError otherwise."""
+    from .coco_eval import polygon_vertices
+    if sizes is None or len(segmentations) != len(sizes):
+        raise ValueError(f"polygon_tables: {len(segmentations)} objects for {0 if sizes is None else len(sizes)} sizes")
+    if offsets is not None and len(offsets) != len(sizes):
+        raise ValueError(f"polygon_tables: {len(offsets)} offsets for {len(sizes)} objects")
+    verts, polys, steps, at = [], [], 0, 0
+    desc = np.zeros((len(sizes), _lib.POLY_DESC_WORDS), dtype=np.int32)
+    n_verts = 0
+    for i, (polygons, hw) in enumerate(zip(segmentations, sizes)):
+        h, w = int(hw[0]), int(hw[1])
+        if h < 0 or w < 0 or (h == 0) != (w == 0):
+            raise ValueError(f"polygon_tables: object {i} has the size {h} x {w}")
+        polygons = list(polygons)
+        if h == 0:
+            if polygons:
+                raise ValueError(f"polygon_tables: object {i} has polygons and the size 0 x 0 of a dead slot")
+            continue
+        first = len(polys)
+        for poly in polygons:
+            xy, n = polygon_vertices(poly)
+            verts.append(np.trunc(5.0 * xy + .5).astype(np.int32))          # polygon_vertices has checked that the grid fits int32
+            polys.append((n_verts, xy.shape[0]))
+            n_verts += xy.shape[0]
+            steps += n
+        stride = (w + 31) // 32
+        off = at if offsets is None else int(offsets[i])
+        if off < 0 or off % 4 or off + h * stride * 4 >= 2 ** 31:
+            raise ValueError(f"polygon_tables: object {i}: a destination offset of {off} bytes (a non-negative multiple of 4, addressed with 31 bits)")
+        desc[i, :6] = (off, h, w, stride, first, len(polys) - first)
+        at = off + h * stride * 4
+    verts = np.concatenate(verts, axis=0) if verts else np.zeros((0, 2), dtype=np.int32)
+    return verts, np.asarray(polys, dtype=np.int32).reshape(-1, 2), desc, steps
+
+
+@dataclass(frozen=True)
+class PackedPolygons:
+    """What DevicePolygonMasks.pack() placed: the object slots, their (h, w), the byte offsets of their packed rows, the polygons, vertices and trace
+    steps of the batch, the end of the packed destination range and the bytes of the one host-to-device copy."""
+    objects: int
+    sizes: tuple
+    offsets: tuple
+    polygons: int
+    vertices: int
+    trace_steps: int
+    packed_bytes: int
+    link_bytes: int
+
+
+class DevicePolygonMasks:
+    """The polygon annotations of a batch's objects -> their masks on the device, bit for bit coco_eval.convert_coco_poly_to_mask (every polygon
+    maskApi.c's rleFrPoly, an object's polygons merged by union): ONE launch (csrc/poly.hip: toist_polygon_masks).  The host link carries the grid
+    vertices, 8 bytes each, instead of masks.
+    Owns fixed-address device memory -- one blob: the descriptor table [max_objects, POLY_DESC_WORDS], the polygon records [max_polygons, 2], the vertex
+    table [max_vertices, 2] -- and its pinned host image.
+      pack(segmentations, sizes, offsets=None) : segmentations[i] = the list of flat polygons of object i, sizes[i] = its (h, w) ((0, 0) = a dead slot);
+                              fills the pinned image and issues ONE asynchronous host-to-device copy on the current stream -> PackedPolygons
+      rasterise(dst, offsets=None) : one launch into dst (uint8 [bytes] on the device): object i's h rows of ceil(w / 32) words in pack_mask_bits'
+                              layout at its offset, every word written, nothing else.  Sizes come from the device only, so the launch can be captured
+                              once and replayed after every pack().  `offsets` replaces the offsets pack() placed (one more small copy).
+      dense(packed)         : list of bool [h_i, w_i] device tensors;  dense_into(out): the live regions into a uint8 [slots, cap_h, cap_w] of the caller's
+    Every capacity (max_objects, max_polygons, max_vertices, max_hw with at most kernels.POLYGON_MAX_ROWS rows, and max_trace_steps = the launch's work,
+    the sum over all edges of max(|dx|, |dy|) on the 5x grid: a vertex far outside the image is legal and must not buy unbounded device time) is checked
+    on the host and raises ValueError before anything is copied or launched."""
+
+    def __init__(self, device, max_objects, max_polygons, max_vertices, max_hw, max_trace_steps):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DevicePolygonMasks rasterises in GPU memory: there is no CPU path")
+        self._set_capacities(max_objects, max_polygons, max_vertices, max_hw, max_trace_steps)
+        self.blob = torch.zeros(self._blob_bytes, dtype=torch.uint8, device=self.device)
+        words = self.blob.view(torch.int32)
+        self.desc = words[:self._polys_at // 4].view(self.max_objects, _lib.POLY_DESC_WORDS)
+        self.polys = words[self._polys_at // 4:self._verts_at // 4].view(self.max_polygons, 2)
+        self.verts = words[self._verts_at // 4:].view(self.max_vertices, 2)
+        self._host = torch.zeros(self._blob_bytes, dtype=torch.uint8).pin_memory()
+        self._host_np = self._host.numpy()
+        self._dense = None                                    # uint8 [max_objects, *max_hw], on the first dense()
+        self._event = None
+        self.last = None                                      # the PackedPolygons of the last pack()
+        self._end = 0                                         # where the packed rows end under the offsets the device holds
+
+    def _set_capacities(self, max_objects, max_polygons, max_vertices, max_hw, max_trace_steps):
+        """The capacities and the byte layout they imply (host only)."""
+        self.max_objects, self.max_polygons, self.max_vertices = int(max_objects), int(max_polygons), int(max_vertices)
+        self.max_hw, self.max_trace_steps = (int(max_hw[0]), int(max_hw[1])), int(max_trace_steps)
+        if min(self.max_objects, self.max_polygons, self.max_vertices, self.max_trace_steps, *self.max_hw) <= 0:
+            raise ValueError("DevicePolygonMasks: capacities must be positive")
+        if self.max_hw[0] > _lib.POLY_MAX_ROWS:
+            raise ValueError(f"DevicePolygonMasks: images of {self.max_hw[0]} rows: the kernel's plane holds {_lib.POLY_MAX_ROWS}")
+        self._polys_at = self.max_objects * _lib.POLY_DESC_WORDS * 4
+        self._verts_at = self._polys_at + self.max_polygons * 8
+        self._blob_bytes = self._verts_at + self.max_vertices * 8
+        if self.max_objects > 65535 or self._blob_bytes >= 2 ** 31:
+            raise ValueError("DevicePolygonMasks: at most 65535 objects, and the blob is addressed with 31 bits")
+
+    # -- host side ----------------------------------------------------------------------------------------------------------------------
+    def _layout(self, segmentations, sizes, offsets=None):
+        """Host check + tables of a batch: -> (PackedPolygons, verts, polys, desc).  Raises ValueError on an invalid polygon and on any capacity
+        overrun; touches no buffer."""
+        verts, polys, desc, steps = polygon_tables(segmentations, sizes, offsets)
+        for what, n, cap in (("objects", desc.shape[0], self.max_objects), ("polygons", polys.shape[0], self.max_polygons),
+                             ("vertices", verts.shape[0], self.max_vertices), ("trace steps", steps, self.max_trace_steps)):
+            if n > cap:
+                raise ValueError(f"DevicePolygonMasks: {n} {what} exceed max_{what.replace(' ', '_')} = {cap}")
+        if desc.shape[0] and (desc[:, 1].max() > self.max_hw[0] or desc[:, 2].max() > self.max_hw[1]):
+            raise ValueError(f"DevicePolygonMasks: an image of {int(desc[:, 1].max())} x {int(desc[:, 2].max())} exceeds max_hw = {self.max_hw[0]} x {self.max_hw[1]}")
+        ends = desc[:, 0].astype(np.int64) + desc[:, 1].astype(np.int64) * desc[:, 3] * 4
+        packed = PackedPolygons(desc.shape[0], tuple((int(r[1]), int(r[2])) for r in desc), tuple(int(r[0]) for r in desc), polys.shape[0], verts.shape[0],
+                                steps, int(ends.max()) if ends.size else 0, self._verts_at + verts.shape[0] * 8)
+        return packed, verts, polys, desc
+
+    def pack(self, segmentations, sizes, offsets=None, _layout=None):
+        """The batch into the blob: descriptors, polygon records and grid vertices into the pinned image, then one asynchronous copy of its used head
+        on the current stream (the previous copy out of the pinned image is waited for first).  -> PackedPolygons."""
+        packed, verts, polys, desc = _layout if _layout is not None else self._layout(segmentations, sizes, offsets)
+        if self._event is not None:
+            self._event.synchronize()
+        host = self._host_np.view(np.int32)
+        table = host[:self._polys_at // 4].reshape(self.max_objects, _lib.POLY_DESC_WORDS)
+        table[:] = 0                                            # slots behind the batch's objects: h = 0 = dead, not written
+        table[:desc.shape[0]] = desc
+        host[self._polys_at // 4:self._polys_at // 4 + polys.size] = polys.reshape(-1)
+        host[self._verts_at // 4:self._verts_at // 4 + verts.size] = verts.reshape(-1)
+        self.blob[:packed.link_bytes].copy_(self._host[:packed.link_bytes], non_blocking=True)
+        self._event = torch.cuda.Event()
+        self._event.record()
+        self.last, self._end = packed, packed.packed_bytes
+        return packed
+
+    # -- device side --------------------------------------------------------------------------------------------------------------------
+    def rasterise(self, dst, offsets=None):
+        """One launch of the batch that pack() placed into dst, uint8 [bytes] on the device (see the class)."""
+        from . import kernels
+        if self.last is None:
+            raise ValueError("DevicePolygonMasks.rasterise: nothing is packed")
+        if not torch.is_tensor(dst) or dst.dtype != torch.uint8 or dst.dim() != 1 or not dst.is_contiguous() or dst.device != self.blob.device:
+            raise ValueError("DevicePolygonMasks.rasterise: the destination is a contiguous uint8 [bytes] tensor on the rasteriser's device")
+        end = self._end
+        if offsets is not None:
+            offsets = tuple(int(o) for o in offsets)
+            if len(offsets) != self.last.objects or any(o < 0 or o % 4 for o in offsets):
+                raise ValueError(f"DevicePolygonMasks.rasterise: {len(offsets)} offsets for {self.last.objects} objects (non-negative multiples of 4)")
+            end = max((o + h * ((w + 31) // 32) * 4 for o, (h, w) in zip(offsets, self.last.sizes) if h), default=0)
+            if end >= 2 ** 31:
+                raise ValueError("DevicePolygonMasks.rasterise: the destination is addressed with 31 bits")
+        if end > dst.numel():
+            raise ValueError(f"DevicePolygonMasks.rasterise: the packed masks end at byte {end}, the destination holds {dst.numel()}")
+        if offsets is not None:
+            if self._event is not None:
+                self._event.synchronize()
+            table = self._host_np.view(np.int32)[:self._polys_at // 4].reshape(self.max_objects, _lib.POLY_DESC_WORDS)
+            table[:self.last.objects, 0] = [o if h else 0 for o, (h, _) in zip(offsets, self.last.sizes)]
+            self.blob[:self._polys_at].copy_(self._host[:self._polys_at], non_blocking=True)
+            self._event = torch.cuda.Event()
+            self._event.record()
+            self._end = end
+        kernels.polygon_masks(self.desc, self.polys, self.verts, dst, cap_hw=self.max_hw)
+        return dst
+
+    def dense_into(self, out):
+        """One launch of the batch that pack() placed into `out`, uint8 (or bool) [slots, cap_h, cap_w] of the caller's: the live h x w region of
+        every slot is written completely (0 / 1), the rest is left alone."""
+        from . import kernels
+        if self.last is None:
+            raise ValueError("DevicePolygonMasks.dense_into: nothing is packed")
+        if out.dim() != 3 or out.shape[0] > self.max_objects or out.shape[0] < self.last.objects:
+            raise ValueError(f"DevicePolygonMasks.dense_into: an output of {tuple(out.shape)} for {self.last.objects} objects (max_objects {self.max_objects})")
+        if any(h > out.shape[1] or w > out.shape[2] for h, w in self.last.sizes):
+            raise ValueError(f"DevicePolygonMasks.dense_into: masks of {self.last.sizes} do not fit {int(out.shape[1])} x {int(out.shape[2])}")
+        kernels.polygon_masks(self.desc[:out.shape[0]], self.polys, self.verts, out)
+        return out
+
+    def dense(self, packed):
+        """The masks of the batch that pack() returned `packed` for: bool [h_i, w_i] device tensors, copies cut from an internal [max_objects, *max_hw]
+        output that the next call overwrites."""
+        if packed is not self.last:
+            raise ValueError("DevicePolygonMasks.dense: `packed` is not the batch of the last pack()")
+        if self._dense is None:
+            self._dense = torch.zeros(self.max_objects, *self.max_hw, dtype=torch.uint8, device=self.device)
+        self.dense_into(self._dense)
+        return [self._dense[i, :h, :w].to(torch.bool) for i, (h, w) in enumerate(packed.sizes)]

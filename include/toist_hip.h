@@ -874,6 +874,20 @@ TOIST_API int toist_target_masks(const uint8_t* src, long long src_bytes, const 
 TOIST_API int toist_polygon_masks(const int32_t* desc, int slots, const int32_t* polys, int poly_cap, const int32_t* verts, int vert_cap, int cap_h,
                      int cap_w, uint8_t* dst, long long dst_bytes, int mode, void* stream);
 
+/* ---- task sweep: T captions over B images as P (image, caption) pairs (replaces the three torch.cat of Transformer.encode_native,
+ * toist_amd/transformer.py:559-565 = models/transformer.py:143-148 of the reference, for a batch whose rows are PAIRS: the image rows of pair p come
+ * from image pair_image[p], the caption rows from caption pair_caption[p]).  One launch; the tables are DEVICE int32 [P], so a captured launch serves
+ * any pairing.  With S = HW + L, all bf16 arrays 16-byte aligned, D % 8 == 0:
+ *   img_tok, img_pos bf16 [B, HW, D], img_pad bytes [B, HW]; txt_tok bf16 [T, L, D], txt_pad bytes [T, L]
+ *   tokens  bf16 [P, S, D] : rows 0 .. HW-1 = the pair's image rows, rows HW .. S-1 = its caption rows
+ *   pos     bf16 [P, S, D] : rows 0 .. HW-1 = the pair's img_pos rows, rows HW .. S-1 = 0 (what PositionEmbeddingSine.tokens(mask, tail=L) writes)
+ *   key_pad bytes [P, S]   : img_pad row | txt_pad row
+ * A pure copy: EVERY output byte is written, every element is bit-equal to its source.  A table entry outside [0, B) / [0, T) is never used as an
+ * index: that pair's tokens, pos and key_pad are zeros and *status = max(*status, p + 1) (int32, atomicMax; the caller zeroes and reads it). */
+TOIST_API int toist_sweep_assemble(const void* img_tok, const void* img_pos, const uint8_t* img_pad, int B, int HW, const void* txt_tok,
+                     const uint8_t* txt_pad, int T, int L, const int32_t* pair_image, const int32_t* pair_caption, int P, int D, void* tokens,
+                     void* pos, uint8_t* key_pad, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedEvalStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
+"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedEvalStep, CapturedSweepStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
 core they share: bucket keys, the static image / text inputs of a bucket and the upload into them, the LRU of buckets, the eager pass followed by the
 capture, and the rule that voids captured graphs once the XCD-resident decoder launches have been turned off."""
 from collections import OrderedDict
@@ -48,7 +48,7 @@ def upload(ent, samples, tokenized):
 
 
 class _CapturedStep:
-    """What the three steps share.  A subclass sets device (+ pad_hw, pad_tokens, max_graphs and _static_inputs(key) when it has more than one bucket)."""
+    """What the captured steps share.  A subclass sets device (+ pad_hw, pad_tokens, max_graphs and _static_inputs(key) when it has more than one bucket)."""
 
     def _init_capture_state(self, side=None, xdec_seen=False):
         self._buckets = OrderedDict()          # (Hp, Wp, Lp) -> dict(static inputs and outputs of the bucket, **_NO_GRAPH), least recently used first
@@ -430,6 +430,132 @@ class CapturedEvalStep(_CapturedStep):
         # (the eval-mode decode checks, and if need be repeats, an XCD-resident launch of the eager pass by itself)
         self._eager_then_capture(ent, lambda: self._forward(ent, key))
         return self._results(ent, orig)
+
+    __call__ = step
+
+
+class CapturedSweepStep(_CapturedStep):
+    """Task-sweep inference replayed from hipGraphs: `captions` captions over the `batch` images of a batch as up to `pairs` (image, caption) pairs, at
+    the cost of ONE image pass per image and ONE text pass per caption (toist_amd/sweep.py).  One graph per input-shape bucket (Hp, Wp, Lp) -- the
+    padding rules and the LRU of `max_graphs` are the shared core's -- holds the image stage, the text stage (a parallel branch), the
+    toist_sweep_assemble launch, the encoder, decode and kernels.postprocess.  Everything runs under torch.no_grad() with the model in eval().
+
+    step(samples, tokenized, orig_sizes, pairs=None) -> (results, pair_image, pair_caption, live): results[p], p < live, is PostProcess's dict of pair
+    (pair_image[p], pair_caption[p]) -- views into the bucket's output buffers, valid until the next step of that bucket; sweep.keyed_results keys
+    them.  pairs: a list of (image, caption), at most the capacity; default every caption on every image, image-major.  The tables are padded to the
+    capacity with the pair (0, 0); the padded rows are computed and never handed out.
+    The pair tables and the per-pair size table (each pair's original (h, w), gathered by pair_image on the host) sit at fixed addresses per bucket;
+    they are uploaded when they CHANGE -- the full product of a whole evaluation is uploaded once.  The graph's assemble launch checks every entry it
+    reads: its status word and the XCD-resident decoder's are read after every replay, where the results are handed out (one synchronisation).  A
+    refused entry raises ValueError (and the tables are uploaded afresh by the next step); a failed decoder launch drops every graph, and the same
+    batch runs again on the per-op launches and is captured again, as in CapturedEvalStep.
+    No prototype choice inside the graph: a cluster criterion raises ValueError -- harness.evaluate_sweep's eager loop serves it."""
+
+    def __init__(self, model, cluster_criterion=None, *, batch, captions, pairs=None, pad_hw=64, pad_tokens=1, max_graphs=4, device=None):
+        if cluster_criterion is not None:
+            raise ValueError("CapturedSweepStep takes no cluster criterion: the prototype choice of a sweep runs in harness.evaluate_sweep's eager loop")
+        if hasattr(model, "detr"):
+            model.encode_sweep()                           # a mask-head model: NotImplementedError naming the follow-up
+        self.model = model
+        self.batch, self.captions = int(batch), int(captions)
+        self.pairs = self.batch * self.captions if pairs is None else int(pairs)
+        if self.batch <= 0 or self.captions <= 0 or self.pairs <= 0:
+            raise ValueError(f"CapturedSweepStep: batch = {batch}, captions = {captions}, pairs = {pairs}")
+        self.pad_hw, self.pad_tokens, self.max_graphs = int(pad_hw), int(pad_tokens), int(max_graphs)
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        self.num_queries = model.query_embed.weight.shape[0]
+        self._init_capture_state()
+
+    def _static_inputs(self, key):
+        Hp, Wp, Lp = key
+        dev, P = self.device, self.pairs
+        pad_id = _pad_id(self.model)
+        ent = {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, dev), **_NO_GRAPH,
+               "pair_image": torch.zeros(P, dtype=torch.int32, device=dev), "pair_caption": torch.zeros(P, dtype=torch.int32, device=dev),
+               "sizes": torch.ones(P, 2, dtype=torch.int64, device=dev),
+               # staging: rows 0 .. P = pair_image, P .. 2P = pair_caption (int32); the sizes (int64)
+               "tables_host": torch.zeros(2 * P, dtype=torch.int32).pin_memory(), "sizes_host": torch.ones(P, 2, dtype=torch.int64).pin_memory(),
+               "tables_event": None, "uploaded": None, "out": None}
+        ent["tok"] = static_inputs(self.captions, 1, 1, Lp, pad_id, dev)["tok"]              # the text inputs hold the CAPTIONS, not one row per image
+        return ent
+
+    def _fill(self, ent, samples, tokenized, pi, pc, sizes):
+        upload(ent, samples, tokenized)
+        tables = (pi.tolist(), pc.tolist(), sizes)
+        if ent["uploaded"] == tables:
+            return
+        P = self.pairs
+        if ent["tables_event"] is not None:
+            ent["tables_event"].synchronize()          # the previous upload has left the staging buffers
+        ent["tables_host"][:P] = pi
+        ent["tables_host"][P:] = pc
+        ent["sizes_host"].copy_(torch.tensor(sizes, dtype=torch.int64))
+        ent["pair_image"].copy_(ent["tables_host"][:P], non_blocking=True)
+        ent["pair_caption"].copy_(ent["tables_host"][P:], non_blocking=True)
+        ent["sizes"].copy_(ent["sizes_host"], non_blocking=True)
+        ent["tables_event"] = torch.cuda.Event()
+        ent["tables_event"].record()
+        ent["uploaded"] = tables
+
+    def _forward(self, ent):
+        """The launches of one batch on the bucket's static inputs (eagerly, and once more under capture)."""
+        state, text = self.model.sweep_stages(ent["samples"], ent["tok"])
+        mc = self.model.sweep_pairs(state, text, ent["pair_image"], ent["pair_caption"], check=False)       # (step reads the status word)
+        outputs = self.model.decode(mc)
+        ent["out"] = kernels.postprocess(outputs["pred_logits"], outputs["pred_boxes"], ent["sizes"], outputs.get("pred_isfinal"), out=ent["out"])
+
+    def _results(self, ent, live):
+        from .postprocessors import PostProcess
+        out, P, Q = ent["out"], self.pairs, self.num_queries
+        lkey = (str(self.device), P, Q)
+        labels = PostProcess._LABELS.get(lkey)
+        if labels is None:
+            labels = PostProcess._LABELS[lkey] = torch.ones(P, Q, dtype=torch.int64, device=self.device)
+        results = []
+        for p in range(live):
+            r = {"scores": out["scores"][p], "labels": labels[p], "boxes": out["boxes"][p]}
+            if "scores_refexp" in out:
+                r["scores_refexp"] = out["scores_refexp"][p]
+            results.append(r)
+        return results
+
+    def _handed_out(self, ent):
+        """Read the assemble launch's status word where the results are handed out (it synchronises): a refused table entry raises ValueError."""
+        try:
+            kernels.sweep_check()
+        except ValueError:
+            ent["uploaded"] = None                         # whatever the device tables hold now, the next step uploads them afresh
+            raise
+
+    @torch.no_grad()
+    def step(self, samples, tokenized, orig_sizes, pairs=None):
+        from . import sweep
+        if isinstance(tokenized, (list, tuple)) and len(tokenized) and isinstance(tokenized[0], str):
+            tokenized = self.model.transformer._tokenize(list(tokenized), self.device)
+        if samples.tensors.shape[0] != self.batch or tokenized["input_ids"].shape[0] != self.captions:
+            raise ValueError(f"CapturedSweepStep was built for {self.batch} images and {self.captions} captions "
+                             f"(got {samples.tensors.shape[0]} and {tokenized['input_ids'].shape[0]})")
+        orig = CapturedEvalStep._pairs(orig_sizes)
+        if len(orig) != self.batch or any(h <= 0 or w <= 0 for h, w in orig):
+            raise ValueError(f"CapturedSweepStep: {len(orig)} original sizes for {self.batch} images, or a size that is not positive")
+        pi, pc, live = sweep.pair_tables(self.batch, self.captions, pairs, capacity=self.pairs)           # ValueError before anything is launched
+        sizes = [orig[i] for i in pi.tolist()]
+        if self.model.training:
+            self.model.eval()
+        key = self.bucket_of(samples, tokenized)
+        ent = self._entry(key)
+        self._fill(ent, samples, tokenized, pi, pc, sizes)
+        if ent["graph"] is not None:
+            ent["graph"].replay()
+            self.replays += 1
+            failed = ent["xdec"] and kernels.xdec_check(raise_on_failure=False)          # (one 4-byte read each; the first synchronises)
+            self._handed_out(ent)
+            if not failed:
+                return self._results(ent, live), pi, pc, live
+            self._void_graphs(force=True)                  # the decoder launch's groups were not co-resident: per-op launches from now on, same batch again
+        self._eager_then_capture(ent, lambda: self._forward(ent))
+        self._handed_out(ent)
+        return self._results(ent, live), pi, pc, live
 
     __call__ = step
 

@@ -1,0 +1,79 @@
+// Task-sweep assembly: the P cross-modal sequences of a sweep of T captions over B images in ONE launch (replaces the three torch.cat of
+// Transformer.encode_native, reference models/transformer.py:143-148, for a batch whose rows are (image, caption) PAIRS).  Pair p takes its image rows
+// from image pair_image[p] and its caption rows from caption pair_caption[p]; both tables live on the device, so one captured launch serves any pairing.
+//     tokens [P, S, D] bf16 : rows 0 .. HW-1 = img_tok[i], rows HW .. S-1 = txt_tok[t]          (S = HW + L)
+//     pos    [P, S, D] bf16 : rows 0 .. HW-1 = img_pos[i], rows HW .. S-1 = 0
+//     key_pad [P, S] bytes  : img_pad[i] | txt_pad[t]
+// A pure copy: every output byte is written (no memset before the launch), every element is bit-equal to its source.  A table entry outside [0, B) /
+// [0, T) is never used as an index: that pair becomes zeros (key_pad 0 as well) and p + 1 goes into *status with atomicMax -- a captured launch reads
+// tables the host rewrote after the capture, so the guard sits on the device.
+// Half a wave owns one row: 32 lanes x 16 bytes = the 512 bytes of a d_model = 256 row in one access each way; the rows go round the grid in a stride
+// loop.  Traffic: 2 * P*S*D*2 bytes out, P*HW*D*2*2 + P*L*D*2 in (L2 serves the repeats of an image): ~48 MB + ~46 MB at B = 8, T = 14, 640 x 640.
+#include "common.h"
+
+namespace toist {
+
+static constexpr int SW_THREADS = 256;
+static constexpr int SW_LANES = 32;                         // lanes of one row
+static constexpr int SW_ROWS = SW_THREADS / SW_LANES;       // rows of one workgroup pass
+static constexpr int SW_MAX_BLOCKS = 1024;                  // 4 workgroups per CU of 256
+
+__global__ __launch_bounds__(SW_THREADS) void sweep_assemble_kernel(const uint4* __restrict__ img_tok, const uint4* __restrict__ img_pos,
+                                                                     const uint8_t* __restrict__ img_pad, int B, int HW,
+                                                                     const uint4* __restrict__ txt_tok, const uint8_t* __restrict__ txt_pad, int T, int L,
+                                                                     const int32_t* __restrict__ pair_image, const int32_t* __restrict__ pair_caption,
+                                                                     int rows, int V, uint4* __restrict__ tokens, uint4* __restrict__ pos,
+                                                                     uint8_t* __restrict__ key_pad, int32_t* __restrict__ status) {
+    const int S = HW + L;
+    const int lane = threadIdx.x & (SW_LANES - 1);
+    for (long long r = (long long)blockIdx.x * SW_ROWS + (threadIdx.x / SW_LANES); r < rows; r += (long long)gridDim.x * SW_ROWS) {
+        const int p = (int)r / S, s = (int)r - p * S;                 // r < rows < 2^31 (the stride alone may step past it)
+        const int i = pair_image[p], t = pair_caption[p];
+        const bool ok = (unsigned)i < (unsigned)B && (unsigned)t < (unsigned)T;
+        const bool image_row = s < HW;
+        // (computed only from checked indices)
+        const size_t src_row = !ok ? 0 : image_row ? (size_t)i * HW + s : (size_t)t * L + (s - HW);
+        const uint4* tok_src = (image_row ? img_tok : txt_tok) + src_row * V;
+        const uint4* pos_src = img_pos + (image_row ? src_row : 0) * V;
+        uint4* tok_dst = tokens + (size_t)r * V;
+        uint4* pos_dst = pos + (size_t)r * V;
+        for (int c = lane; c < V; c += SW_LANES) {
+            uint4 tv = make_uint4(0u, 0u, 0u, 0u), pv = make_uint4(0u, 0u, 0u, 0u);
+            if (ok) {
+                tv = tok_src[c];
+                if (image_row) pv = pos_src[c];
+            }
+            tok_dst[c] = tv;
+            pos_dst[c] = pv;
+        }
+        if (lane == 0) {
+            key_pad[r] = !ok ? (uint8_t)0 : image_row ? img_pad[src_row] : txt_pad[src_row];
+            if (!ok && s == 0) atomicMax(status, p + 1);
+        }
+    }
+}
+
+}  // namespace toist
+
+using namespace toist;
+
+extern "C" int toist_sweep_assemble(const void* img_tok, const void* img_pos, const uint8_t* img_pad, int B, int HW, const void* txt_tok,
+                                    const uint8_t* txt_pad, int T, int L, const int32_t* pair_image, const int32_t* pair_caption, int P, int D,
+                                    void* tokens, void* pos, uint8_t* key_pad, int32_t* status, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    TOIST_REQUIRE(B > 0 && HW > 0 && T > 0 && L > 0 && P >= 0 && D > 0, "toist_sweep_assemble: bad extents B=%d HW=%d T=%d L=%d P=%d D=%d", B, HW, T, L, P, D);
+    TOIST_REQUIRE(D % 8 == 0, "toist_sweep_assemble: D=%d is not a multiple of 8 (rows move as 16-byte accesses)", D);
+    const long long S = (long long)HW + L, rows = (long long)P * S;
+    TOIST_REQUIRE(S < (1ll << 31) && rows < (1ll << 31) && (long long)B * HW < (1ll << 31) && (long long)T * L < (1ll << 31),
+                  "toist_sweep_assemble: P*(HW+L), B*HW and T*L must stay below 2^31 (P=%d HW=%d L=%d B=%d T=%d)", P, HW, L, B, T);
+    if (P == 0) return TOIST_OK;
+    TOIST_REQUIRE(img_tok && img_pos && img_pad && txt_tok && txt_pad && pair_image && pair_caption && tokens && pos && key_pad && status,
+                  "toist_sweep_assemble: null pointer");
+    TOIST_REQUIRE((((uintptr_t)img_tok | (uintptr_t)img_pos | (uintptr_t)txt_tok | (uintptr_t)tokens | (uintptr_t)pos) & 15) == 0,
+                  "toist_sweep_assemble: the bf16 arrays must be 16-byte aligned");
+    const long long want = (rows + SW_ROWS - 1) / SW_ROWS;
+    const dim3 grid((unsigned)(want < SW_MAX_BLOCKS ? want : SW_MAX_BLOCKS));
+    hipLaunchKernelGGL(sweep_assemble_kernel, grid, dim3(SW_THREADS), 0, stream, (const uint4*)img_tok, (const uint4*)img_pos, img_pad, B, HW,
+                       (const uint4*)txt_tok, txt_pad, T, L, pair_image, pair_caption, (int)rows, D / 8, (uint4*)tokens, (uint4*)pos, key_pad, status);
+    return check_launch("toist_sweep_assemble");
+}

@@ -5,7 +5,7 @@ from types import SimpleNamespace
 
 import torch
 
-from .captured import CapturedDistillStep, CapturedEvalStep, CapturedTrainStep  # noqa: F401
+from .captured import CapturedDistillStep, CapturedEvalStep, CapturedSweepStep, CapturedTrainStep  # noqa: F401
 from .transformer import TokenizedText
 
 
@@ -193,6 +193,92 @@ def _captured_eval_batch(captured, batch):
     if captured.cluster_criterion is not None:
         names, captions = [t["dataset_name"] for t in targets], [t["caption"] for t in targets]
     return captured.step(batch["samples"], text, orig, sizes, dataset_names=names, captions=captions)
+
+
+@torch.no_grad()
+def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criterion=None, captured=None, max_pairs=None, tokenized=None, observe=None):
+    """Task-sweep inference: every task's caption on every image of every batch, at the cost of ONE image pass per image and ONE text pass per
+    caption for the whole loop (the reference's loader makes one sample per (image, task): engine.py:253-342 runs the ResNet and RoBERTa once per pair).
+    tasks: [(name, caption[, dataset_name])]; batches yield dicts with "samples", "image_ids", "orig_sizes" ((h, w) per image, host values) and
+    optionally "pairs" (a list of (image, task) indices: only those; default every task on every image).
+    -> {(image_id, task_name): {"scores" [Q], "labels" [Q], "boxes" [Q, 4]}}: PostProcess's result of that pair, tensors on the device.
+    The text stage runs once, before the first batch.  max_pairs: the most pairs one pair stage (encoder, decoder, heads) may hold; a batch with more
+    runs it per group of max_pairs // B captions, every group on the same image state.
+    cluster_criterion: the prototype choice (ClusterCriterion.infer_choice) runs per pair stage, with each pair's dataset name and caption; it needs the
+    tasks' dataset names, and captions that answer char_to_token (strings through the model's tokenizer, or tokenized= a BatchEncoding of them).
+    captured: a CapturedSweepStep built around `model` -- image stage, text stage, assembly, decode and post-processing of a batch are one graph
+    replay; it takes no cluster criterion.  tokenized: the T captions already tokenized (offline use; else the strings go through the tokenizer).
+    observe: callable(memory_cache, outputs, pair_image, pair_caption) called after every eager pair stage (tests, logging)."""
+    from . import kernels, sweep
+    tasks = [tuple(t) for t in tasks]
+    if not tasks or any(len(t) not in (2, 3) for t in tasks):
+        raise ValueError("tasks is a non-empty list of (name, caption) or (name, caption, dataset_name)")
+    names, captions = [t[0] for t in tasks], [t[1] for t in tasks]
+    dataset_names = [t[2] if len(t) == 3 else None for t in tasks]
+    if len(set(names)) != len(names):
+        raise ValueError("task names must be unique: they key the results")
+    T = len(tasks)
+    if cluster_criterion is not None:
+        if captured is not None:
+            raise ValueError("a captured sweep takes no cluster criterion: run the eager loop (captured=None) for the prototype choice")
+        if any(n is None for n in dataset_names):
+            raise ValueError("the prototype choice needs every task's dataset name: tasks = [(name, caption, dataset_name)]")
+        cluster_criterion.eval()
+    model.eval()
+    text = tokenized if tokenized is not None else captions
+    out = {}
+    for batch in batches:
+        samples, image_ids, orig = batch["samples"], list(batch["image_ids"]), CapturedEvalStep._pairs(batch["orig_sizes"])
+        B = len(image_ids)
+        if len(orig) != B or samples.tensors.shape[0] != B:
+            raise ValueError(f"a batch of {samples.tensors.shape[0]} images with {B} image ids and {len(orig)} original sizes")
+        pi, pc, live = sweep.pair_tables(B, T, batch.get("pairs"))
+        if captured is not None:
+            results, pi, pc, live = captured.step(samples, text, orig, pairs=batch.get("pairs"))
+            out.update(sweep.keyed_results(results, image_ids, names, pi, pc, live))
+            continue
+        samples = samples.to(device)
+        if not hasattr(text, "flat"):
+            text = model.sweep_text(text, device=device)          # once: the captions do not change
+            if text.key_pad.shape[0] != T:
+                raise ValueError(f"{T} tasks but {text.key_pad.shape[0]} tokenized captions")
+        state = model.sweep_images(samples)
+        for lo, hi in _sweep_groups(pi, pc, B, T, max_pairs, product=batch.get("pairs") is None):
+            gi, gc = pi[lo:hi], pc[lo:hi]
+            mc = model.sweep_pairs(state, text, gi, gc)
+            if cluster_criterion is not None:
+                mc = cluster_criterion.infer_choice(mc, [dataset_names[t] for t in gc.tolist()], [captions[t] for t in gc.tolist()])
+            outputs = model.decode(mc)
+            sizes = torch.tensor([orig[i] for i in gi.tolist()], dtype=torch.int64).to(device, non_blocking=True)
+            results = postprocessor(outputs, sizes)
+            if observe is not None:
+                observe(mc, outputs, gi, gc)
+            out.update(sweep.keyed_results(results, image_ids, names, gi, gc))
+        kernels.sweep_check()     # (one 4-byte read: it synchronises) a pair table entry the launch refused
+        kernels.xdec_check()      # an XCD-resident decoder launch whose groups were not co-resident
+    return out
+
+
+def _sweep_groups(pair_image, pair_caption, B, T, max_pairs, product):
+    """The (lo, hi) slices of a batch's pair tables that each run as one pair stage.  The full product is image-major (p = i * T + t), so a group of
+    captions is not a slice of it: the tables are re-ordered IN PLACE group by group (image-major inside a group) -- the keys do not depend on the
+    order.  An explicit pair list is cut in its own order."""
+    P = pair_image.numel()
+    if max_pairs is None or P <= int(max_pairs):
+        return [(0, P)]
+    max_pairs = int(max_pairs)
+    if not product:
+        if max_pairs < 1:
+            raise ValueError("max_pairs must be at least 1")
+        return [(lo, min(lo + max_pairs, P)) for lo in range(0, P, max_pairs)]
+    per = max_pairs // B
+    if per < 1:
+        raise ValueError(f"max_pairs = {max_pairs} does not hold one caption on each of the batch's {B} images")
+    order = [i * T + t for g in range(0, T, per) for i in range(B) for t in range(g, min(g + per, T))]
+    index = torch.tensor(order, dtype=torch.int64)
+    pair_image.copy_(pair_image[index])
+    pair_caption.copy_(pair_caption[index])
+    return [(g * B, min(g + per, T) * B) for g in range(0, T, per)]
 
 
 @torch.no_grad()

@@ -1114,6 +1114,73 @@ def postprocess(pred_logits, pred_boxes, sizes_dev, pred_isfinal=None, out=None)
     return out
 
 
+# ---- task sweep (csrc/sweep.hip) ----------------------------------------------------------------------------------------------------------
+_SWEEP_STATUS = {}      # device -> int32[1]: max over the launches since the last sweep_check() of (first bad pair + 1)
+
+
+def sweep_status(device, create=True):
+    """The status word of the device's toist_sweep_assemble launches.  Allocated once per device and EAGERLY, like the XCD-resident decoder's control
+    words: a word taken from a capturing graph's pool could be handed out again inside that graph.  None while a capture runs and no word exists yet."""
+    device = torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
+    st = _SWEEP_STATUS.get(device)
+    if st is None and create:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        st = _SWEEP_STATUS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return st
+
+
+def sweep_check(raise_on_failure=True):
+    """Read (and clear) the status words of the task-sweep launches: one 4-byte read per device, it synchronises.  A set word means that a launch met a
+    pair-table entry outside its images / captions; that pair's sequence is zeros, so its results mean nothing.  -> 0, or the first such pair + 1
+    (raise_on_failure=False); raises ValueError otherwise.  Called where results are handed out: harness.evaluate_sweep, CapturedSweepStep.step."""
+    bad = 0
+    for st in _SWEEP_STATUS.values():
+        v = int(st.item())
+        if v:
+            st.zero_()
+            bad = bad or v
+    if bad and raise_on_failure:
+        raise ValueError(f"sweep_assemble: pair {bad - 1} names an image or a caption that does not exist (its sequence was zeroed on the device)")
+    return bad
+
+
+def sweep_assemble(img_tok, img_pos, img_pad, txt_tok, txt_pad, pair_image, pair_caption, out=None, check=True):
+    """The cross-modal sequences of P (image, caption) pairs in one launch (include/toist_hip.h: toist_sweep_assemble).  img_tok / img_pos bf16
+    [B, HW, D], img_pad bool or uint8 [B, HW], txt_tok bf16 [T, L, D], txt_pad bool or uint8 [T, L], pair_image / pair_caption int32 [P] ON THE DEVICE.
+    -> (tokens bf16 [P, S, D], pos bf16 [P, S, D], key_pad uint8 [P, S]), S = HW + L; `out` = such a triple to write into (fixed addresses for a
+    captured graph).  check: read the status word right away (synchronises; never during a capture) -- a caller that validated the tables on the host
+    passes False and calls sweep_check() where it hands its results out."""
+    B, HW, D = img_tok.shape
+    T, L = txt_tok.shape[:2]
+    P, S, dev = pair_image.numel(), HW + L, img_tok.device
+    u8 = lambda t: t.view(torch.uint8) if t.dtype == torch.bool else t
+    img_pad, txt_pad = u8(img_pad), u8(txt_pad)
+    if tuple(img_pos.shape) != (B, HW, D) or tuple(img_pad.shape) != (B, HW) or tuple(txt_tok.shape) != (T, L, D) or tuple(txt_pad.shape) != (T, L):
+        raise ValueError("sweep_assemble: img_tok / img_pos [B, HW, D], img_pad [B, HW], txt_tok [T, L, D] and txt_pad [T, L] must agree")
+    if pair_caption.numel() != P or pair_image.dim() != 1 or pair_caption.dim() != 1:
+        raise ValueError("sweep_assemble: pair_image and pair_caption are int32 vectors of one length")
+    for t in (img_tok, img_pos, img_pad, txt_tok, txt_pad, pair_image, pair_caption):
+        if not t.is_contiguous():
+            raise ValueError("sweep_assemble: every input must be contiguous")
+    status = sweep_status(dev)
+    if status is None:
+        raise RuntimeError("sweep_assemble: the first launch on a device cannot be captured (its status word is allocated outside any graph)")
+    if out is None:
+        out = (torch.empty(P, S, D, dtype=torch.bfloat16, device=dev), torch.empty(P, S, D, dtype=torch.bfloat16, device=dev),
+               torch.empty(P, S, dtype=torch.uint8, device=dev))
+    tokens, pos, key_pad = out
+    if tuple(tokens.shape) != (P, S, D) or tuple(pos.shape) != (P, S, D) or tuple(key_pad.shape) != (P, S) or not all(t.is_contiguous() for t in out):
+        raise ValueError("sweep_assemble: out = (tokens [P, S, D], pos [P, S, D], key_pad [P, S]), contiguous")
+    _lib.check(_lib.lib().toist_sweep_assemble(_p(img_tok, torch.bfloat16), _p(img_pos, torch.bfloat16), _p(img_pad, torch.uint8), B, HW,
+                                               _p(txt_tok, torch.bfloat16), _p(txt_pad, torch.uint8), T, L, _p(pair_image, torch.int32),
+                                               _p(pair_caption, torch.int32), P, D, _p(tokens, torch.bfloat16), _p(pos, torch.bfloat16),
+                                               _p(key_pad, torch.uint8), _p(status, torch.int32), _stream()), "toist_sweep_assemble")
+    if check and not torch.cuda.is_current_stream_capturing():
+        sweep_check()
+    return out
+
+
 def mask_pack(dense):
     """[n, h, w] bool / uint8 -> bit planes."""
     n, h, w = dense.shape

@@ -268,6 +268,113 @@ class MDETR(nn.Module):
         mc["_native"]["src_proj"] = tok
         return mc
 
+    # ---- task sweep: T captions over B images at the cost of B image passes and T text passes -------------------
+    # (inference only.  The backbone, input_proj and the position encoding depend on the image alone, RoBERTa + resizer on the caption alone; the two
+    # meet first in the cross-modal sequence, which toist_sweep_assemble builds for any list of (image, caption) pairs -- see toist_amd/sweep.py)
+    def _sweep_ready(self, tensor=None):
+        if torch.is_grad_enabled() or self.training:
+            raise RuntimeError("the task sweep is inference only: call it on model.eval() under torch.no_grad()")
+        if tensor is not None and not tensor.is_cuda:
+            raise RuntimeError("the task sweep needs device tensors (got a CPU tensor); there is no CPU fallback")
+
+    def sweep_images(self, samples):
+        """The image stage: backbone, input_proj, position tokens (no caption tail), mask -> sweep.SweepImages, reusable for any captions."""
+        from .sweep import SweepImages
+        if not isinstance(samples, NestedTensor):
+            samples = NestedTensor.from_tensor_list(samples)
+        self._sweep_ready(samples.tensors)
+        k.stamp("fwd.backbone.start")
+        feats = self.backbone[0].forward_native(samples.tensors, (4,), premasked=(0,))
+        k.stamp("fwd.backbone.end")
+        c5 = feats[-1]
+        B, h, w, _ = c5.shape
+        mask = nearest_mask(samples.mask, (h, w))
+        pos = self.backbone[1].tokens(mask, tail=0) if hasattr(self.backbone[1], "tokens") else \
+            self.backbone[1](NestedTensor(c5.permute(0, 3, 1, 2), mask)).flatten(2).permute(0, 2, 1).to(BF16).contiguous()
+        tok = self._project(c5).view(B, h * w, -1)
+        return SweepImages(tok, pos, mask, feats)
+
+    def _sweep_text(self, captions, device):
+        """sweep_text without the join -> (EncodedText, the side stream the caller's stream still has to wait for, or None)."""
+        from .transformer import EncodedText
+        if isinstance(captions, EncodedText):
+            return captions, None
+        side = None
+        if engine.overlap_enabled():
+            main = torch.cuda.current_stream()
+            side = engine.side_stream(device, "text")
+            k.stamp("fwd.fork")
+            side.wait_stream(main)
+        with torch.cuda.stream(side if side is not None else torch.cuda.current_stream()):
+            k.stamp("fwd.text.start")
+            tokenized = self.transformer._tokenize(captions, device)
+            flat, key_pad = self.transformer.encode_text(tokenized)
+            k.stamp("fwd.text.end")
+        return EncodedText(tokenized, flat, key_pad), side
+
+    def sweep_text(self, captions, device=None):
+        """The text stage: T caption strings (or a tokenized batch of T rows) -> EncodedText, reusable for any images.  Runs on the text side stream, as
+        encode's text branch does; the current stream has joined it on return."""
+        self._sweep_ready()
+        device = torch.device(device) if device is not None else self.query_embed.weight.device
+        if device.type != "cuda":
+            raise RuntimeError("the task sweep needs the model on the device; there is no CPU fallback")
+        text, side = self._sweep_text(captions, device)
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+            k.stamp("fwd.join")
+        return text
+
+    def sweep_pairs(self, image_state, text, pair_image, pair_caption, out=None, tokenized=None, check=None):
+        """The pair stage: one toist_sweep_assemble launch builds the cross-modal sequences of the P pairs (pair_image[p], pair_caption[p]), the encoder
+        runs over them -> an ordinary MemoryCache of batch P: decode(), PostProcess and ClusterCriterion.infer_choice take it unchanged.
+        pair_image / pair_caption: lists or host tensors (checked here, then uploaded), or int32 DEVICE vectors (checked by the launch: its status word
+        is read right away outside a capture -- check=False leaves that to the caller, as CapturedSweepStep does).  out: (tokens, pos, key_pad) buffers at fixed addresses.
+        tokenized: what the cache carries as "tokenized"; by default a sweep.SweepTokenized over the captions' rows (host tables only)."""
+        from . import sweep
+        self._sweep_ready(image_state.tok)
+        B, HW, d = image_state.tok.shape
+        T, L = text.key_pad.shape
+        dev = image_state.tok.device
+        on_device = torch.is_tensor(pair_image) and pair_image.is_cuda
+        if on_device:
+            pi, pc = pair_image, pair_caption
+        else:
+            pi_host, pc_host = sweep.check_tables(pair_image, pair_caption, B, T)
+            pi, pc = pi_host.to(dev, non_blocking=True), pc_host.to(dev, non_blocking=True)
+            if tokenized is None and text.tokenized is not None:
+                tokenized = sweep.SweepTokenized(text.tokenized, pc_host)
+        P = pi.numel()
+        tokens, pos, key_pad = k.sweep_assemble(image_state.tok, image_state.pos, image_state.mask.flatten(1), text.flat.view(T, L, d), text.key_pad,
+                                                pi, pc, out=out, check=on_device if check is None else check)
+        S = HW + L
+        mask = key_pad.view(torch.bool)
+        mc = self.transformer.encode_sequences(tokens.view(P * S, d), pos.view(P * S, d), mask, P, S, L, self.query_embed.weight, tokenized,
+                                               mask[:, HW:], tokens[:, HW:])
+        mc["_native"].update(features=image_state.feats, cuts={}, feat_mask=image_state.mask, src_proj=image_state.tok, pair_image=pi, pair_caption=pc)
+        return mc
+
+    def encode_sweep(self, samples, captions, pairs=None):
+        """sweep_images + sweep_text + sweep_pairs: the memory cache of `pairs` (a list of (image, caption) indices; default: every caption on every
+        image, image-major, p = i * T + t).  Callers that sweep many batches with the same captions keep sweep_text's result and call the stages."""
+        from . import sweep
+        state, text = self.sweep_stages(samples, captions)
+        pi, pc, _ = sweep.pair_tables(state.tok.shape[0], text.key_pad.shape[0], pairs)
+        return self.sweep_pairs(state, text, pi, pc)
+
+    def sweep_stages(self, samples, captions):
+        """sweep_images and sweep_text side by side -> (image state, EncodedText): the text stage runs on its side stream beside the backbone (a parallel
+        branch of a captured graph), as the two branches of encode do.  captions may be an EncodedText kept from an earlier call."""
+        if not isinstance(samples, NestedTensor):
+            samples = NestedTensor.from_tensor_list(samples)
+        self._sweep_ready(samples.tensors)
+        text, side = self._sweep_text(captions, samples.tensors.device)
+        state = self.sweep_images(samples)
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+        k.stamp("fwd.join")
+        return state, text
+
     def decode(self, memory_cache):
         native = memory_cache.get("_native")
         key = "img_memory_mod" if (self.args is not None and getattr(self.args, "cluster", False)) else "img_memory"

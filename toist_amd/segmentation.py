@@ -481,6 +481,14 @@ class DETRsegm(nn.Module):
         out["pred_masks"] = self._masks(stack[-1], mem, src, c4, c3, c2, nat["feat_mask"], B, Q, h, w)
         return out
 
+    # ---- task sweep: detection models only ------------------------------------------------------------------
+    def _no_sweep(self, *args, **kw):
+        raise NotImplementedError("task sweep with a mask head: the mask program indexes its per-image FPN terms by row / Q, so a batch of (image, caption) "
+                                  "pairs needs a pair table inside the mask-head kernels -- the follow-up 'DETRsegm sweeps: share the FPN terms of an "
+                                  "image among its pairs'.  Sweep a detection model (MDETR.encode_sweep), or run the per-pair path")
+
+    sweep_images = sweep_text = sweep_pairs = sweep_stages = encode_sweep = _no_sweep
+
 
 # ------------------------------------------------------------------------------------------ mask losses
 class _MaskLossFn(torch.autograd.Function):

@@ -563,6 +563,13 @@ class Transformer(nn.Module):
         else:
             pos = torch.cat([pos_img, torch.zeros(B, L, d, dtype=BF16, device=dev)], dim=1).reshape(B * S, d).contiguous()
         mask = torch.cat([mask_img, text_attention_mask], dim=1)
+        return self.encode_sequences(tokens, pos, mask, B, S, L, query_embed, tokenized, text_attention_mask, text_tok, text_memory_resized)
+
+    def encode_sequences(self, tokens, pos, mask, B, S, L, query_embed, tokenized, text_attention_mask, text_tok, text_memory_resized=None):
+        """The encoder layers over B assembled cross-modal sequences and the memory_cache around their output: what encode_native does behind its
+        torch.cat, and what MDETR.sweep_pairs does behind toist_sweep_assemble (there B counts (image, caption) pairs).  tokens / pos: bf16 [B*S, d];
+        mask: bool [B, S]; text_tok: bf16 [B, L, d], the caption rows of `tokens`."""
+        d = tokens.shape[-1]
         key_pad = mask.view(torch.uint8)
         mem = self.encode_tokens(tokens, pos, key_pad, B, S)
         mem3 = mem.view(B, S, d)

@@ -43,24 +43,22 @@ def test_live_static_targets_pack_carries_the_word_behind_the_seven_views():
     views, total0 = StaticTargets.arena_views(B, B * per, K)
     total = total0 + 16
 
-    def host_only(cls, size):
-        st = cls.__new__(cls)
-        st.B, st.max_per_image, st.Q, st.K, st.mask_hw, st.cap = B, per, 10, K, None, B * per
-        st._views, st._host, st._live_off = views, torch.zeros(size, dtype=torch.uint8), total0
-        return st
+    host_only = lambda cls: cls(B, per, 10, K, device="cpu")         # (a host-only instance: ordinary buffers, no GPU runtime)
     targets = [{"boxes": torch.rand(2, 4)}, {"boxes": torch.rand(1, 4)}]
     pm, masks = torch.rand(3, K), torch.tensor([[6, 0, 0, 0], [1, 0, 0, 0], [1 << 40, 0, 0, 0]], dtype=torch.int64)
-    st = host_only(LiveStaticTargets, total)
-    host, sizes = st.pack(targets, pm, masks, out=st._host, live_tokens=11)
+    st = host_only(LiveStaticTargets)
+    own = st._stage.open()
+    assert own.numel() == total
+    host, sizes = st.pack(targets, pm, masks, out=own, live_tokens=11)
     word = st._live_word(host)
     assert sizes == [2, 1] and (word.dtype, word.tolist()) == (torch.int32, [11]) and word.data_ptr() == host.data_ptr() + total0
-    ref, _ = host_only(StaticTargets, total0).pack(targets, pm, masks, out=torch.zeros(total0, dtype=torch.uint8))
+    ref, _ = host_only(StaticTargets).pack(targets, pm, masks, out=torch.zeros(total0, dtype=torch.uint8))
     assert torch.equal(host[:total0], ref)                           # the seven segments sit where they sat and hold what they held
     assert views(host)[3].tolist() == [0, 2, 3] and views(host)[5].tolist() == [3.0]
-    host, _ = st.pack(targets, pm, masks, out=st._host, live_tokens=9)      # each side of a pair packs its own count
+    host, _ = st.pack(targets, pm, masks, out=own, live_tokens=9)      # each side of a pair packs its own count
     assert st._live_word(host).tolist() == [9]
     with pytest.raises(ValueError, match="live_tokens"):
-        st.pack(targets, pm, masks, out=st._host)
+        st.pack(targets, pm, masks, out=own)
 
 
 def test_caption_tables_of_a_longer_bucket_are_zero_beyond_the_caption():

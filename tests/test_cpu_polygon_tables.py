@@ -154,8 +154,8 @@ def _host_only_rasteriser(**caps):
     from toist_amd.preprocess import DevicePolygonMasks
     r = object.__new__(DevicePolygonMasks)
     r._set_capacities(**caps)
-    r.blob = r.desc = r.polys = r.verts = r._host = r._host_np = _Untouchable()
-    r._event = r.last = r._dense = None
+    r.blob = r.desc = r.polys = r.verts = r._stage = _Untouchable()
+    r.last = r._dense = None
     r._end = 0
     return r
 

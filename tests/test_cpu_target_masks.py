@@ -222,26 +222,24 @@ def test_capacity_overruns_raise_and_layout_is_consistent():
 def test_static_targets_take_mask_sizes_instead_of_masks():
     """StaticTargets.pack on host buffers only: "mask_size" targets feed valid_hw as the masks' shapes do and stage no mask bytes."""
     from toist_amd.matcher import StaticTargets
-    st = StaticTargets.__new__(StaticTargets)
-    st.B, st.max_per_image, st.Q, st.K, st.mask_hw, st.mask_pred_of, st.cap = 2, 3, 10, 8, (64, 96), (lambda side: (side + 3) // 4), 6
+    st = StaticTargets(2, 3, 10, 8, device="cpu", mask_hw=(64, 96))       # (a host-only instance: ordinary buffers, no GPU runtime)
     views, total = StaticTargets.arena_views(2, 6, 8)
-    st._host = torch.zeros(total, dtype=torch.uint8)
-    st._views = views
-    st._mask_host = torch.zeros(6, 64, 96, dtype=torch.uint8)
+    own = st._stage.open()
+    assert own.numel() == total and tuple(st._mask_host.shape) == (6, 64, 96)
     boxes = lambda n: torch.rand(n, 4)
     by_masks = [{"boxes": boxes(2), "masks": torch.ones(2, 40, 90, dtype=torch.bool)}, {"boxes": boxes(0), "masks": torch.ones(0, 60, 50, dtype=torch.bool)}]
     by_size = [{"boxes": by_masks[0]["boxes"], "mask_size": (40, 90)}, {"boxes": boxes(0), "mask_size": (60, 50)}]
     pm = torch.rand(2, 8)
-    host_a, sizes_a, mh = st.pack(by_masks, pm, out=st._host)
+    host_a, sizes_a, mh = st.pack(by_masks, pm, out=own)
     valid_a = views(host_a)[6].clone()
     host_b, sizes_b, none = st.pack(by_size, pm, out=torch.zeros(total, dtype=torch.uint8))
     assert none is None and mh is not None and sizes_a == sizes_b == [2, 0]
     assert valid_a.tolist() == views(host_b)[6].tolist() == [60, 90, 15, 23]
     assert torch.equal(host_a, host_b)
     with pytest.raises(ValueError, match="mask_size"):
-        st.pack([by_masks[0], by_size[1]], pm, out=st._host)
+        st.pack([by_masks[0], by_size[1]], pm, out=own)
     with pytest.raises(ValueError, match="mask_size of 65 x 90"):
-        st.pack([{"boxes": by_masks[0]["boxes"], "mask_size": (65, 90)}, by_size[1]], pm, out=st._host)
+        st.pack([{"boxes": by_masks[0]["boxes"], "mask_size": (65, 90)}, by_size[1]], pm, out=own)
 
 
 def test_entry_point_checks_its_arguments_without_a_gpu():

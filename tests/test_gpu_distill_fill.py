@@ -170,7 +170,7 @@ def test_kmeans_start_mismatch_sets_the_status_bit(dev):
     assert status == 1
     assert pick.tolist() == want_p and torch.allclose(cc.cluster_centers, want_c, rtol=1e-4, atol=1e-5)
     # the host raises at the deferred check, then the word is clear again
-    cc.__dict__["_kmeans_status"], cc.__dict__["_kmeans_pending"] = torch.ones(1, dtype=torch.int32, device=dev), []
+    cc._start_status(torch.device(dev)).fill_(1)
     with pytest.raises(RuntimeError, match="sync_host_state"):
         cc.check_start_status(defer=False)
     cc.check_start_status(defer=False)
@@ -178,7 +178,7 @@ def test_kmeans_start_mismatch_sets_the_status_bit(dev):
 
 # ---- the reference's own fill sequence through the kernels ------------------------------------------------------------------------------------------
 def _load_groups(tb, tasks):
-    host = torch.zeros(tb._host.numel(), dtype=torch.uint8)
+    host = torch.zeros(tb.nbytes, dtype=torch.uint8)
     v = [x.numpy() for x in tb._views(host)]
     tb._pack_groups([int(t) for t in tasks], v[4], v[5], v[6], v[7])
     tb.load_packed(host)

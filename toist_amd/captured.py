@@ -5,7 +5,7 @@ from collections import OrderedDict
 
 import torch
 
-from . import kernels
+from . import kernels, staging
 from .misc import NestedTensor
 from .transformer import TokenizedText
 
@@ -45,6 +45,23 @@ def upload(ent, samples, tokenized):
         att.zero_()
     ids[:, :L].copy_(tokenized["input_ids"], non_blocking=True)
     att[:, :L].copy_(tokenized["attention_mask"], non_blocking=True)
+
+
+def row_results(out, rows, live, num_queries, device):
+    """PostProcess's dict for each of the first `live` of the `rows` rows of kernels.postprocess's output `out`: views into it, and into the cached
+    all-ones labels tensor of that shape."""
+    from .postprocessors import PostProcess
+    lkey = (str(device), rows, num_queries)
+    labels = PostProcess._LABELS.get(lkey)
+    if labels is None:
+        labels = PostProcess._LABELS[lkey] = torch.ones(rows, num_queries, dtype=torch.int64, device=device)
+    results = []
+    for i in range(live):
+        r = {"scores": out["scores"][i], "labels": labels[i], "boxes": out["boxes"][i]}
+        if "scores_refexp" in out:
+            r["scores_refexp"] = out["scores_refexp"][i]
+        results.append(r)
+    return results
 
 
 class _CapturedStep:
@@ -334,8 +351,8 @@ class CapturedEvalStep(_CapturedStep):
         dev, B = self.device, self.batch
         ent = {**static_inputs(B, Hp, Wp, Lp, _pad_id(self.model), dev), **_NO_GRAPH,
                # rows 0 .. 2B: (h, w) originals for toist_postprocess; rows 2B .. 6B: (crop_h, crop_w, h, w) for toist_mask_resize_pack_batch
-               "sizes_host": torch.ones(6 * B, dtype=torch.int64).pin_memory(), "sizes": torch.ones(6 * B, dtype=torch.int64, device=dev),
-               "sizes_event": None, "out": None, "tables": None,
+               "sizes_stage": staging.Staging(torch.ones(6 * B, dtype=torch.int64), dev), "sizes": torch.ones(6 * B, dtype=torch.int64, device=dev),
+               "out": None, "tables": None,
                "bits": torch.zeros(B * self.capacity_words, dtype=torch.int64, device=dev) if self.masks else None}
         if self.cluster_criterion is not None:
             from .distill import DistillTables
@@ -345,21 +362,12 @@ class CapturedEvalStep(_CapturedStep):
     def _fill(self, ent, samples, tokenized, orig, crop, dataset_names, captions):
         B = self.batch
         upload(ent, samples, tokenized)
-        if ent["sizes_event"] is not None:
-            ent["sizes_event"].synchronize()           # the previous upload has left the staging buffer
-        host = ent["sizes_host"]
+        host = ent["sizes_stage"].open()
         host[:2 * B] = torch.tensor(orig, dtype=torch.int64).view(-1)
         host[2 * B:] = torch.tensor([c + o for c, o in zip(crop, orig)], dtype=torch.int64).view(-1)
-        ent["sizes"].copy_(host, non_blocking=True)
-        ent["sizes_event"] = torch.cuda.Event()
-        ent["sizes_event"].record()
+        ent["sizes_stage"].upload((ent["sizes"], host))
         if ent["tables"] is not None:
-            tb = ent["tables"]
-            if tb._event is not None:
-                tb._event.synchronize()
-            tb.load_packed(tb.pack_eval(tokenized, captions, dataset_names, out=tb._host))
-            tb._event = torch.cuda.Event()
-            tb._event.record()
+            ent["tables"].load_eval(tokenized, captions, dataset_names)
 
     def _forward(self, ent, key):
         """The launches of one batch on the bucket's static inputs (eagerly, and once more under capture)."""
@@ -379,25 +387,16 @@ class CapturedEvalStep(_CapturedStep):
                                            self.threshold)
 
     def _results(self, ent, orig):
-        from .postprocessors import PostProcess
-        out, B, Q = ent["out"], self.batch, self.num_queries
-        lkey = (str(self.device), B, Q)
-        labels = PostProcess._LABELS.get(lkey)
-        if labels is None:
-            labels = PostProcess._LABELS[lkey] = torch.ones(B, Q, dtype=torch.int64, device=self.device)
-        results = []
-        for i, (h, w) in enumerate(orig):
-            r = {"scores": out["scores"][i], "labels": labels[i], "boxes": out["boxes"][i]}
-            if "scores_refexp" in out:
-                r["scores_refexp"] = out["scores_refexp"][i]
-            if self.masks:
+        Q = self.num_queries
+        results = row_results(ent["out"], self.batch, self.batch, Q, self.device)
+        if self.masks:
+            for i, (r, (h, w)) in enumerate(zip(results, orig)):
                 words = kernels.mask_words(h)
                 bits = ent["bits"][i * self.capacity_words:i * self.capacity_words + Q * w * words].view(Q, w, words)
                 if self.dense_masks:
                     r["masks"] = kernels.mask_unpack(bits, h, w).unsqueeze(1).cpu()
                 else:
                     r["mask_bits"], r["mask_size"] = bits, (h, w)
-            results.append(r)
         return results
 
     # -- the step -------------------------------------------------------------------------------------------------------------------
@@ -464,6 +463,7 @@ class CapturedSweepStep(_CapturedStep):
         self.pad_hw, self.pad_tokens, self.max_graphs = int(pad_hw), int(pad_tokens), int(max_graphs)
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
         self.num_queries = model.query_embed.weight.shape[0]
+        self._host_views, self._host_bytes = staging.typed_views([(torch.int32, (2 * self.pairs,)), (torch.int64, (self.pairs, 2))])
         self._init_capture_state()
 
     def _static_inputs(self, key):
@@ -473,9 +473,8 @@ class CapturedSweepStep(_CapturedStep):
         ent = {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, dev), **_NO_GRAPH,
                "pair_image": torch.zeros(P, dtype=torch.int32, device=dev), "pair_caption": torch.zeros(P, dtype=torch.int32, device=dev),
                "sizes": torch.ones(P, 2, dtype=torch.int64, device=dev),
-               # staging: rows 0 .. P = pair_image, P .. 2P = pair_caption (int32); the sizes (int64)
-               "tables_host": torch.zeros(2 * P, dtype=torch.int32).pin_memory(), "sizes_host": torch.ones(P, 2, dtype=torch.int64).pin_memory(),
-               "tables_event": None, "uploaded": None, "out": None}
+               # staging: rows 0 .. P = pair_image, P .. 2P = pair_caption (int32); behind them the sizes (int64): three copies under one fence
+               "stage": staging.Staging(torch.zeros(self._host_bytes, dtype=torch.uint8), dev), "uploaded": None, "out": None}
         ent["tok"] = static_inputs(self.captions, 1, 1, Lp, pad_id, dev)["tok"]              # the text inputs hold the CAPTIONS, not one row per image
         return ent
 
@@ -485,16 +484,11 @@ class CapturedSweepStep(_CapturedStep):
         if ent["uploaded"] == tables:
             return
         P = self.pairs
-        if ent["tables_event"] is not None:
-            ent["tables_event"].synchronize()          # the previous upload has left the staging buffers
-        ent["tables_host"][:P] = pi
-        ent["tables_host"][P:] = pc
-        ent["sizes_host"].copy_(torch.tensor(sizes, dtype=torch.int64))
-        ent["pair_image"].copy_(ent["tables_host"][:P], non_blocking=True)
-        ent["pair_caption"].copy_(ent["tables_host"][P:], non_blocking=True)
-        ent["sizes"].copy_(ent["sizes_host"], non_blocking=True)
-        ent["tables_event"] = torch.cuda.Event()
-        ent["tables_event"].record()
+        tables_host, sizes_host = self._host_views(ent["stage"].open())
+        tables_host[:P] = pi
+        tables_host[P:] = pc
+        sizes_host.copy_(torch.tensor(sizes, dtype=torch.int64))
+        ent["stage"].upload((ent["pair_image"], tables_host[:P]), (ent["pair_caption"], tables_host[P:]), (ent["sizes"], sizes_host))
         ent["uploaded"] = tables
 
     def _forward(self, ent):
@@ -505,19 +499,7 @@ class CapturedSweepStep(_CapturedStep):
         ent["out"] = kernels.postprocess(outputs["pred_logits"], outputs["pred_boxes"], ent["sizes"], outputs.get("pred_isfinal"), out=ent["out"])
 
     def _results(self, ent, live):
-        from .postprocessors import PostProcess
-        out, P, Q = ent["out"], self.pairs, self.num_queries
-        lkey = (str(self.device), P, Q)
-        labels = PostProcess._LABELS.get(lkey)
-        if labels is None:
-            labels = PostProcess._LABELS[lkey] = torch.ones(P, Q, dtype=torch.int64, device=self.device)
-        results = []
-        for p in range(live):
-            r = {"scores": out["scores"][p], "labels": labels[p], "boxes": out["boxes"][p]}
-            if "scores_refexp" in out:
-                r["scores_refexp"] = out["scores_refexp"][p]
-            results.append(r)
-        return results
+        return row_results(ent["out"], self.pairs, live, self.num_queries, self.device)
 
     def _handed_out(self, ent):
         """Read the assemble launch's status word where the results are handed out (it synchronises): a refused table entry raises ValueError."""

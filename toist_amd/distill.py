@@ -8,13 +8,13 @@ is a handful of device tensor ops per iteration ([1024, 256] bank, 3 centres), a
 Buffer names and shapes equal the reference's, so a reference checkpoint of the criterion loads unchanged.
 """
 import collections
-import copy
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import staging
 from .matcher import linear_sum_assignment_batch
 
 
@@ -185,29 +185,16 @@ class DistillTables:
     def __init__(self, batch, tokens, device, pronoun_side):
         self.B, self.L, self.pronoun_side = int(batch), int(tokens), bool(pronoun_side)
         self.device = torch.device(device)
-        B, L = self.B, self.L
-        sizes = [B * L * 4, B * L * 4, L * B, L * B, B * 4, B * 4, (B + 1) * 4, B * 4]
-        offs, total = [], 0
-        for n in sizes:
-            offs.append(total)
-            total += (n + 15) // 16 * 16
+        B, L = self.B, self.L                                    # nbytes: the size of the arena = of a pack()ed host image
+        self._views, self.nbytes = staging.typed_views([(torch.float32, (B, L)), (torch.float32, (B, L)), (torch.uint8, (L, B)), (torch.uint8, (L, B)),
+                                                        (torch.int32, (B,)), (torch.int32, (B,)), (torch.int32, (B + 1,)), (torch.int32, (B,))])
         self._pin = self.device.type == "cuda"                   # (a host-only instance packs tables in the CPU tests)
-        self._host = torch.zeros(total, dtype=torch.uint8)
-        if self._pin:
-            self._host = self._host.pin_memory()
-        self._dev = torch.zeros(total, dtype=torch.uint8, device=self.device)
-
-        def views(buf):
-            cut = lambda i, dt, shape: buf[offs[i]:offs[i] + sizes[i]].view(dt).view(shape)
-            return (cut(0, torch.float32, (B, L)), cut(1, torch.float32, (B, L)), cut(2, torch.uint8, (L, B)), cut(3, torch.uint8, (L, B)), cut(4, torch.int32, (B,)),
-                    cut(5, torch.int32, (B,)), cut(6, torch.int32, (B + 1,)), cut(7, torch.int32, (B,)))
-
-        self._views = views
-        self.W_span, self.W_sth, self.sub_span, self.sub_sth, self.task, self.group_task, self.group_off, self.members = views(self._dev)
-        self._event = None
+        self._stage = staging.Staging(torch.zeros(self.nbytes, dtype=torch.uint8), self.device)
+        self._dev = torch.zeros(self.nbytes, dtype=torch.uint8, device=self.device)
+        self.W_span, self.W_sth, self.sub_span, self.sub_sth, self.task, self.group_task, self.group_off, self.members = self._views(self._dev)
 
     def _staging(self, out):
-        host = out if out is not None else torch.zeros(self._host.numel(), dtype=torch.uint8)
+        host = out if out is not None else torch.zeros(self.nbytes, dtype=torch.uint8)
         if out is None and self._pin:
             host = host.pin_memory()
         host.zero_()
@@ -256,11 +243,12 @@ class DistillTables:
         return self
 
     def load(self, tokenized, targets, captions=None):
-        if self._event is not None:
-            self._event.synchronize()          # the previous upload has left the staging buffer
-        self.load_packed(self.pack(tokenized, targets, captions, out=self._host))
-        self._event = torch.cuda.Event()
-        self._event.record()
+        self._stage.upload((self._dev, self.pack(tokenized, targets, captions, out=self._stage.open())))
+        return self
+
+    def load_eval(self, tokenized, captions, dataset_names):
+        """pack_eval() into the internal staging buffer + the copy."""
+        self._stage.upload((self._dev, self.pack_eval(tokenized, captions, dataset_names, out=self._stage.open())))
         return self
 
 
@@ -277,11 +265,8 @@ class FillTables:
         if self.B > int(memory_size):
             raise ValueError(f"a batch of {self.B} images does not fit a memory bank of {int(memory_size)} rows")
         self.device = torch.device(device)
-        self._host = torch.full((2, self.B, self.K), -1, dtype=torch.int32)
-        if self.device.type == "cuda":
-            self._host = self._host.pin_memory()
+        self._stage = staging.Staging(torch.full((2, self.B, self.K), -1, dtype=torch.int32), self.device)
         self.init = torch.full((2, self.B, self.K), -1, dtype=torch.int32, device=self.device)
-        self._event = None
 
     def attach(self, noun_tables, sth_tables):
         noun_tables.init_rows, sth_tables.init_rows = self.init[0], self.init[1]
@@ -297,12 +282,7 @@ class FillTables:
         return host
 
     def load(self, init_noun, init_sth):
-        if self._event is not None:
-            self._event.synchronize()          # the previous upload has left the staging buffer
-        self.init.copy_(self.pack(init_noun, init_sth, out=self._host), non_blocking=True)
-        if self.device.type == "cuda":
-            self._event = torch.cuda.Event()
-            self._event.record()
+        self._stage.upload((self.init, self.pack(init_noun, init_sth, out=self._stage.open())))
         return self
 
 
@@ -348,6 +328,7 @@ class ClusterCriterion(nn.Module):
         self.register_buffer("cluster_centers", torch.randn(task_count, cluster_num, feature_dim))
         self.register_buffer("update_count", torch.zeros(task_count))
         self.register_buffer("full_label", torch.zeros(task_count))
+        self._start_mail = staging.Mailbox()          # toist_kmeans_init's status word and its copies on their way to the host (check_start_status)
 
     @staticmethod
     def _world():
@@ -516,42 +497,28 @@ class ClusterCriterion(nn.Module):
             out.append(init)
         return out[0], out[1]
 
-    def __deepcopy__(self, memo):
-        """(the status word and its pinned copies in flight belong to this object's launches: a copy starts without them)"""
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        for key, val in self.__dict__.items():
-            if key not in ("_kmeans_status", "_kmeans_pending"):
-                new.__dict__[key] = copy.deepcopy(val, memo)
-        return new
-
     def _start_status(self, device):
-        """the sticky i32 status word of toist_kmeans_init on `device` (allocated on first use: before any capture, in the eager pass)"""
-        st = self.__dict__.get("_kmeans_status")
-        if st is None or st.device != device:
-            st = self.__dict__["_kmeans_status"] = torch.zeros(1, dtype=torch.int32, device=device)
-            self.__dict__["_kmeans_pending"] = []
-        return st
+        """the sticky i32 status word of toist_kmeans_init on `device` (allocated on first use: before any capture, in the eager pass).  It lives in
+        the mailbox its copies travel through: a deep copy of the criterion starts without either."""
+        mail = self._start_mail
+        if mail.word is None or mail.word.device != device:
+            mail.clear()
+            mail.word = torch.zeros(1, dtype=torch.int32, device=device)
+        return mail.word
 
     def check_start_status(self, defer=True):
         """Raise when a toist_kmeans_init launch found the device's full_label and the host's plan (plan_fill) in disagreement -- the buffers were written
         without sync_host_state().  defer=True: the design of matcher.check_lsap_status(defer=True) -- the word is copied to pinned memory behind an
         event and the copies of EARLIER calls that have arrived are looked at, so no step waits for the device; defer=False waits."""
-        st = self.__dict__.get("_kmeans_status")
+        mail = self._start_mail
+        st = mail.word
         if st is None or torch.cuda.is_current_stream_capturing():
             return
-        pending = self.__dict__["_kmeans_pending"]
-        host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-        host.copy_(st, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        pending.append((host, ev))
-        while pending and (not defer or pending[0][1].query()):
-            host, ev = pending.pop(0)
-            ev.synchronize()
+        mail.post(st)
+        for host in mail.drain(wait=not defer):
             if int(host[0]) != 0:
                 st.zero_()
-                pending.clear()
+                mail.clear()
                 raise RuntimeError("ClusterCriterion: the device's full_label and the host's plan of the k-means start disagreed in a captured step (the "
                                    "launch fell back to the stored centres); call sync_host_state() after writing update_count / full_label directly")
 

@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from . import kernels as k
+from . import staging
 
 TOKEN_MASK_WORDS = 4      # 64-bit words of a target's token-span mask: 256 tokens = the reference's max_text_len (csrc/contrastive.hip: CA_MW)
 
@@ -80,45 +81,39 @@ class StaticTargets:
     maps have the size of the ResNet C2 feature: ceil(side / 4), `mask_pred_of`); the mask losses map that corner of the bucket's prediction onto that corner of the bucket's targets and
     normalise by VH * VW, so a batch gives the same mask losses in any bucket."""
 
+    _tail_bytes = 0           # bytes a subclass keeps behind the seven segments, in the same arena (LiveStaticTargets)
+
     def __init__(self, batch, max_per_image, num_queries, K=256, device="cuda", mask_hw=None, mask_pred_of=lambda side: (side + 3) // 4):
         self.B, self.max_per_image, self.Q, self.K = batch, max_per_image, num_queries, K
         # mask_hw = (TH, TW): the ground-truth masks of the targets travel too (uint8 [cap, TH, TW], zero-padded to the padded batch size like
         # NestedTensor.from_tensor_list, util/misc.py:185-209) -- the mask losses of configs[2] then replay from the same graph as the detection losses
         self.mask_hw = None if mask_hw is None else (int(mask_hw[0]), int(mask_hw[1]))
         self.mask_pred_of = mask_pred_of          # image side -> side of pred_masks (the mask head resizes to each FPN level and ends at C2's size: segmentation.py:223-240)
-        self.masks = self._mask_host = None
-        if self.mask_hw is not None:
-            self.masks = torch.zeros(batch * max_per_image, *self.mask_hw, dtype=torch.uint8, device=device)
-            self._mask_host = torch.zeros(batch * max_per_image, *self.mask_hw, dtype=torch.uint8).pin_memory()
         self.cap = cap = batch * max_per_image
         self.device = torch.device(device)
-        self._views, total = self.arena_views(batch, cap, K)
-        self._host = torch.zeros(total, dtype=torch.uint8).pin_memory()
+        self._views, self._tail_off = self.arena_views(batch, cap, K)
+        total = self._tail_off + self._tail_bytes
+        self._stage = staging.Staging(torch.zeros(total, dtype=torch.uint8), self.device)          # load()'s host image, and the fence of its upload
         self._dev = torch.zeros(total, dtype=torch.uint8, device=self.device)
+        self.masks = self._mask_host = None
+        if self.mask_hw is not None:
+            self.masks = torch.zeros(cap, *self.mask_hw, dtype=torch.uint8, device=device)
+            self._mask_host = torch.zeros(cap, *self.mask_hw, dtype=torch.uint8)                  # travels behind the arena, under its fence
+            if self._stage.pinned:
+                self._mask_host = self._mask_host.pin_memory()
         self.boxes, self.positive_map, self.tok_mask, self.tgt_off, self.match_off, self._nb_local, self.valid_hw = self._views(self._dev)
         if self.mask_hw is None:
             self.valid_hw = None
         self.num_boxes = torch.ones(1, dtype=torch.float32, device=self.device)
         self.sizes = [0] * batch
         self._out = {}        # L -> (src [L, cap], tgt [L, cap], status [L*B])
-        self._event = None
         self.distill = None   # distill.DistillTables of this side of a (noun, pronoun) pair: the captured distillation step (harness.CapturedDistillStep)
 
     @staticmethod
     def arena_views(batch, cap, K):
         """The arena layout (class docstring) as host code: -> (views(buf) = the seven typed views of a uint8 buffer of `total` bytes, total)."""
-        sizes = [cap * 4 * 4, cap * K * 4, cap * TOKEN_MASK_WORDS * 8, (batch + 1) * 4, (batch + 1) * 4, 4, 16]
-        offs, total = [], 0
-        for n in sizes:
-            offs.append(total)
-            total += (n + 15) // 16 * 16
-
-        def views(buf):
-            cut = lambda i, dt, shape: buf[offs[i]:offs[i] + sizes[i]].view(dt).view(shape)
-            return (cut(0, torch.float32, (cap, 4)), cut(1, torch.float32, (cap, K)), cut(2, torch.int64, (cap, TOKEN_MASK_WORDS)), cut(3, torch.int32, (batch + 1,)),
-                    cut(4, torch.int32, (batch + 1,)), cut(5, torch.float32, (1,)), cut(6, torch.int32, (4,)))
-
-        return views, total
+        return staging.typed_views([(torch.float32, (cap, 4)), (torch.float32, (cap, K)), (torch.int64, (cap, TOKEN_MASK_WORDS)), (torch.int32, (batch + 1,)),
+                                    (torch.int32, (batch + 1,)), (torch.float32, (1,)), (torch.int32, (4,))])
 
     def pack(self, targets, positive_map, token_masks=None, out=None):
         """Host image of one batch (pinned uint8 tensor in the arena layout, + the per-image target counts): build it ahead of time -- in a
@@ -130,7 +125,7 @@ class StaticTargets:
         sizes = [int(t["boxes"].shape[0]) for t in targets]
         if len(sizes) != self.B or max(sizes, default=0) > self.max_per_image:
             raise ValueError(f"StaticTargets holds {self.B} images x <= {self.max_per_image} targets; got sizes {sizes}")
-        host = out if out is not None else torch.zeros(self._host.numel(), dtype=torch.uint8).pin_memory()
+        host = out if out is not None else torch.zeros(self._tail_off + self._tail_bytes, dtype=torch.uint8).pin_memory()
         hb, hp, hm, hto, hmo, hnb, hvalid = self._views(host)
         tot = sum(sizes)
         if tot:
@@ -195,14 +190,10 @@ class StaticTargets:
             torch.clamp(self._nb_local, min=1, out=self.num_boxes)
         return self
 
-    def load(self, targets, positive_map, token_masks=None):
-        """pack() into the internal staging buffer + load_packed()."""
-        if self._event is not None:
-            self._event.synchronize()          # the previous upload has left the staging buffer
-        packed = self.pack(targets, positive_map, token_masks, out=self._host)
-        self.load_packed(packed)
-        self._event = torch.cuda.Event()
-        self._event.record()
+    def load(self, targets, positive_map, token_masks=None, **pack_kw):
+        """pack() into the internal staging buffer + load_packed().  pack_kw: a subclass's further keywords of pack()."""
+        self.load_packed(self.pack(targets, positive_map, token_masks, out=self._stage.open(), **pack_kw))
+        self._stage.fence()
         return self
 
     def outputs(self, L):
@@ -227,14 +218,11 @@ class LiveStaticTargets(StaticTargets):
     one more 16-byte segment BEHIND the arena of StaticTargets, whose seven views keep their offsets; pack(..., live_tokens=L) writes it and
     load_packed() carries it in the same single copy.  SetCriterion finds it as `tok_mask.live_tokens`."""
 
+    _tail_bytes = 16
+
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        self._live_off = self._host.numel()
-        self._host = torch.zeros(self._live_off + 16, dtype=torch.uint8).pin_memory()
-        self._dev = torch.zeros(self._live_off + 16, dtype=torch.uint8, device=self.device)
-        self.boxes, self.positive_map, self.tok_mask, self.tgt_off, self.match_off, self._nb_local, valid_hw = self._views(self._dev)
-        if self.mask_hw is not None:
-            self.valid_hw = valid_hw
+        self._live_off = self._tail_off           # the word's byte offset: the trailing segment of the arena
         self.live_tokens = self._live_word(self._dev)
         self.tok_mask.live_tokens = self.live_tokens
 
@@ -248,15 +236,6 @@ class LiveStaticTargets(StaticTargets):
         packed = super().pack(targets, positive_map, token_masks, out=out)
         self._live_word(packed[0])[0] = int(live_tokens)
         return packed
-
-    def load(self, targets, positive_map, token_masks=None, live_tokens=None):
-        """pack() into the internal staging buffer + load_packed()."""
-        if self._event is not None:
-            self._event.synchronize()          # the previous upload has left the staging buffer
-        self.load_packed(self.pack(targets, positive_map, token_masks, out=self._host, live_tokens=live_tokens))
-        self._event = torch.cuda.Event()
-        self._event.record()
-        return self
 
 
 class HungarianMatcher(nn.Module):
@@ -339,7 +318,7 @@ def _lsap_meta(shapes, offsets, dev):
     return ent
 
 
-_LSAP_PENDING = []      # (pinned host copy of a status vector, event recorded behind the copy)
+_LSAP_MAIL = staging.Mailbox()      # the status vectors of deferred checks on their way to the host
 
 
 def _raise_on(st):
@@ -360,25 +339,12 @@ def check_lsap_status(status, defer=False):
     if torch.cuda.is_current_stream_capturing():      # (an event recorded on this stream before the capture may not even be queried now)
         return
     check_lsap_pending(wait=False)
-    host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record()
-    _LSAP_PENDING.append((host, ev))
+    _LSAP_MAIL.post(status)
 
 
 def check_lsap_pending(wait=True):
-    keep = []
-    try:
-        while _LSAP_PENDING:
-            host, ev = _LSAP_PENDING.pop(0)
-            if not wait and not ev.query():
-                keep.append((host, ev))
-                continue
-            ev.synchronize()
-            _raise_on(host)
-    finally:
-        _LSAP_PENDING[:0] = keep
+    for host in _LSAP_MAIL.drain(wait):     # (a raise leaves the copies behind this one queued)
+        _raise_on(host)
 
 
 def lsap_blocks(cost, shapes, offsets, ld):

@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import dist, engine, functions, matcher
+from . import dist, engine, functions, matcher, staging
 from . import kernels as k
 from .backbone import build_backbone, nearest_mask
 from .matcher import StaticTargets, build_matcher, pair_slots
@@ -425,7 +425,7 @@ class SetCriterion(nn.Module):
         self.last_match = None
         self._nb, self._nb_reduced = {}, {}
         self._tokmask = None       # (member mask tensors, concatenated [sum T, 4] int64): spans of the last batch, uploaded once
-        self._pending_status = []  # (pinned host copy, event) of matcher status words not yet looked at
+        self._status_mail = staging.Mailbox()  # matcher status words not yet looked at
 
     # -- helpers ------------------------------------------------------------------------------------------
     def _num_boxes(self, targets, device):
@@ -472,31 +472,18 @@ class SetCriterion(nn.Module):
         """The losses of a layer whose cost block was invalid are NaN already (criterion kernel); additionally stage the status
         words in pinned host memory without waiting, so the NEXT call (or check_status()) can raise the reference's
         ValueError -- no host sync on the step's critical path."""
-        st = match.status
-        if not st.is_cuda or torch.cuda.is_current_stream_capturing():
-            return
-        host = torch.empty(st.shape, dtype=st.dtype, pin_memory=True)
-        host.copy_(st, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._pending_status.append((host, ev))
+        self._status_mail.post(match.status)
 
     def check_status(self, wait=True):
         """Raise ValueError (as scipy.optimize.linear_sum_assignment does inside the reference matcher) if a cost block of an
-        earlier call held NaN / -inf.  wait=False only looks at copies that have already arrived."""
-        keep = []
-        for host, ev in self._pending_status:
-            if not wait and not ev.query():
-                keep.append((host, ev))
-                continue
-            ev.synchronize()
+        earlier call held NaN / -inf.  wait=False only looks at copies that have already arrived.  A raise drops every copy still queued."""
+        for host in self._status_mail.drain(wait):
             if bool((host == 1).any()):
-                self._pending_status = []
+                self._status_mail.clear()
                 raise ValueError("matrix contains invalid numeric entries")
             if bool((host == 2).any()):
-                self._pending_status = []
+                self._status_mail.clear()
                 raise ValueError("cost matrix is infeasible")
-        self._pending_status = keep
 
     def token_masks_host(self, targets, tokenized):
         """int64 [sum T, TOKEN_MASK_WORDS] host tensor of the targets' token-span bit masks (input of StaticTargets.load)."""
@@ -593,7 +580,7 @@ class SetCriterion(nn.Module):
         return losses
 
     def forward(self, memory_cache, outputs, targets, positive_map, example_rel=None):
-        if self._pending_status and not torch.cuda.is_current_stream_capturing():
+        if len(self._status_mail) and not torch.cuda.is_current_stream_capturing():
             self.check_status(wait=False)   # an invalid cost block of an earlier call raises here, like SciPy inside the reference matcher
         if isinstance(outputs, list):
             if isinstance(targets[0], StaticTargets):

@@ -23,7 +23,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, staging
 from .box_ops import box_xyxy_to_cxcywh
 from .misc import NestedTensor, interpolate
 
@@ -410,9 +410,7 @@ class DevicePreprocessor:
         self.mid = self.blob[self._head_bytes:]
         self.lut = normalisation_table().to(self.device)
         self.out = NestedTensor(torch.zeros(B, 3, *self.cap_hw, device=self.device), torch.ones(B, *self.cap_hw, dtype=torch.bool, device=self.device))
-        self._host = torch.zeros(self._head_bytes, dtype=torch.uint8).pin_memory()
-        self._host_np = self._host.numpy()
-        self._event = None
+        self._stage = staging.Staging(torch.zeros(self._head_bytes, dtype=torch.uint8), self.device)
         self._last = None
 
     # -- host side ----------------------------------------------------------------------------------------------------------------------
@@ -492,9 +490,7 @@ class DevicePreprocessor:
         stream (the previous copy out of the pinned buffer is waited for first).  -> PackedBatch."""
         packed, rows, tables, pixels, used = _layout if _layout is not None else self._layout(images, plans, _u8)
         assert used <= self._head_bytes
-        if self._event is not None:
-            self._event.synchronize()
-        host = self._host_np
+        host = self._stage.open_np()
         desc = host[:self._desc_bytes].view(np.int32).reshape(2, self.max_batch, _lib.PREP_DESC_WORDS)
         desc[:] = 0                                             # unused slots: out_h = 0 = an empty image (padding only)
         for s in (0, 1):
@@ -507,9 +503,7 @@ class DevicePreprocessor:
             words[at + bounds.size:at + bounds.size + coef.size] = coef.reshape(-1)
         for at, a in pixels:
             host[at:at + a.size].reshape(a.shape)[...] = a
-        self.blob[:used].copy_(self._host[:used], non_blocking=True)
-        self._event = torch.cuda.Event()
-        self._event.record()
+        self._stage.upload_head(self.blob, used)
         self._last = packed
         return packed
 
@@ -604,10 +598,8 @@ class DeviceTargetMasks:
         self.blob = torch.zeros(self._blob_bytes, dtype=torch.uint8, device=self.device)
         self.desc = self.blob[:self._desc_bytes].view(torch.int32).view(self.max_slots, _lib.TMASK_DESC_WORDS)
         self.arena = self.blob.view(torch.int32)              # table offsets are int32 words from the blob's start
-        self._host = torch.zeros(self._blob_bytes, dtype=torch.uint8).pin_memory()
-        self._host_np = self._host.numpy()
+        self._stage = staging.Staging(torch.zeros(self._blob_bytes, dtype=torch.uint8), self.device)
         self._dense = None                                    # uint8 [max_slots, *max_out_hw], on the first dense()
-        self._event = None
         self.last = None                                      # the PackedTargetMasks of the last pack()
 
     def _set_capacities(self, max_batch, max_targets_per_image, max_src_pixels, max_out_hw, max_table_words=None):
@@ -624,6 +616,26 @@ class DeviceTargetMasks:
             raise ValueError("DeviceTargetMasks: at most 65535 slots, and the blob is addressed with 31 bits")
 
     # -- host side ----------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _selected(rows, n, what):
+        """One image's "mask_rows" as int64 indices into its n masks / segmentations; ValueError when one points outside."""
+        rows = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows, dtype=np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= n):
+            raise ValueError(f"DeviceTargetMasks: mask rows {rows.tolist()} of an image with {n} {what}")
+        return rows
+
+    def _write_head(self, rows, tables):
+        """The descriptors of the live slots and the index tables into the pinned image, once its previous upload has left it -> its numpy view."""
+        host = self._stage.open_np()
+        desc = host[:self._desc_bytes].view(np.int32).reshape(self.max_slots, _lib.TMASK_DESC_WORDS)
+        desc[:] = 0                                             # slots behind the batch's targets: out_h = 0 = dead, not written
+        for i, r in enumerate(rows):
+            desc[i] = [r[name] for name in TMASK_DESC_FIELDS]
+        words = host.view(np.int32)
+        for at, table in tables:
+            words[at:at + table.size] = table
+        return host
+
     def _layout(self, masks_per_image, plans, rows_per_image=None):
         """Host check + placement of a batch: -> (PackedTargetMasks, descriptor dicts of the live slots, [(word, table)], [(byte, source masks)], used
         bytes).  Raises ValueError on any capacity overrun; touches no buffer."""
@@ -639,10 +651,7 @@ class DeviceTargetMasks:
             if a.shape[0] and a.shape[1:] != (p.height, p.width):
                 raise ValueError(f"DeviceTargetMasks: {a.shape[1]} x {a.shape[2]} masks with a plan for {p.height} x {p.width}")
             if rows_per_image is not None:
-                rows = np.asarray(rows_per_image[i].cpu() if torch.is_tensor(rows_per_image[i]) else rows_per_image[i], dtype=np.int64).reshape(-1)
-                if rows.size and (rows.min() < 0 or rows.max() >= a.shape[0]):
-                    raise ValueError(f"DeviceTargetMasks: mask rows {rows.tolist()} of an image with {a.shape[0]} masks")
-                a = a[rows]
+                a = a[self._selected(rows_per_image[i], a.shape[0], "masks")]
             if a.shape[0] > self.max_targets_per_image:
                 raise ValueError(f"DeviceTargetMasks: {a.shape[0]} targets of one image exceed max_targets_per_image = {self.max_targets_per_image}")
             if p.final[0] > self.max_out_hw[0] or p.final[1] > self.max_out_hw[1]:
@@ -683,22 +692,11 @@ class DeviceTargetMasks:
         current stream (the previous copy out of the pinned image is waited for first).  -> PackedTargetMasks."""
         packed, rows, tables, bits, used = self._layout(masks_per_image, plans, rows_per_image)
         assert used <= self._blob_bytes and packed.slots <= self.max_slots
-        if self._event is not None:
-            self._event.synchronize()
-        host = self._host_np
-        desc = host[:self._desc_bytes].view(np.int32).reshape(self.max_slots, _lib.TMASK_DESC_WORDS)
-        desc[:] = 0                                             # slots behind the batch's targets: out_h = 0 = dead, not written
-        for i, r in enumerate(rows):
-            desc[i] = [r[name] for name in TMASK_DESC_FIELDS]
-        words = host.view(np.int32)
-        for at, table in tables:
-            words[at:at + table.size] = table
+        host = self._write_head(rows, tables)
         for at, a in bits:
             b = _pack_bits(a)
             host[at:at + b.size] = b.reshape(-1)
-        self.blob[:used].copy_(self._host[:used], non_blocking=True)
-        self._event = torch.cuda.Event()
-        self._event.record()
+        self._stage.upload_head(self.blob, used)
         self.last = packed
         return packed
 
@@ -716,30 +714,16 @@ class DeviceTargetMasks:
         for i, (segs, p) in enumerate(zip(segmentations_per_image, plans)):
             segs = list(segs)
             if rows_per_image is not None:
-                rows = np.asarray(rows_per_image[i].cpu() if torch.is_tensor(rows_per_image[i]) else rows_per_image[i], dtype=np.int64).reshape(-1)
-                if rows.size and (rows.min() < 0 or rows.max() >= len(segs)):
-                    raise ValueError(f"DeviceTargetMasks: mask rows {rows.tolist()} of an image with {len(segs)} segmentations")
-                segs = [segs[r] for r in rows.tolist()]
+                segs = [segs[r] for r in self._selected(rows_per_image[i], len(segs), "segmentations").tolist()]
             objects.append(segs)
             shapes.append(np.broadcast_to(_NO_MASK, (len(segs), int(p.height), int(p.width))))          # pack()'s placement reads the shapes only
         packed, rows, tables, bits, used = self._layout(shapes, plans)
         assert used <= self._blob_bytes and packed.slots <= self.max_slots
         flat = [seg for segs in objects for seg in segs]
         layout = polygons._layout(flat, [(r["src_h"], r["src_w"]) for r in rows], [r["src_off"] for r in rows])
-        if self._event is not None:
-            self._event.synchronize()
-        host = self._host_np
-        desc = host[:self._desc_bytes].view(np.int32).reshape(self.max_slots, _lib.TMASK_DESC_WORDS)
-        desc[:] = 0
-        for i, r in enumerate(rows):
-            desc[i] = [r[name] for name in TMASK_DESC_FIELDS]
-        words = host.view(np.int32)
-        for at, table in tables:
-            words[at:at + table.size] = table
+        self._write_head(rows, tables)
         head = min((at for at, _ in bits), default=used)       # the descriptors and the tables: the bits behind them are written on the device
-        self.blob[:head].copy_(self._host[:head], non_blocking=True)
-        self._event = torch.cuda.Event()
-        self._event.record()
+        self._stage.upload_head(self.blob, head)
         placed = polygons.pack(flat, None, _layout=layout)
         polygons.rasterise(self.blob)
         self.last = PackedTargetMasks(packed.slots, packed.counts, packed.sizes, head + placed.link_bytes)
@@ -865,10 +849,8 @@ class DevicePolygonMasks:
         self.desc = words[:self._polys_at // 4].view(self.max_objects, _lib.POLY_DESC_WORDS)
         self.polys = words[self._polys_at // 4:self._verts_at // 4].view(self.max_polygons, 2)
         self.verts = words[self._verts_at // 4:].view(self.max_vertices, 2)
-        self._host = torch.zeros(self._blob_bytes, dtype=torch.uint8).pin_memory()
-        self._host_np = self._host.numpy()
+        self._stage = staging.Staging(torch.zeros(self._blob_bytes, dtype=torch.uint8), self.device)
         self._dense = None                                    # uint8 [max_objects, *max_hw], on the first dense()
-        self._event = None
         self.last = None                                      # the PackedPolygons of the last pack()
         self._end = 0                                         # where the packed rows end under the offsets the device holds
 
@@ -906,17 +888,13 @@ class DevicePolygonMasks:
         """The batch into the blob: descriptors, polygon records and grid vertices into the pinned image, then one asynchronous copy of its used head
         on the current stream (the previous copy out of the pinned image is waited for first).  -> PackedPolygons."""
         packed, verts, polys, desc = _layout if _layout is not None else self._layout(segmentations, sizes, offsets)
-        if self._event is not None:
-            self._event.synchronize()
-        host = self._host_np.view(np.int32)
+        host = self._stage.open_np().view(np.int32)
         table = host[:self._polys_at // 4].reshape(self.max_objects, _lib.POLY_DESC_WORDS)
         table[:] = 0                                            # slots behind the batch's objects: h = 0 = dead, not written
         table[:desc.shape[0]] = desc
         host[self._polys_at // 4:self._polys_at // 4 + polys.size] = polys.reshape(-1)
         host[self._verts_at // 4:self._verts_at // 4 + verts.size] = verts.reshape(-1)
-        self.blob[:packed.link_bytes].copy_(self._host[:packed.link_bytes], non_blocking=True)
-        self._event = torch.cuda.Event()
-        self._event.record()
+        self._stage.upload_head(self.blob, packed.link_bytes)
         self.last, self._end = packed, packed.packed_bytes
         return packed
 
@@ -939,13 +917,9 @@ class DevicePolygonMasks:
         if end > dst.numel():
             raise ValueError(f"DevicePolygonMasks.rasterise: the packed masks end at byte {end}, the destination holds {dst.numel()}")
         if offsets is not None:
-            if self._event is not None:
-                self._event.synchronize()
-            table = self._host_np.view(np.int32)[:self._polys_at // 4].reshape(self.max_objects, _lib.POLY_DESC_WORDS)
+            table = self._stage.open_np().view(np.int32)[:self._polys_at // 4].reshape(self.max_objects, _lib.POLY_DESC_WORDS)
             table[:self.last.objects, 0] = [o if h else 0 for o, (h, _) in zip(offsets, self.last.sizes)]
-            self.blob[:self._polys_at].copy_(self._host[:self._polys_at], non_blocking=True)
-            self._event = torch.cuda.Event()
-            self._event.record()
+            self._stage.upload_head(self.blob, self._polys_at)
             self._end = end
         kernels.polygon_masks(self.desc, self.polys, self.verts, dst, cap_hw=self.max_hw)
         return dst

@@ -136,7 +136,7 @@ def main():
 
     B = a.batch
     tb = cap.sides[1]["targets"].distill
-    host = torch.zeros(tb._host.numel(), dtype=torch.uint8)
+    host = torch.zeros(tb.nbytes, dtype=torch.uint8)
     views = [v.numpy() for v in tb._views(host)]
     tb._pack_groups(list(range(B)), views[4], views[5], views[6], views[7])          # B samples in B filling tasks
     tb.load_packed(host)

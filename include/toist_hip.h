@@ -888,6 +888,17 @@ TOIST_API int toist_sweep_assemble(const void* img_tok, const void* img_pos, con
                      const uint8_t* txt_pad, int T, int L, const int32_t* pair_image, const int32_t* pair_caption, int P, int D, void* tokens,
                      void* pos, uint8_t* key_pad, int32_t* status, void* stream);
 
+/* The gradient of toist_sweep_assemble with respect to its token inputs, one launch (the shared-image training step, MDETR.encode_pairs):
+ *   d_seq bf16 [P, S, D]  ->  d_img bf16 [B, HW, D], d_txt bf16 [T, L, D]
+ *   d_img[i, s, :] = bf16( sum over p ascending with pair_image[p]   == i of float(d_seq[p, s,      :]) )
+ *   d_txt[t, l, :] = bf16( sum over p ascending with pair_caption[p] == t of float(d_seq[p, HW + l, :]) )
+ * One fp32 accumulator per element, pairs added in ascending order, ONE round-to-nearest-even at the end; no atomics: bit-reproducible.  EVERY
+ * element of an output is written (no pair: zeros; P == 0: all zeros; no memset before the launch).  The tables are read from the device on every
+ * launch; a pair with an entry outside [0, B) / [0, T) is never used as an index and adds to NEITHER output.  d_img or d_txt may be NULL (frozen
+ * backbone / frozen text side): that half is skipped.  Same extent rules as the forward: D % 8 == 0, 16-byte aligned arrays, P*S < 2^31. */
+TOIST_API int toist_sweep_assemble_bwd(const void* d_seq, const int32_t* pair_image, const int32_t* pair_caption, int P, int B, int HW, int T, int L,
+                     int D, void* d_img, void* d_txt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

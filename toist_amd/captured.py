@@ -1,4 +1,4 @@
-"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedEvalStep, CapturedSweepStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
+"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedPairTrainStep, CapturedEvalStep, CapturedSweepStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
 core they share: bucket keys, the static image / text inputs of a bucket and the upload into them, the LRU of buckets, the eager pass followed by the
 capture, and the rule that voids captured graphs once the XCD-resident decoder launches have been turned off."""
 from collections import OrderedDict
@@ -281,6 +281,123 @@ class CapturedTrainStep(_CapturedStep):
             return ent["loss"]
         return self._eager_then_capture(ent, lambda: self._fwd_bwd_opt(ent), reset=lambda: self.optimizer.zero_grad(set_to_none=True),
                                         capture=not _is_distributed())       # (collectives are not captured)
+
+    __call__ = step
+
+
+class CapturedPairTrainStep(_CapturedStep):
+    """CapturedTrainStep for batches whose rows are (image, caption) PAIRS: `batch` images and `captions` captions give exactly `pairs` training
+    samples at the cost of ONE backbone pass per image and ONE text pass per caption (MDETR.encode_pairs; the assembly's backward sums the gradients
+    of an image's pairs).  One graph per bucket (Hp, Wp, Lp) -- the padding rules, the LRU, the eager first step, the finite-loss guard and
+    resolve_skipped() are CapturedTrainStep's -- serves ANY pairing of the bucket's images and captions: the two pair tables sit at fixed device
+    addresses and are refilled before each replay.
+
+    step(samples [batch], tokenized [captions], pair_image, pair_caption, targets [pairs], positive_map) -> total loss.  targets and positive_map
+    are in PAIR order: target dict p belongs to pair p.
+    Unlike CapturedTrainStep: the number of pairs must equal `pairs` (a padding pair would add no-object loss terms and change the criterion):
+    ValueError; the tables are checked on the host before anything is uploaded or launched; torch.distributed raises RuntimeError (no eager
+    fall-back: encode_pairs has no data-parallel path); a criterion with mask losses raises ValueError and a mask-head model NotImplementedError."""
+
+    def __init__(self, model, criterion, optimizer, weight_dict, *, batch, captions, pairs, max_targets_per_image=16, pad_hw=64, pad_tokens=1,
+                 max_graphs=4, contrastive=None, device=None):
+        if hasattr(model, "detr"):
+            model.encode_pairs()                           # a mask-head model: NotImplementedError
+        if "masks" in getattr(criterion, "losses", ()):
+            raise ValueError("CapturedPairTrainStep takes no mask losses: the mask losses index ground-truth masks by image row, not by pair")
+        self.batch, self.captions, self.pairs = int(batch), int(captions), int(pairs)
+        if self.batch <= 0 or self.captions <= 0 or self.pairs <= 0:
+            raise ValueError(f"CapturedPairTrainStep: batch = {batch}, captions = {captions}, pairs = {pairs}")
+        if _is_distributed():
+            raise RuntimeError("CapturedPairTrainStep is single-process: MDETR.encode_pairs has no data-parallel path (run CapturedTrainStep on the "
+                               "expanded batch under torch.distributed)")
+        self.model, self.criterion, self.optimizer, self.weight_dict = model, criterion, optimizer, weight_dict
+        self.max_t = int(max_targets_per_image)
+        self.pad_hw, self.pad_tokens, self.max_graphs = int(pad_hw), int(pad_tokens), int(max_graphs)
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        self.num_queries = model.query_embed.weight.shape[0]
+        self.contrastive = bool(getattr(model, "contrastive_align_loss", False)) if contrastive is None else bool(contrastive)
+        self._host_views, self._host_bytes = staging.typed_views([(torch.int32, (2 * self.pairs,))])
+        self._init_capture_state(xdec_seen=kernels.XDEC_FAILED)
+        self._ready = False                                # device state (seed word, guard words) is set up by the first step that passed the checks
+
+    def _device_state(self):
+        if self._ready:
+            return
+        if kernels.SEED_DEV is None:
+            kernels.SEED_DEV = torch.zeros(1, dtype=torch.int64, device=self.device)
+        from . import engine
+        engine.REUSE_GRAD_BUFFERS = True       # as in CapturedTrainStep: the loop owns the gradients
+        self._init_guard([self.optimizer])
+        self._ready = True
+
+    def _static_inputs(self, key):
+        from .matcher import StaticTargets
+        Hp, Wp, Lp = key
+        dev, P = self.device, self.pairs
+        pad_id = _pad_id(self.model)
+        ent = {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, dev), **_NO_GRAPH,
+               "pair_image": torch.zeros(P, dtype=torch.int32, device=dev), "pair_caption": torch.zeros(P, dtype=torch.int32, device=dev),
+               "stage": staging.Staging(torch.zeros(self._host_bytes, dtype=torch.uint8), dev),       # rows 0 .. P = pair_image, P .. 2P = pair_caption
+               "targets": StaticTargets(P, self.max_t, self.num_queries, 256, dev)}
+        ent["tok"] = static_inputs(self.captions, 1, 1, Lp, pad_id, dev)["tok"]              # the text inputs hold the CAPTIONS, not one row per image
+        return ent
+
+    def check_batch(self, samples, tokenized, pair_image, pair_caption, targets):
+        """Host check of a step's arguments (ValueError; nothing has been uploaded or launched) -> the two tables as int32 host tensors."""
+        from . import sweep
+        B, T = samples.tensors.shape[0], tokenized["input_ids"].shape[0]
+        if B != self.batch or T != self.captions:
+            raise ValueError(f"CapturedPairTrainStep was built for {self.batch} images and {self.captions} captions (got {B} and {T})")
+        pi, pc = sweep.check_tables(pair_image, pair_caption, self.batch, self.captions)
+        if pi.numel() != self.pairs:
+            raise ValueError(f"CapturedPairTrainStep was built for exactly {self.pairs} pairs (got {pi.numel()}): a padding pair would add no-object "
+                             "loss terms")
+        if targets is not None and len(targets) != self.pairs:
+            raise ValueError(f"CapturedPairTrainStep: {len(targets)} target dicts for {self.pairs} pairs (targets are in pair order)")
+        return pi, pc
+
+    def _fill(self, ent, samples, tokenized, pi, pc, targets, positive_map):
+        from . import sweep
+        P = self.pairs
+        upload(ent, samples, tokenized)
+        (tables,) = self._host_views(ent["stage"].open())
+        tables[:P] = pi
+        tables[P:] = pc
+        ent["stage"].upload((ent["pair_image"], tables[:P]), (ent["pair_caption"], tables[P:]))
+        host_t = [{k_: (v.cpu() if torch.is_tensor(v) else v) for k_, v in t.items()} for t in targets]
+        masks = None
+        if self.contrastive:                   # (character spans are looked up in the caption of the target's PAIR; token spans need no lookup)
+            by_pair = sweep.SweepTokenized(tokenized, pc) if any("token_spans" not in t for t in host_t) else None
+            masks = self.criterion.token_masks_host(host_t, by_pair)
+        ent["targets"].load(host_t, positive_map.cpu() if torch.is_tensor(positive_map) else positive_map, masks)
+
+    def _fwd_bwd_opt(self, ent):
+        from .mdetr import weighted_total
+        kernels.SEED_DEV.add_(1000003)
+        mc = self.model.encode_pairs(ent["samples"], ent["tok"], ent["pair_image"], ent["pair_caption"], check=False)      # (host-checked tables)
+        out = self.model.decode(mc)
+        losses = self.criterion(mc, out, ent["targets"], None, None)
+        total = weighted_total(losses, self.weight_dict)
+        total.backward()
+        if self._loss_word is not None:
+            self._loss_word.copy_(total.detach())
+        self.optimizer.step()
+        return total
+
+    def step(self, samples, tokenized, pair_image, pair_caption, targets, positive_map):
+        if _is_distributed():
+            raise RuntimeError("CapturedPairTrainStep is single-process: MDETR.encode_pairs has no data-parallel path")
+        pi, pc = self.check_batch(samples, tokenized, pair_image, pair_caption, targets)
+        self._device_state()
+        ent = self._entry(self.bucket_of(samples, tokenized))
+        self._fill(ent, samples, tokenized, pi, pc, targets, positive_map)
+        if ent["graph"] is not None:
+            ent["graph"].replay()
+            self.replays += 1
+            if hasattr(self.optimizer, "note_replayed_step"):
+                self.optimizer.note_replayed_step()
+            return ent["loss"]
+        return self._eager_then_capture(ent, lambda: self._fwd_bwd_opt(ent), reset=lambda: self.optimizer.zero_grad(set_to_none=True))
 
     __call__ = step
 

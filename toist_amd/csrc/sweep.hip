@@ -53,6 +53,49 @@ __global__ __launch_bounds__(SW_THREADS) void sweep_assemble_kernel(const uint4*
     }
 }
 
+// The gradient of the assembly with respect to its token inputs (the shared-image training step, MDETR.encode_pairs): an image's tokens receive the
+// sum of the image rows of its pairs, a caption's tokens the sum of the caption rows of its pairs.
+//     d_img[i, s, :] = bf16( sum over p ascending, pair_image[p]   == i, of float(d_seq[p, s,      :]) )
+//     d_txt[t, l, :] = bf16( sum over p ascending, pair_caption[p] == t, of float(d_seq[p, HW + l, :]) )
+// A gather, not a scatter: half a wave owns one OUTPUT row (the B*HW image rows first, the T*L caption rows behind them) and finds the row's pairs
+// by scanning the two pair tables, which the host may have rewritten since a capture -- there is no inverse table to keep in step.  The scan is
+// uniform over the lanes of a row and reads 8 bytes per pair from the L1 (P is 8 .. 16 in a training step; any P is correct, nothing is staged on
+// chip).  One fp32 accumulator per element, pairs added in ascending order, one rounding at the end: no atomics, one defined value.  Every output
+// element is written (an image or caption without a pair gets zeros; no memset before the launch).  A pair with a table entry outside [0, B) /
+// [0, T) is never used as an index and adds to neither output (the forward zeroed its sequence and raised the status word).
+__global__ __launch_bounds__(SW_THREADS) void sweep_assemble_bwd_kernel(const uint4* __restrict__ d_seq, int B, int HW, int T, int L,
+                                                                         const int32_t* __restrict__ pair_image,
+                                                                         const int32_t* __restrict__ pair_caption, int P, int V, long long img_rows,
+                                                                         long long rows, uint4* __restrict__ d_img, uint4* __restrict__ d_txt) {
+    const int S = HW + L;
+    const int lane = threadIdx.x & (SW_LANES - 1);
+    for (long long r = (long long)blockIdx.x * SW_ROWS + (threadIdx.x / SW_LANES); r < rows; r += (long long)gridDim.x * SW_ROWS) {
+        const bool image_row = r < img_rows;
+        const int q = (int)(image_row ? r : r - img_rows);            // the row inside its output: q < B*HW or q < T*L, both below 2^31
+        const int per = image_row ? HW : L;
+        const int owner = q / per, s = q - owner * per;               // image i (or caption t) and the token row inside it
+        const size_t seq_row = image_row ? s : HW + s;
+        uint4* dst = (image_row ? d_img : d_txt) + (size_t)q * V;
+        for (int c = lane; c < V; c += SW_LANES) {
+            float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int p = 0; p < P; ++p) {
+                const int i = pair_image[p], t = pair_caption[p];
+                if ((unsigned)i >= (unsigned)B || (unsigned)t >= (unsigned)T || (image_row ? i : t) != owner) continue;
+                const uint4 g = d_seq[((size_t)p * S + seq_row) * V + c];
+                acc[0] += __uint_as_float(g.x << 16);
+                acc[1] += __uint_as_float(g.x & 0xFFFF0000u);
+                acc[2] += __uint_as_float(g.y << 16);
+                acc[3] += __uint_as_float(g.y & 0xFFFF0000u);
+                acc[4] += __uint_as_float(g.z << 16);
+                acc[5] += __uint_as_float(g.z & 0xFFFF0000u);
+                acc[6] += __uint_as_float(g.w << 16);
+                acc[7] += __uint_as_float(g.w & 0xFFFF0000u);
+            }
+            dst[c] = make_uint4(pack2bf(acc[0], acc[1]), pack2bf(acc[2], acc[3]), pack2bf(acc[4], acc[5]), pack2bf(acc[6], acc[7]));
+        }
+    }
+}
+
 }  // namespace toist
 
 using namespace toist;
@@ -76,4 +119,24 @@ extern "C" int toist_sweep_assemble(const void* img_tok, const void* img_pos, co
     hipLaunchKernelGGL(sweep_assemble_kernel, grid, dim3(SW_THREADS), 0, stream, (const uint4*)img_tok, (const uint4*)img_pos, img_pad, B, HW,
                        (const uint4*)txt_tok, txt_pad, T, L, pair_image, pair_caption, (int)rows, D / 8, (uint4*)tokens, (uint4*)pos, key_pad, status);
     return check_launch("toist_sweep_assemble");
+}
+
+extern "C" int toist_sweep_assemble_bwd(const void* d_seq, const int32_t* pair_image, const int32_t* pair_caption, int P, int B, int HW, int T, int L,
+                                        int D, void* d_img, void* d_txt, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    TOIST_REQUIRE(B > 0 && HW > 0 && T > 0 && L > 0 && P >= 0 && D > 0, "toist_sweep_assemble_bwd: bad extents B=%d HW=%d T=%d L=%d P=%d D=%d", B, HW, T, L, P,
+                  D);
+    TOIST_REQUIRE(D % 8 == 0, "toist_sweep_assemble_bwd: D=%d is not a multiple of 8 (rows move as 16-byte accesses)", D);
+    const long long S = (long long)HW + L;
+    TOIST_REQUIRE(S < (1ll << 31) && (long long)P * S < (1ll << 31) && (long long)B * HW < (1ll << 31) && (long long)T * L < (1ll << 31),
+                  "toist_sweep_assemble_bwd: P*(HW+L), B*HW and T*L must stay below 2^31 (P=%d HW=%d L=%d B=%d T=%d)", P, HW, L, B, T);
+    if (!d_img && !d_txt) return TOIST_OK;             // both sides frozen: nothing to write
+    TOIST_REQUIRE(P == 0 || (d_seq && pair_image && pair_caption), "toist_sweep_assemble_bwd: null pointer");
+    TOIST_REQUIRE((((uintptr_t)d_seq | (uintptr_t)d_img | (uintptr_t)d_txt) & 15) == 0, "toist_sweep_assemble_bwd: the bf16 arrays must be 16-byte aligned");
+    const long long img_rows = d_img ? (long long)B * HW : 0, rows = img_rows + (d_txt ? (long long)T * L : 0);
+    const long long want = (rows + SW_ROWS - 1) / SW_ROWS;
+    const dim3 grid((unsigned)(want < SW_MAX_BLOCKS ? want : SW_MAX_BLOCKS));
+    hipLaunchKernelGGL(sweep_assemble_bwd_kernel, grid, dim3(SW_THREADS), 0, stream, (const uint4*)d_seq, B, HW, T, L, pair_image, pair_caption, P, D / 8,
+                       img_rows, rows, (uint4*)d_img, (uint4*)d_txt);
+    return check_launch("toist_sweep_assemble_bwd");
 }

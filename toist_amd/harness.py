@@ -5,7 +5,7 @@ from types import SimpleNamespace
 
 import torch
 
-from .captured import CapturedDistillStep, CapturedEvalStep, CapturedSweepStep, CapturedTrainStep  # noqa: F401
+from .captured import CapturedDistillStep, CapturedEvalStep, CapturedPairTrainStep, CapturedSweepStep, CapturedTrainStep  # noqa: F401
 from .transformer import TokenizedText
 
 
@@ -82,6 +82,45 @@ def synthetic_batch(batch, height=640, width=640, tokens=16, seed=1000, device="
     samples = NestedTensor(images.to(device), mask.to(device))
     targets = [{k: (to(v) if k != "token_spans" else v) for k, v in t.items()} for t in targets]
     return samples, tokenized.to(device), targets, positive_map.to(device)
+
+
+# ---- shared-image training: B images and T captions as P (image, caption) pairs (MDETR.encode_pairs) ----------------------------
+def synthetic_pair_batch(images, captions, pairs, height=640, width=640, tokens=16, seed=1000, max_targets=10, device="cpu"):
+    """What a loader that serves several captions of one augmented image delivers: `images` images, `captions` tokenized captions and P pairs.
+    pairs: a list of (image, caption) in batch order, or the number P -- then pair p is (image p * images // P, caption p % captions): every image
+    and caption is used when P >= max(images, captions), each image by a run of consecutive pairs.
+    -> (samples [B], tokenized [T], pair_image int32 [P], pair_caption int32 [P] (host), targets [P], positive_map [sum of the targets, 256]): the
+    targets and the positive map are in PAIR order -- target dict p belongs to pair p, as batch row p of the expanded batch would carry it."""
+    from . import sweep
+    images, captions = int(images), int(captions)
+    if not isinstance(pairs, (list, tuple)):
+        P = int(pairs)
+        pairs = [(p * images // P, p % captions) for p in range(P)]
+    pair_image, pair_caption, P = sweep.pair_tables(images, captions, pairs)
+    samples = synthetic_batch(images, height, width, tokens=tokens, seed=seed, device=device, max_targets=0)[0]
+    tokenized = synthetic_batch(captions, 1, 1, tokens=tokens, seed=seed + 1, device=device, max_targets=0)[1]
+    _, _, targets, positive_map = synthetic_batch(P, 1, 1, tokens=tokens, seed=seed + 2, device=device, max_targets=max_targets)
+    return samples, tokenized, pair_image, pair_caption, targets, positive_map
+
+
+def expand_pairs(samples, tokenized, pair_image, pair_caption, targets, positive_map):
+    """The per-sample batch of a pair batch: samples[pair_image], tokenized[pair_caption] and the same targets -> (samples [P], tokenized [P],
+    targets, positive_map), what MDETR.encode / CapturedTrainStep take.  This is what the per-sample path has to run for the same P problems."""
+    from . import sweep
+    from .misc import NestedTensor
+    dev = samples.tensors.device
+    rows = torch.as_tensor(sweep._index_list(pair_image, "pair_image"), dtype=torch.int64, device=dev)
+    expanded = NestedTensor(samples.tensors.index_select(0, rows), samples.mask.index_select(0, rows))
+    return expanded, sweep.SweepTokenized(tokenized, sweep._index_list(pair_caption, "pair_caption")), targets, positive_map
+
+
+def pair_train_losses(model, criterion, batch):
+    """The eager forward half of the shared-image training step on batch = (samples, tokenized, pair_image, pair_caption, targets, positive_map):
+    encode_pairs -> decode -> criterion.  -> (loss dict, outputs)."""
+    samples, tokenized, pair_image, pair_caption, targets, positive_map = batch
+    mc = model.encode_pairs(samples, tokenized, pair_image, pair_caption)
+    outputs = model.decode(mc)
+    return criterion(mc, outputs, targets, positive_map, None), outputs
 
 
 # ---- distillation (BASELINE config 5): (noun, pronoun) pairs -------------------------------------------------------

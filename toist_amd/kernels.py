@@ -1181,6 +1181,35 @@ def sweep_assemble(img_tok, img_pos, img_pad, txt_tok, txt_pad, pair_image, pair
     return out
 
 
+def sweep_assemble_bwd(d_seq, pair_image, pair_caption, B, HW, T, L, want_img=True, want_txt=True, out=None):
+    """The gradient of sweep_assemble with respect to its token inputs in one launch (include/toist_hip.h: toist_sweep_assemble_bwd).  d_seq bf16
+    [P, HW + L, D], pair_image / pair_caption int32 [P] ON THE DEVICE -> (d_img bf16 [B, HW, D] or None, d_txt bf16 [T, L, D] or None): per element
+    the fp32 sum over the image's (caption's) pairs in ascending pair order, rounded to bf16 once.  want_img / want_txt = False skips that half (a
+    frozen backbone / text side).  Every element of an output is written; out = (d_img, d_txt) buffers to write into."""
+    B, HW, T, L = int(B), int(HW), int(T), int(L)
+    if d_seq.dim() != 3 or d_seq.shape[1] != HW + L:
+        raise ValueError(f"sweep_assemble_bwd: d_seq must be [P, HW + L, D] with HW + L = {HW + L} (got {tuple(d_seq.shape)})")
+    P, S, D = d_seq.shape
+    dev = d_seq.device
+    if pair_image.dim() != 1 or pair_caption.dim() != 1 or pair_image.numel() != P or pair_caption.numel() != P:
+        raise ValueError("sweep_assemble_bwd: pair_image and pair_caption are int32 vectors with one entry per row of d_seq")
+    for t in (d_seq, pair_image, pair_caption):
+        if not t.is_contiguous():
+            raise ValueError("sweep_assemble_bwd: every input must be contiguous")
+    d_img, d_txt = out if out is not None else (None, None)
+    if want_img and d_img is None:
+        d_img = torch.empty(B, HW, D, dtype=torch.bfloat16, device=dev)
+    if want_txt and d_txt is None:
+        d_txt = torch.empty(T, L, D, dtype=torch.bfloat16, device=dev)
+    d_img, d_txt = (d_img if want_img else None), (d_txt if want_txt else None)
+    if (d_img is not None and (tuple(d_img.shape) != (B, HW, D) or not d_img.is_contiguous())) or \
+            (d_txt is not None and (tuple(d_txt.shape) != (T, L, D) or not d_txt.is_contiguous())):
+        raise ValueError("sweep_assemble_bwd: out = (d_img [B, HW, D], d_txt [T, L, D]), contiguous")
+    _lib.check(_lib.lib().toist_sweep_assemble_bwd(_p(d_seq, torch.bfloat16), _p(pair_image, torch.int32), _p(pair_caption, torch.int32), P, B, HW, T, L,
+                                                   D, _p(d_img, torch.bfloat16), _p(d_txt, torch.bfloat16), _stream()), "toist_sweep_assemble_bwd")
+    return d_img, d_txt
+
+
 def mask_pack(dense):
     """[n, h, w] bool / uint8 -> bit planes."""
     n, h, w = dense.shape

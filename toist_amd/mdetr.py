@@ -375,6 +375,89 @@ class MDETR(nn.Module):
         k.stamp("fwd.join")
         return state, text
 
+    # ---- shared-image training: P (image, caption) pairs at the cost of B image passes and T text passes, differentiable ------------
+    def encode_pairs(self, samples, captions, pair_image, pair_caption, out=None, check=None):
+        """encode() for a batch whose rows are PAIRS: the backbone runs on the B images, the text branch on the T captions (forked onto the text side
+        stream and joined as in encode), one toist_sweep_assemble launch builds the P cross-modal sequences and the encoder runs over them -> the
+        memory cache of an ordinary batch of P rows: decode() and SetCriterion take it unchanged, with P target dicts and a positive map in pair order.
+        Works with grad enabled and in train(): the assembly's backward (toist_sweep_assemble_bwd) sums the gradients of an image's (a caption's)
+        pairs in ascending pair order.  Exact because FrozenBN makes an image's features independent of its batch mates.  In train() a caption's
+        RoBERTa dropout mask is drawn once and shared by its pairs (the reference draws one per sample); encoder and decoder draw per pair row.
+        pair_image / pair_caption: lists or host tensors (checked here, before anything is launched), or int32 DEVICE vectors (checked by the launch:
+        its status word is read right away outside a capture -- check=False leaves kernels.sweep_check() to the caller).  out: (tokens, pos, key_pad)
+        buffers for the assembled sequences.  The cache carries "tokenized" as a sweep.SweepTokenized over the pair rows.
+        Not supported: backward cuts / data-parallel training (RuntimeError), mask-head models (DETRsegm raises NotImplementedError)."""
+        from . import sweep
+        from .transformer import EncodedText
+        if not isinstance(samples, NestedTensor):
+            samples = NestedTensor.from_tensor_list(samples)
+        if getattr(self, "split_backward", False):
+            raise RuntimeError("encode_pairs does not support backward cuts (split_backward / parallel.enable_backward_cuts, the data-parallel step): "
+                               "the shared image pass is single-process; run encode() on the expanded batch there")
+        if not samples.tensors.is_cuda:
+            raise RuntimeError("encode_pairs needs device tensors (got a CPU tensor); there is no CPU fallback")
+        dev = samples.tensors.device
+        B = samples.tensors.shape[0]
+        if isinstance(captions, EncodedText):
+            T = captions.key_pad.shape[0]
+        elif isinstance(captions, (list, tuple)):
+            T = len(captions)
+        else:
+            T = captions["input_ids"].shape[0]
+        on_device = torch.is_tensor(pair_image) and pair_image.is_cuda
+        pc_host = None
+        if on_device:
+            pi, pc = pair_image, pair_caption
+        else:
+            pi_host, pc_host = sweep.check_tables(pair_image, pair_caption, B, T)             # ValueError before anything is launched
+            pi, pc = pi_host.to(dev, non_blocking=True), pc_host.to(dev, non_blocking=True)
+        # the text branch beside the backbone, as in encode()
+        side = None
+        if isinstance(captions, EncodedText):
+            text = captions
+        else:
+            fork = engine.overlap_enabled()
+            if fork:
+                main = torch.cuda.current_stream()
+                side = engine.side_stream(dev, "text")
+                k.stamp("fwd.fork")
+                side.wait_stream(main)
+                functions.REJOIN = main
+            try:
+                with torch.cuda.stream(side if fork else torch.cuda.current_stream()):
+                    k.stamp("fwd.text.start")
+                    tokenized = self.transformer._tokenize(captions, dev)
+                    flat, key_pad_text = self.transformer.encode_text(tokenized)
+                    k.stamp("fwd.text.end")
+            finally:
+                functions.REJOIN = None
+            text = EncodedText(tokenized, flat, key_pad_text)
+        k.stamp("fwd.backbone.start")
+        feats = self.backbone[0].forward_native(samples.tensors, (4,), premasked=(0,))
+        k.stamp("fwd.backbone.end")
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+        k.stamp("fwd.join")
+        c5 = feats[-1]
+        _, h, w, _ = c5.shape
+        mask = nearest_mask(samples.mask, (h, w))
+        pos_img = self.backbone[1].tokens(mask, tail=0) if hasattr(self.backbone[1], "tokens") else \
+            self.backbone[1](NestedTensor(c5.permute(0, 3, 1, 2), mask)).flatten(2).permute(0, 2, 1).to(BF16).contiguous()
+        tok = self._project(c5).view(B, h * w, -1)
+        HW, d = h * w, tok.shape[-1]
+        L = text.key_pad.shape[1]
+        P, S = pi.numel(), HW + L
+        read_status = (on_device if check is None else bool(check)) and not torch.cuda.is_current_stream_capturing()
+        tokens, pos, key_pad = _PairAssembleFn.apply(tok, pos_img, mask.flatten(1), text.flat.view(T, L, d), text.key_pad, pi, pc, out, read_status)
+        tokenized = None
+        if text.tokenized is not None and (pc_host is not None or read_status):
+            tokenized = sweep.SweepTokenized(text.tokenized, pc_host if pc_host is not None else pc)
+        seq_mask = key_pad.view(torch.bool)
+        mc = self.transformer.encode_sequences(tokens.view(P * S, d), pos.view(P * S, d), seq_mask, P, S, L, self.query_embed.weight, tokenized,
+                                               seq_mask[:, HW:], tokens[:, HW:])
+        mc["_native"].update(features=feats, cuts={}, feat_mask=mask, src_proj=tok, pair_image=pi, pair_caption=pc)
+        return mc
+
     def decode(self, memory_cache):
         native = memory_cache.get("_native")
         key = "img_memory_mod" if (self.args is not None and getattr(self.args, "cluster", False)) else "img_memory"
@@ -908,6 +991,34 @@ class _ContrastiveFn(torch.autograd.Function):
         k.contrastive_bwd(pq, pt, tok_mask, m.tgt_off_dev, m.match_off_dev, m.src[-L:], m.tgt[-L:], num_boxes, ctx.temperature,
                           g.float().contiguous(), dpq, dpt, live_tokens=ctx.live_tokens)
         return dpq, dpt, None, None, None, None, None
+
+
+class _PairAssembleFn(torch.autograd.Function):
+    """(tokens [P,S,d], pos [P,S,d], key_pad [P,S]) = toist_sweep_assemble of B images' and T captions' tokens over P pairs (csrc/sweep.hip); backward =
+    toist_sweep_assemble_bwd: an image's (a caption's) token gradient is the fp32 sum over its pairs, in pair order, rounded to bf16 once.  The position
+    rows get a gradient only when they require one (PositionEmbeddingLearned): a second call of the same launcher, image half only.  The sine encoding
+    and key_pad get none."""
+
+    @staticmethod
+    def forward(ctx, img_tok, img_pos, img_pad, txt_tok, txt_pad, pair_image, pair_caption, out, check):
+        tokens, pos, key_pad = k.sweep_assemble(img_tok.contiguous(), img_pos.contiguous(), img_pad.contiguous(), txt_tok.contiguous(),
+                                                txt_pad.contiguous(), pair_image, pair_caption, out=out, check=check)
+        ctx.tables = (pair_image, pair_caption)
+        ctx.extents = (img_tok.shape[0], img_tok.shape[1], txt_tok.shape[0], txt_tok.shape[1])
+        ctx.mark_non_differentiable(key_pad)
+        return tokens, pos, key_pad
+
+    @staticmethod
+    def backward(ctx, g_tokens, g_pos, _g_pad):
+        pi, pc = ctx.tables
+        B, HW, T, L = ctx.extents
+        d_img = d_txt = d_pos = None
+        want_img, want_txt = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        if g_tokens is not None and (want_img or want_txt):
+            d_img, d_txt = k.sweep_assemble_bwd(g_tokens.to(BF16).contiguous(), pi, pc, B, HW, T, L, want_img=want_img, want_txt=want_txt)
+        if g_pos is not None and ctx.needs_input_grad[1]:
+            d_pos, _ = k.sweep_assemble_bwd(g_pos.to(BF16).contiguous(), pi, pc, B, HW, T, L, want_img=True, want_txt=False)
+        return d_img, d_pos, None, d_txt, None, None, None, None, None
 
 
 class _L2NormFn(torch.autograd.Function):

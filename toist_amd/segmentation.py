@@ -489,6 +489,11 @@ class DETRsegm(nn.Module):
 
     sweep_images = sweep_text = sweep_pairs = sweep_stages = encode_sweep = _no_sweep
 
+    def encode_pairs(self, *args, **kw):
+        raise NotImplementedError("shared-image training with a mask head: the mask program and the mask losses index an image's FPN terms and ground-truth "
+                                  "masks by batch row, so a batch of (image, caption) pairs needs a pair table inside them.  Train a detection model "
+                                  "through MDETR.encode_pairs, or run encode() on the expanded batch")
+
 
 # ------------------------------------------------------------------------------------------ mask losses
 class _MaskLossFn(torch.autograd.Function):

@@ -1,6 +1,9 @@
 """The steps replayed from hipGraphs -- CapturedTrainStep, CapturedPairTrainStep, CapturedEvalStep, CapturedSweepStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
-core they share: bucket keys, the static image / text inputs of a bucket and the upload into them, the LRU of buckets, the eager pass followed by the
-capture, and the rule that voids captured graphs once the XCD-resident decoder launches have been turned off."""
+core they share: bucket keys, the static image / text inputs of a bucket and the upload into them, the pair tables of a pair-shaped bucket and
+their fill (pair_inputs / fill_pair_inputs), the LRU of buckets, the eager pass followed by the capture, the rule that voids captured graphs once
+the XCD-resident decoder launches have been turned off, and the bodies of a step on a filled bucket: _CapturedStep._train_tail and
+_replay_or_capture for the two training steps (the distillation step keeps its own two-call backward and shares _replayed), _replay_checked for
+the two inference steps."""
 from collections import OrderedDict
 
 import torch
@@ -18,6 +21,24 @@ def _is_distributed():
 
 def _pad_id(model):
     return getattr(getattr(model, "detr", model).transformer.text_encoder.config, "pad_token_id", 1)
+
+
+def round_up(v, m):
+    return (int(v) + m - 1) // m * m
+
+
+def size_pairs(v):
+    """(h, w) rows as a caller has them -- lists, host tensors, a list of tensors -- -> a list of int pairs."""
+    rows = v.tolist() if torch.is_tensor(v) else [(r.tolist() if torch.is_tensor(r) else r) for r in v]
+    return [(int(r[0]), int(r[1])) for r in rows]
+
+
+def host_targets(targets):
+    return [{k_: (v.cpu() if torch.is_tensor(v) else v) for k_, v in t.items()} for t in targets]
+
+
+def host_positive_map(positive_map):
+    return positive_map.cpu() if torch.is_tensor(positive_map) else positive_map
 
 
 def static_inputs(batch, Hp, Wp, Lp, pad_id, device, mask_fill=True):
@@ -45,6 +66,32 @@ def upload(ent, samples, tokenized):
         att.zero_()
     ids[:, :L].copy_(tokenized["input_ids"], non_blocking=True)
     att[:, :L].copy_(tokenized["attention_mask"], non_blocking=True)
+
+
+def pair_inputs(captions, pairs, Lp, pad_id, device, sizes=False):
+    """What a pair-shaped bucket holds besides its images: text inputs for the CAPTIONS (not one row per image), the two int32 pair tables at fixed
+    device addresses (+ sizes: an int64 [pairs, 2] table of each pair's original (h, w)) and ONE staging buffer for them -- rows 0 .. P = pair_image,
+    P .. 2P = pair_caption, behind them the sizes -- so that fill_pair_inputs' copies travel under one fence."""
+    views, nbytes = staging.typed_views([(torch.int32, (2 * pairs,))] + ([(torch.int64, (pairs, 2))] if sizes else []))
+    ent = {"tok": static_inputs(captions, 1, 1, Lp, pad_id, device)["tok"],
+           "pair_image": torch.zeros(pairs, dtype=torch.int32, device=device), "pair_caption": torch.zeros(pairs, dtype=torch.int32, device=device),
+           "stage": staging.Staging(torch.zeros(nbytes, dtype=torch.uint8), device), "stage_views": views}
+    if sizes:
+        ent["sizes"] = torch.ones(pairs, 2, dtype=torch.int64, device=device)
+    return ent
+
+
+def fill_pair_inputs(ent, pi, pc, sizes=None):
+    """Host tables (int32 [P] each, + a list of P (h, w) when the bucket holds sizes) into pair_inputs' device tables: two or three copies, one record."""
+    P = pi.numel()
+    tables, *rest = ent["stage_views"](ent["stage"].open())
+    tables[:P] = pi
+    tables[P:] = pc
+    copies = [(ent["pair_image"], tables[:P]), (ent["pair_caption"], tables[P:])]
+    if sizes is not None:
+        rest[0].copy_(torch.tensor(sizes, dtype=torch.int64))
+        copies.append((ent["sizes"], rest[0]))
+    ent["stage"].upload(*copies)
 
 
 def row_results(out, rows, live, num_queries, device):
@@ -118,8 +165,7 @@ class _CapturedStep:
     def bucket_of(self, samples, tokenized):
         H, W = samples.tensors.shape[-2:]
         L = tokenized["input_ids"].shape[1]
-        up = lambda v, m: (int(v) + m - 1) // m * m
-        return up(H, self.pad_hw), up(W, self.pad_hw), up(L, self.pad_tokens)
+        return round_up(H, self.pad_hw), round_up(W, self.pad_hw), round_up(L, self.pad_tokens)
 
     def _void_graphs(self, force=False):
         """Graphs captured before kernels.XDEC_FAILED flipped contain XCD-resident decoder launches, which are off from then on (kernels.xdec_check: an
@@ -169,6 +215,53 @@ class _CapturedStep:
                 self.captures += 1
         torch.cuda.current_stream().wait_stream(side)
         return result
+
+    # -- training steps: self.criterion, self.weight_dict and one self.optimizer; the subclass's _fwd_bwd_opt(ent) ends in _train_tail ---------------
+    def _train_tail(self, mc, out, targets):
+        """criterion -> weighted sum -> backward -> loss word -> optimizer.step() -> the total loss.  (The seed bump comes before the forward.)"""
+        from .mdetr import weighted_total
+        total = weighted_total(self.criterion(mc, out, targets, None, None), self.weight_dict)
+        total.backward()
+        if self._loss_word is not None:
+            self._loss_word.copy_(total.detach())      # (device to device, captured like any other launch: every replay hands its own loss to the guard)
+        self.optimizer.step()
+        return total
+
+    def _replayed(self, ent, optimizers):
+        """Behind a training graph's replay -> its loss."""
+        self.replays += 1
+        for o in optimizers:
+            if hasattr(o, "note_replayed_step"):
+                o.note_replayed_step()                 # copies of the weights that the captured tail does not rewrite are stale now
+        return ent["loss"]
+
+    def _replay_or_capture(self, ent, capture=True):
+        """A training step on a filled bucket: the replay of its graph, or its first step run eagerly and captured right after."""
+        if ent["graph"] is not None:
+            ent["graph"].replay()
+            return self._replayed(ent, [self.optimizer])
+        return self._eager_then_capture(ent, lambda: self._fwd_bwd_opt(ent), reset=lambda: self.optimizer.zero_grad(set_to_none=True), capture=capture)
+
+    # -- inference steps ---------------------------------------------------------------------------------------------------------------------------
+    def _replay_checked(self, ent, forward, results, handed_out=None):
+        """An inference step on a filled bucket -> results().  The replay of its graph; the status words are read where the results are handed out
+        (one 4-byte read each; the first synchronises): the XCD-resident decoder's when the graph holds that launch, then the step's own
+        (handed_out(), which may raise) -- also behind a failed decoder launch.  That failure drops every graph (the launch's groups were not
+        co-resident: per-op launches from now on), and the same batch runs again as a first batch does: forward() eagerly -- the eval-mode decode
+        checks, and if need be repeats, an XCD-resident launch of the eager pass by itself -- and captured right after."""
+        if ent["graph"] is not None:
+            ent["graph"].replay()
+            self.replays += 1
+            failed = ent["xdec"] and kernels.xdec_check(raise_on_failure=False)
+            if handed_out is not None:
+                handed_out()
+            if not failed:
+                return results()
+            self._void_graphs(force=True)
+        self._eager_then_capture(ent, forward)
+        if handed_out is not None:
+            handed_out()
+        return results()
 
 
 class CapturedTrainStep(_CapturedStep):
@@ -239,9 +332,9 @@ class CapturedTrainStep(_CapturedStep):
         upload(ent, samples, tokenized)
         st = ent["targets"]
         if packed is None:
-            host_t = [{k_: (v.cpu() if torch.is_tensor(v) else v) for k_, v in t.items()} for t in targets]
+            host_t = host_targets(targets)
             masks = self.criterion.token_masks_host(host_t, tokenized) if self.contrastive else None
-            st.load(host_t, positive_map.cpu() if torch.is_tensor(positive_map) else positive_map, masks)
+            st.load(host_t, host_positive_map(positive_map), masks)
         else:
             st.load_packed(packed)
         if target_masks is not None:
@@ -252,17 +345,10 @@ class CapturedTrainStep(_CapturedStep):
             target_masks.write_into(st)        # outside the graph, like upload(): the ground-truth masks of the batch, gathered on the device
 
     def _fwd_bwd_opt(self, ent):
-        from .mdetr import weighted_total
         kernels.SEED_DEV.add_(1000003)
         mc = self.model(ent["samples"], ent["tok"], encode_and_save=True)
         out = self.model(ent["samples"], ent["tok"], encode_and_save=False, memory_cache=mc)
-        losses = self.criterion(mc, out, ent["targets"], None, None)
-        total = weighted_total(losses, self.weight_dict)
-        total.backward()
-        if self._loss_word is not None:
-            self._loss_word.copy_(total.detach())      # (device to device, captured like any other launch: every replay hands its own loss to the guard)
-        self.optimizer.step()
-        return total
+        return self._train_tail(mc, out, ent["targets"])
 
     # -- the step -------------------------------------------------------------------------------------------------------------------
     def step(self, samples, tokenized, targets=None, positive_map=None, packed=None, target_masks=None):
@@ -273,14 +359,7 @@ class CapturedTrainStep(_CapturedStep):
                                  "whose pack() holds this batch's masks")
         ent = self._entry(self.bucket_of(samples, tokenized))
         self._fill(ent, samples, tokenized, targets, positive_map, packed, target_masks)
-        if ent["graph"] is not None:
-            ent["graph"].replay()
-            self.replays += 1
-            if hasattr(self.optimizer, "note_replayed_step"):
-                self.optimizer.note_replayed_step()      # copies of the weights that the captured tail does not rewrite are stale now
-            return ent["loss"]
-        return self._eager_then_capture(ent, lambda: self._fwd_bwd_opt(ent), reset=lambda: self.optimizer.zero_grad(set_to_none=True),
-                                        capture=not _is_distributed())       # (collectives are not captured)
+        return self._replay_or_capture(ent, capture=not _is_distributed())       # (collectives are not captured)
 
     __call__ = step
 
@@ -316,7 +395,6 @@ class CapturedPairTrainStep(_CapturedStep):
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
         self.num_queries = model.query_embed.weight.shape[0]
         self.contrastive = bool(getattr(model, "contrastive_align_loss", False)) if contrastive is None else bool(contrastive)
-        self._host_views, self._host_bytes = staging.typed_views([(torch.int32, (2 * self.pairs,))])
         self._init_capture_state(xdec_seen=kernels.XDEC_FAILED)
         self._ready = False                                # device state (seed word, guard words) is set up by the first step that passed the checks
 
@@ -333,14 +411,9 @@ class CapturedPairTrainStep(_CapturedStep):
     def _static_inputs(self, key):
         from .matcher import StaticTargets
         Hp, Wp, Lp = key
-        dev, P = self.device, self.pairs
         pad_id = _pad_id(self.model)
-        ent = {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, dev), **_NO_GRAPH,
-               "pair_image": torch.zeros(P, dtype=torch.int32, device=dev), "pair_caption": torch.zeros(P, dtype=torch.int32, device=dev),
-               "stage": staging.Staging(torch.zeros(self._host_bytes, dtype=torch.uint8), dev),       # rows 0 .. P = pair_image, P .. 2P = pair_caption
-               "targets": StaticTargets(P, self.max_t, self.num_queries, 256, dev)}
-        ent["tok"] = static_inputs(self.captions, 1, 1, Lp, pad_id, dev)["tok"]              # the text inputs hold the CAPTIONS, not one row per image
-        return ent
+        return {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, self.device), **pair_inputs(self.captions, self.pairs, Lp, pad_id, self.device),
+                **_NO_GRAPH, "targets": StaticTargets(self.pairs, self.max_t, self.num_queries, 256, self.device)}
 
     def check_batch(self, samples, tokenized, pair_image, pair_caption, targets):
         """Host check of a step's arguments (ValueError; nothing has been uploaded or launched) -> the two tables as int32 host tensors."""
@@ -358,31 +431,19 @@ class CapturedPairTrainStep(_CapturedStep):
 
     def _fill(self, ent, samples, tokenized, pi, pc, targets, positive_map):
         from . import sweep
-        P = self.pairs
         upload(ent, samples, tokenized)
-        (tables,) = self._host_views(ent["stage"].open())
-        tables[:P] = pi
-        tables[P:] = pc
-        ent["stage"].upload((ent["pair_image"], tables[:P]), (ent["pair_caption"], tables[P:]))
-        host_t = [{k_: (v.cpu() if torch.is_tensor(v) else v) for k_, v in t.items()} for t in targets]
+        fill_pair_inputs(ent, pi, pc)
+        host_t = host_targets(targets)
         masks = None
         if self.contrastive:                   # (character spans are looked up in the caption of the target's PAIR; token spans need no lookup)
             by_pair = sweep.SweepTokenized(tokenized, pc) if any("token_spans" not in t for t in host_t) else None
             masks = self.criterion.token_masks_host(host_t, by_pair)
-        ent["targets"].load(host_t, positive_map.cpu() if torch.is_tensor(positive_map) else positive_map, masks)
+        ent["targets"].load(host_t, host_positive_map(positive_map), masks)
 
     def _fwd_bwd_opt(self, ent):
-        from .mdetr import weighted_total
         kernels.SEED_DEV.add_(1000003)
         mc = self.model.encode_pairs(ent["samples"], ent["tok"], ent["pair_image"], ent["pair_caption"], check=False)      # (host-checked tables)
-        out = self.model.decode(mc)
-        losses = self.criterion(mc, out, ent["targets"], None, None)
-        total = weighted_total(losses, self.weight_dict)
-        total.backward()
-        if self._loss_word is not None:
-            self._loss_word.copy_(total.detach())
-        self.optimizer.step()
-        return total
+        return self._train_tail(mc, self.model.decode(mc), ent["targets"])
 
     def step(self, samples, tokenized, pair_image, pair_caption, targets, positive_map):
         if _is_distributed():
@@ -391,13 +452,7 @@ class CapturedPairTrainStep(_CapturedStep):
         self._device_state()
         ent = self._entry(self.bucket_of(samples, tokenized))
         self._fill(ent, samples, tokenized, pi, pc, targets, positive_map)
-        if ent["graph"] is not None:
-            ent["graph"].replay()
-            self.replays += 1
-            if hasattr(self.optimizer, "note_replayed_step"):
-                self.optimizer.note_replayed_step()
-            return ent["loss"]
-        return self._eager_then_capture(ent, lambda: self._fwd_bwd_opt(ent), reset=lambda: self.optimizer.zero_grad(set_to_none=True))
+        return self._replay_or_capture(ent)
 
     __call__ = step
 
@@ -445,14 +500,9 @@ class CapturedEvalStep(_CapturedStep):
         self._init_capture_state()
 
     # -- helpers ------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _pairs(v):
-        rows = v.tolist() if torch.is_tensor(v) else [(r.tolist() if torch.is_tensor(r) else r) for r in v]
-        return [(int(r[0]), int(r[1])) for r in rows]
-
     def check_sizes(self, key, orig_sizes, sizes):
         """Host check of a batch's sizes against the bucket and the mask capacity (ValueError; nothing has been launched).  -> (orig, sizes) as int pairs."""
-        orig, crop = self._pairs(orig_sizes), self._pairs(sizes)
+        orig, crop = size_pairs(orig_sizes), size_pairs(sizes)
         if len(orig) != self.batch or len(crop) != self.batch:
             raise ValueError(f"CapturedEvalStep was built for batches of {self.batch} images (got {len(orig)} original sizes, {len(crop)} sizes)")
         for (h, w), (ch, cw) in zip(orig, crop):
@@ -536,16 +586,7 @@ class CapturedEvalStep(_CapturedStep):
             self.model.eval()
         ent = self._entry(key)
         self._fill(ent, samples, tokenized, orig, crop, dataset_names, captions)
-        if ent["graph"] is not None:
-            ent["graph"].replay()
-            self.replays += 1
-            # the results are handed out here: read the XCD-resident launch's status word first (one 4-byte read; it synchronises)
-            if not (ent["xdec"] and kernels.xdec_check(raise_on_failure=False)):
-                return self._results(ent, orig)
-            self._void_graphs(force=True)                  # the launch's groups were not co-resident: per-op launches from now on, same batch again
-        # (the eval-mode decode checks, and if need be repeats, an XCD-resident launch of the eager pass by itself)
-        self._eager_then_capture(ent, lambda: self._forward(ent, key))
-        return self._results(ent, orig)
+        return self._replay_checked(ent, lambda: self._forward(ent, key), lambda: self._results(ent, orig))
 
     __call__ = step
 
@@ -580,33 +621,20 @@ class CapturedSweepStep(_CapturedStep):
         self.pad_hw, self.pad_tokens, self.max_graphs = int(pad_hw), int(pad_tokens), int(max_graphs)
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
         self.num_queries = model.query_embed.weight.shape[0]
-        self._host_views, self._host_bytes = staging.typed_views([(torch.int32, (2 * self.pairs,)), (torch.int64, (self.pairs, 2))])
         self._init_capture_state()
 
     def _static_inputs(self, key):
         Hp, Wp, Lp = key
-        dev, P = self.device, self.pairs
         pad_id = _pad_id(self.model)
-        ent = {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, dev), **_NO_GRAPH,
-               "pair_image": torch.zeros(P, dtype=torch.int32, device=dev), "pair_caption": torch.zeros(P, dtype=torch.int32, device=dev),
-               "sizes": torch.ones(P, 2, dtype=torch.int64, device=dev),
-               # staging: rows 0 .. P = pair_image, P .. 2P = pair_caption (int32); behind them the sizes (int64): three copies under one fence
-               "stage": staging.Staging(torch.zeros(self._host_bytes, dtype=torch.uint8), dev), "uploaded": None, "out": None}
-        ent["tok"] = static_inputs(self.captions, 1, 1, Lp, pad_id, dev)["tok"]              # the text inputs hold the CAPTIONS, not one row per image
-        return ent
+        return {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, self.device), **pair_inputs(self.captions, self.pairs, Lp, pad_id, self.device, sizes=True),
+                **_NO_GRAPH, "uploaded": None, "out": None}
 
     def _fill(self, ent, samples, tokenized, pi, pc, sizes):
         upload(ent, samples, tokenized)
         tables = (pi.tolist(), pc.tolist(), sizes)
-        if ent["uploaded"] == tables:
-            return
-        P = self.pairs
-        tables_host, sizes_host = self._host_views(ent["stage"].open())
-        tables_host[:P] = pi
-        tables_host[P:] = pc
-        sizes_host.copy_(torch.tensor(sizes, dtype=torch.int64))
-        ent["stage"].upload((ent["pair_image"], tables_host[:P]), (ent["pair_caption"], tables_host[P:]), (ent["sizes"], sizes_host))
-        ent["uploaded"] = tables
+        if ent["uploaded"] != tables:                      # (the full product of a whole evaluation is uploaded once)
+            fill_pair_inputs(ent, pi, pc, sizes)
+            ent["uploaded"] = tables
 
     def _forward(self, ent):
         """The launches of one batch on the bucket's static inputs (eagerly, and once more under capture)."""
@@ -634,7 +662,7 @@ class CapturedSweepStep(_CapturedStep):
         if samples.tensors.shape[0] != self.batch or tokenized["input_ids"].shape[0] != self.captions:
             raise ValueError(f"CapturedSweepStep was built for {self.batch} images and {self.captions} captions "
                              f"(got {samples.tensors.shape[0]} and {tokenized['input_ids'].shape[0]})")
-        orig = CapturedEvalStep._pairs(orig_sizes)
+        orig = size_pairs(orig_sizes)
         if len(orig) != self.batch or any(h <= 0 or w <= 0 for h, w in orig):
             raise ValueError(f"CapturedSweepStep: {len(orig)} original sizes for {self.batch} images, or a size that is not positive")
         pi, pc, live = sweep.pair_tables(self.batch, self.captions, pairs, capacity=self.pairs)           # ValueError before anything is launched
@@ -644,17 +672,8 @@ class CapturedSweepStep(_CapturedStep):
         key = self.bucket_of(samples, tokenized)
         ent = self._entry(key)
         self._fill(ent, samples, tokenized, pi, pc, sizes)
-        if ent["graph"] is not None:
-            ent["graph"].replay()
-            self.replays += 1
-            failed = ent["xdec"] and kernels.xdec_check(raise_on_failure=False)          # (one 4-byte read each; the first synchronises)
-            self._handed_out(ent)
-            if not failed:
-                return self._results(ent, live), pi, pc, live
-            self._void_graphs(force=True)                  # the decoder launch's groups were not co-resident: per-op launches from now on, same batch again
-        self._eager_then_capture(ent, lambda: self._forward(ent))
-        self._handed_out(ent)
-        return self._results(ent, live), pi, pc, live
+        results = self._replay_checked(ent, lambda: self._forward(ent), lambda: self._results(ent, live), lambda: self._handed_out(ent))
+        return results, pi, pc, live
 
     __call__ = step
 
@@ -765,8 +784,8 @@ class CapturedDistillStep(_CapturedStep):
         if shapes[0][0] != self.B or any(int(t["input_ids"].shape[0]) != self.B for t in batch["tokenized"]):
             raise ValueError(f"CapturedDistillStep was built for batches of {self.B} pairs (got {shapes[0][0]} images, "
                              f"{[int(t['input_ids'].shape[0]) for t in batch['tokenized']]} captions)")
-        up = lambda v, m: (int(v) + m - 1) // m * m
-        return up(shapes[0][2], self.pad_hw), up(shapes[0][3], self.pad_hw), up(max(int(t["input_ids"].shape[1]) for t in batch["tokenized"]), self.pad_tokens)
+        longer = max(int(t["input_ids"].shape[1]) for t in batch["tokenized"])
+        return round_up(shapes[0][2], self.pad_hw), round_up(shapes[0][3], self.pad_hw), round_up(longer, self.pad_tokens)
 
     def _table_packers(self, Lp):
         tb = self._pack_tb.get(Lp)
@@ -789,12 +808,11 @@ class CapturedDistillStep(_CapturedStep):
             samples, tok, targets = batch["samples"][i], batch["tokenized"][i], batch["targets"][i]
             if not self.bucketed and (tuple(samples.tensors.shape) != (self.B, 3, *self.hw) or tuple(tok["input_ids"].shape) != (self.B, self.L)):
                 raise ValueError(f"CapturedDistillStep was built for {self.B} x 3 x {self.hw[0]} x {self.hw[1]} images and {self.L}-token captions")
-            host_t = [{k_: (v.cpu() if torch.is_tensor(v) else v) for k_, v in t.items()} for t in targets]
-            pm = batch["positive_map"][i]
+            host_t = host_targets(targets)
             masks = self.criterion.token_masks_host(host_t, tok) if self.contrastive else None
             live = {"live_tokens": int(tok["input_ids"].shape[1])} if self.bucketed else {}       # each side's OWN caption length
             out.append({"samples": samples, "tok": tok, "key": key,
-                        "targets": self._pack_st[i].pack(host_t, pm.cpu() if torch.is_tensor(pm) else pm, masks, **live),
+                        "targets": self._pack_st[i].pack(host_t, host_positive_map(batch["positive_map"][i]), masks, **live),
                         "tables": tables[i].pack(tok, host_t, batch["captions"][i])})
         return out
 
@@ -869,10 +887,6 @@ class CapturedDistillStep(_CapturedStep):
             if self.fill is not None:
                 self.cluster_criterion.check_start_status(defer=True)
         torch.cuda.current_stream().wait_stream(side)
-        self.replays += 1
-        for o in self.optimizers:
-            if hasattr(o, "note_replayed_step"):
-                o.note_replayed_step()
-        return ent["loss"]
+        return self._replayed(ent, self.optimizers)
 
     __call__ = step

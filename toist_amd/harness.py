@@ -5,7 +5,7 @@ from types import SimpleNamespace
 
 import torch
 
-from .captured import CapturedDistillStep, CapturedEvalStep, CapturedPairTrainStep, CapturedSweepStep, CapturedTrainStep  # noqa: F401
+from .captured import CapturedDistillStep, CapturedEvalStep, CapturedPairTrainStep, CapturedSweepStep, CapturedTrainStep, size_pairs  # noqa: F401
 from .transformer import TokenizedText
 
 
@@ -267,7 +267,7 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
     text = tokenized if tokenized is not None else captions
     out = {}
     for batch in batches:
-        samples, image_ids, orig = batch["samples"], list(batch["image_ids"]), CapturedEvalStep._pairs(batch["orig_sizes"])
+        samples, image_ids, orig = batch["samples"], list(batch["image_ids"]), size_pairs(batch["orig_sizes"])
         B = len(image_ids)
         if len(orig) != B or samples.tensors.shape[0] != B:
             raise ValueError(f"a batch of {samples.tensors.shape[0]} images with {B} image ids and {len(orig)} original sizes")

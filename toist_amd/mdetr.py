@@ -203,47 +203,87 @@ class MDETR(nn.Module):
         assert memory_cache is not None
         return self.decode(memory_cache)
 
+    # ---- the stages behind encode, the task sweep and encode_pairs: each is written once -------------------------
+    def _text_branch(self, captions, device):
+        """The text branch (RoBERTa + resizer) -> (EncodedText, the side stream the caller's stream still has to wait for, or None); an EncodedText
+        kept from an earlier call passes through.  The branch and the image branch (ResNet) are independent until the cross-modal encoder: under
+        engine.overlap_enabled() it is forked onto its own HIP stream, so its small GEMMs fill the tails of the backbone kernels (a parallel branch of
+        the captured hipGraph).  torch.autograd replays each node's backward on the stream of its forward, so the backward pass forks the same way;
+        functions.REJOIN tells the branch's programs which stream their backward hands over to."""
+        from .transformer import EncodedText
+        if isinstance(captions, EncodedText):
+            return captions, None
+        side = None
+        if engine.overlap_enabled():
+            main = torch.cuda.current_stream()
+            side = engine.side_stream(device, "text")
+            k.stamp("fwd.fork")
+            side.wait_stream(main)
+            functions.REJOIN = main
+        try:
+            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream()):
+                k.stamp("fwd.text.start")
+                tokenized = self.transformer._tokenize(captions, device)
+                flat, key_pad = self.transformer.encode_text(tokenized)
+                k.stamp("fwd.text.end")
+        finally:
+            functions.REJOIN = None
+        return EncodedText(tokenized, flat, key_pad), side
+
+    @staticmethod
+    def _join(side):
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+        k.stamp("fwd.join")
+
+    def _backbone_stage(self, samples, levels=(4,), premasked=(0,), stage_cuts=None):
+        k.stamp("fwd.backbone.start")
+        feats = self.backbone[0].forward_native(samples.tensors, levels, premasked=premasked, stage_cuts=stage_cuts)
+        k.stamp("fwd.backbone.end")
+        return feats
+
+    def _image_tokens(self, c5, image_mask, tail=0):
+        """NHWC C5 and the batch's pixel mask -> (tok bf16 [B, hw, d], position rows bf16 with `tail` caption rows behind each image's, mask bool [B, h, w])."""
+        B, h, w, _ = c5.shape
+        mask = nearest_mask(image_mask, (h, w))
+        pos = self.backbone[1].tokens(mask, tail=tail) if hasattr(self.backbone[1], "tokens") else \
+            self.backbone[1](NestedTensor(c5.permute(0, 3, 1, 2), mask)).flatten(2).permute(0, 2, 1).to(BF16).contiguous()
+        return self._project(c5).view(B, h * w, -1), pos, mask
+
+    def _pair_stage(self, image, text, pi, pc, out, read_status, tokenized, rows=None):
+        """One toist_sweep_assemble launch (under autograd: _PairAssembleFn) over the device tables pi / pc, the encoder over the P sequences -> memory
+        cache.  image: a sweep.SweepImages.  read_status: read the launch's status word right away.  tokenized: what the cache carries as
+        "tokenized"; None and rows (a pair_caption table): a sweep.SweepTokenized over them, built once the launch (and that read) is behind."""
+        from .sweep import SweepTokenized
+        HW, d = image.tok.shape[1:]
+        T, L = text.key_pad.shape
+        P, S = pi.numel(), HW + L
+        tokens, pos, key_pad = _PairAssembleFn.apply(image.tok, image.pos, image.mask.flatten(1), text.flat.view(T, L, d), text.key_pad, pi, pc, out,
+                                                     read_status)
+        if tokenized is None and rows is not None and text.tokenized is not None:
+            tokenized = SweepTokenized(text.tokenized, rows)
+        mask = key_pad.view(torch.bool)
+        mc = self.transformer.encode_sequences(tokens.view(P * S, d), pos.view(P * S, d), mask, P, S, L, self.query_embed.weight, tokenized,
+                                               mask[:, HW:], tokens[:, HW:])
+        mc["_native"].update(features=image.feats, cuts={}, feat_mask=image.mask, src_proj=image.tok, pair_image=pi, pair_caption=pc)
+        return mc
+
     def encode(self, samples, captions, levels=(4,)):
-        body = self.backbone[0]
-        # The text branch (RoBERTa + resizer) and the image branch (ResNet) are independent until the
-        # cross-modal encoder: fork the text branch onto its own HIP stream so its small GEMMs fill the
-        # tails of the backbone kernels (a parallel branch of the captured hipGraph).  torch.autograd
-        # replays each node's backward on the stream of its forward, so the backward pass forks the same way.
         side = None
         cuts = {}
         cut_on = getattr(self, "split_backward", False) and torch.is_grad_enabled()
         pre_encoded = isinstance(captions, tuple) and len(captions) == 3 and torch.is_tensor(captions[0])
-        fork = not pre_encoded and samples.tensors.is_cuda and engine.overlap_enabled()
         tail = captions[1].shape[0] if pre_encoded else 0           # caption tokens behind the image tokens of the cross-modal sequence
         if not pre_encoded and samples.tensors.is_cuda:
-            from .transformer import EncodedText
-            if fork:
-                main = torch.cuda.current_stream()
-                side = engine.side_stream(samples.tensors.device, "text")
-                k.stamp("fwd.fork")
-                side.wait_stream(main)
-                functions.REJOIN = main
-            try:
-                with torch.cuda.stream(side if fork else torch.cuda.current_stream()):
-                    k.stamp("fwd.text.start")
-                    tokenized = self.transformer._tokenize(captions, samples.tensors.device)
-                    flat, key_pad_text = self.transformer.encode_text(tokenized)
-                    k.stamp("fwd.text.end")
-            finally:
-                functions.REJOIN = None
-            if cut_on and flat.requires_grad:
-                leaf = flat.detach().requires_grad_(True)
-                cuts["text"] = ([flat], [leaf])
-                flat = leaf
-            captions = EncodedText(tokenized, flat, key_pad_text)
-            tail = tokenized["input_ids"].shape[1]
+            captions, side = self._text_branch(captions, samples.tensors.device)
+            if cut_on and captions.flat.requires_grad:
+                leaf = captions.flat.detach().requires_grad_(True)
+                cuts["text"] = ([captions.flat], [leaf])
+                captions = type(captions)(captions.tokenized, leaf, captions.key_pad)
+            tail = captions.tokenized["input_ids"].shape[1]
         stage_cuts = [] if cut_on else None          # data-parallel: the ResNet body runs as three programs with cuts between them
-        k.stamp("fwd.backbone.start")
-        feats = body.forward_native(samples.tensors, levels, premasked=(len(levels) - 1,), stage_cuts=stage_cuts)
-        k.stamp("fwd.backbone.end")
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-        k.stamp("fwd.join")
+        feats = self._backbone_stage(samples, levels, premasked=(len(levels) - 1,), stage_cuts=stage_cuts)
+        self._join(side)
         # Data-parallel jobs may cut the autograd graph at the outputs of the backbone and of the text encoder
         # (toist_amd.parallel.enable_backward_cuts): loss.backward() then stops there and the two long leaf programs are
         # run by backward_cut(memory_cache, name), so each gradient all-reduce can start as soon as its segment is done
@@ -255,12 +295,7 @@ class MDETR(nn.Module):
             # backward order: "backbone" (layer4, or the whole body when it ran as one program), then layer3, then stem .. layer2
             for name, y, leaf in stage_cuts or ():      # "backbone.layer2", "backbone.layer3": only the stages that produced a differentiable output
                 cuts[name] = ([y], [leaf])
-        c5 = feats[-1]
-        B, h, w, _ = c5.shape
-        mask = nearest_mask(samples.mask, (h, w))
-        pos_tok = self.backbone[1].tokens(mask, tail=tail) if hasattr(self.backbone[1], "tokens") else \
-            self.backbone[1](NestedTensor(c5.permute(0, 3, 1, 2), mask)).flatten(2).permute(0, 2, 1).to(BF16).contiguous()
-        tok = self._project(c5).view(B, h * w, -1)
+        tok, pos_tok, mask = self._image_tokens(feats[-1], samples.mask, tail)
         mc = self.transformer.encode_native(tok, pos_tok, mask.flatten(1), self.query_embed.weight, captions)
         mc["_native"]["features"] = feats
         mc["_native"]["cuts"] = cuts
@@ -283,34 +318,8 @@ class MDETR(nn.Module):
         if not isinstance(samples, NestedTensor):
             samples = NestedTensor.from_tensor_list(samples)
         self._sweep_ready(samples.tensors)
-        k.stamp("fwd.backbone.start")
-        feats = self.backbone[0].forward_native(samples.tensors, (4,), premasked=(0,))
-        k.stamp("fwd.backbone.end")
-        c5 = feats[-1]
-        B, h, w, _ = c5.shape
-        mask = nearest_mask(samples.mask, (h, w))
-        pos = self.backbone[1].tokens(mask, tail=0) if hasattr(self.backbone[1], "tokens") else \
-            self.backbone[1](NestedTensor(c5.permute(0, 3, 1, 2), mask)).flatten(2).permute(0, 2, 1).to(BF16).contiguous()
-        tok = self._project(c5).view(B, h * w, -1)
-        return SweepImages(tok, pos, mask, feats)
-
-    def _sweep_text(self, captions, device):
-        """sweep_text without the join -> (EncodedText, the side stream the caller's stream still has to wait for, or None)."""
-        from .transformer import EncodedText
-        if isinstance(captions, EncodedText):
-            return captions, None
-        side = None
-        if engine.overlap_enabled():
-            main = torch.cuda.current_stream()
-            side = engine.side_stream(device, "text")
-            k.stamp("fwd.fork")
-            side.wait_stream(main)
-        with torch.cuda.stream(side if side is not None else torch.cuda.current_stream()):
-            k.stamp("fwd.text.start")
-            tokenized = self.transformer._tokenize(captions, device)
-            flat, key_pad = self.transformer.encode_text(tokenized)
-            k.stamp("fwd.text.end")
-        return EncodedText(tokenized, flat, key_pad), side
+        feats = self._backbone_stage(samples)
+        return SweepImages(*self._image_tokens(feats[-1], samples.mask), feats)
 
     def sweep_text(self, captions, device=None):
         """The text stage: T caption strings (or a tokenized batch of T rows) -> EncodedText, reusable for any images.  Runs on the text side stream, as
@@ -319,10 +328,9 @@ class MDETR(nn.Module):
         device = torch.device(device) if device is not None else self.query_embed.weight.device
         if device.type != "cuda":
             raise RuntimeError("the task sweep needs the model on the device; there is no CPU fallback")
-        text, side = self._sweep_text(captions, device)
+        text, side = self._text_branch(captions, device)
         if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-            k.stamp("fwd.join")
+            self._join(side)
         return text
 
     def sweep_pairs(self, image_state, text, pair_image, pair_caption, out=None, tokenized=None, check=None):
@@ -333,26 +341,10 @@ class MDETR(nn.Module):
         tokenized: what the cache carries as "tokenized"; by default a sweep.SweepTokenized over the captions' rows (host tables only)."""
         from . import sweep
         self._sweep_ready(image_state.tok)
-        B, HW, d = image_state.tok.shape
-        T, L = text.key_pad.shape
-        dev = image_state.tok.device
-        on_device = torch.is_tensor(pair_image) and pair_image.is_cuda
-        if on_device:
-            pi, pc = pair_image, pair_caption
-        else:
-            pi_host, pc_host = sweep.check_tables(pair_image, pair_caption, B, T)
-            pi, pc = pi_host.to(dev, non_blocking=True), pc_host.to(dev, non_blocking=True)
-            if tokenized is None and text.tokenized is not None:
-                tokenized = sweep.SweepTokenized(text.tokenized, pc_host)
-        P = pi.numel()
-        tokens, pos, key_pad = k.sweep_assemble(image_state.tok, image_state.pos, image_state.mask.flatten(1), text.flat.view(T, L, d), text.key_pad,
-                                                pi, pc, out=out, check=on_device if check is None else check)
-        S = HW + L
-        mask = key_pad.view(torch.bool)
-        mc = self.transformer.encode_sequences(tokens.view(P * S, d), pos.view(P * S, d), mask, P, S, L, self.query_embed.weight, tokenized,
-                                               mask[:, HW:], tokens[:, HW:])
-        mc["_native"].update(features=image_state.feats, cuts={}, feat_mask=image_state.mask, src_proj=image_state.tok, pair_image=pi, pair_caption=pc)
-        return mc
+        pi, pc, pc_host = sweep.device_tables(pair_image, pair_caption, image_state.tok.shape[0], text.key_pad.shape[0], image_state.tok.device)
+        if tokenized is None and pc_host is not None and text.tokenized is not None:
+            tokenized = sweep.SweepTokenized(text.tokenized, pc_host)
+        return self._pair_stage(image_state, text, pi, pc, out, pc_host is None if check is None else check, tokenized)
 
     def encode_sweep(self, samples, captions, pairs=None):
         """sweep_images + sweep_text + sweep_pairs: the memory cache of `pairs` (a list of (image, caption) indices; default: every caption on every
@@ -368,11 +360,9 @@ class MDETR(nn.Module):
         if not isinstance(samples, NestedTensor):
             samples = NestedTensor.from_tensor_list(samples)
         self._sweep_ready(samples.tensors)
-        text, side = self._sweep_text(captions, samples.tensors.device)
+        text, side = self._text_branch(captions, samples.tensors.device)
         state = self.sweep_images(samples)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-        k.stamp("fwd.join")
+        self._join(side)
         return state, text
 
     # ---- shared-image training: P (image, caption) pairs at the cost of B image passes and T text passes, differentiable ------------
@@ -404,59 +394,14 @@ class MDETR(nn.Module):
             T = len(captions)
         else:
             T = captions["input_ids"].shape[0]
-        on_device = torch.is_tensor(pair_image) and pair_image.is_cuda
-        pc_host = None
-        if on_device:
-            pi, pc = pair_image, pair_caption
-        else:
-            pi_host, pc_host = sweep.check_tables(pair_image, pair_caption, B, T)             # ValueError before anything is launched
-            pi, pc = pi_host.to(dev, non_blocking=True), pc_host.to(dev, non_blocking=True)
-        # the text branch beside the backbone, as in encode()
-        side = None
-        if isinstance(captions, EncodedText):
-            text = captions
-        else:
-            fork = engine.overlap_enabled()
-            if fork:
-                main = torch.cuda.current_stream()
-                side = engine.side_stream(dev, "text")
-                k.stamp("fwd.fork")
-                side.wait_stream(main)
-                functions.REJOIN = main
-            try:
-                with torch.cuda.stream(side if fork else torch.cuda.current_stream()):
-                    k.stamp("fwd.text.start")
-                    tokenized = self.transformer._tokenize(captions, dev)
-                    flat, key_pad_text = self.transformer.encode_text(tokenized)
-                    k.stamp("fwd.text.end")
-            finally:
-                functions.REJOIN = None
-            text = EncodedText(tokenized, flat, key_pad_text)
-        k.stamp("fwd.backbone.start")
-        feats = self.backbone[0].forward_native(samples.tensors, (4,), premasked=(0,))
-        k.stamp("fwd.backbone.end")
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-        k.stamp("fwd.join")
-        c5 = feats[-1]
-        _, h, w, _ = c5.shape
-        mask = nearest_mask(samples.mask, (h, w))
-        pos_img = self.backbone[1].tokens(mask, tail=0) if hasattr(self.backbone[1], "tokens") else \
-            self.backbone[1](NestedTensor(c5.permute(0, 3, 1, 2), mask)).flatten(2).permute(0, 2, 1).to(BF16).contiguous()
-        tok = self._project(c5).view(B, h * w, -1)
-        HW, d = h * w, tok.shape[-1]
-        L = text.key_pad.shape[1]
-        P, S = pi.numel(), HW + L
-        read_status = (on_device if check is None else bool(check)) and not torch.cuda.is_current_stream_capturing()
-        tokens, pos, key_pad = _PairAssembleFn.apply(tok, pos_img, mask.flatten(1), text.flat.view(T, L, d), text.key_pad, pi, pc, out, read_status)
-        tokenized = None
-        if text.tokenized is not None and (pc_host is not None or read_status):
-            tokenized = sweep.SweepTokenized(text.tokenized, pc_host if pc_host is not None else pc)
-        seq_mask = key_pad.view(torch.bool)
-        mc = self.transformer.encode_sequences(tokens.view(P * S, d), pos.view(P * S, d), seq_mask, P, S, L, self.query_embed.weight, tokenized,
-                                               seq_mask[:, HW:], tokens[:, HW:])
-        mc["_native"].update(features=feats, cuts={}, feat_mask=mask, src_proj=tok, pair_image=pi, pair_caption=pc)
-        return mc
+        pi, pc, pc_host = sweep.device_tables(pair_image, pair_caption, B, T, dev)             # host tables: ValueError before anything is launched
+        text, side = self._text_branch(captions, dev)                                         # beside the backbone, as in encode()
+        feats = self._backbone_stage(samples)
+        self._join(side)
+        image = sweep.SweepImages(*self._image_tokens(feats[-1], samples.mask), feats)
+        read_status = (pc_host is None if check is None else bool(check)) and not torch.cuda.is_current_stream_capturing()
+        rows = pc_host if pc_host is not None else pc if read_status else None          # (device tables are read back only behind their status word)
+        return self._pair_stage(image, text, pi, pc, out, read_status, None, rows)
 
     def decode(self, memory_cache):
         native = memory_cache.get("_native")

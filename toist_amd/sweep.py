@@ -46,6 +46,16 @@ def check_tables(pair_image, pair_caption, n_images, n_captions):
     return torch.tensor(pi, dtype=torch.int32), torch.tensor(pc, dtype=torch.int32)
 
 
+def device_tables(pair_image, pair_caption, n_images, n_captions, device):
+    """The two pair tables as the launches take them -> (pair_image, pair_caption int32 on the device, pair_caption on the host or None).  Lists and
+    host tensors: check_tables (ValueError), then two uploads that nothing waits for.  int32 DEVICE vectors pass as they are -- the launch that
+    reads them checks them -- and the host knows nothing of them: None."""
+    if torch.is_tensor(pair_image) and pair_image.is_cuda:
+        return pair_image, pair_caption, None
+    pi, pc = check_tables(pair_image, pair_caption, n_images, n_captions)
+    return pi.to(device, non_blocking=True), pc.to(device, non_blocking=True), pc
+
+
 def pair_tables(n_images, n_captions, pairs=None, capacity=None):
     """-> (pair_image int32 [P], pair_caption int32 [P], live): the tables toist_sweep_assemble reads, on the host.
     pairs=None: the full product, image-major (p = i * n_captions + t); else the explicit list of (image, caption), in its order, repeats allowed.

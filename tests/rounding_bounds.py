@@ -70,25 +70,29 @@ def ratio(got, ref, bound):
     return float(r.max()) if r.numel() else 0.0
 
 
-def record(kernel, case, value, widen=None):
-    """{kernel, case, max err/bound, widening factor} into RECORD (one entry per kernel and case), BEFORE the assertion"""
-    os.makedirs(os.path.dirname(RECORD), exist_ok=True)
+def record(kernel, case, value, widen=None, file=None, extra=None):
+    """{kernel, case, max err/bound, widening factor} into RECORD (one entry per kernel and case), BEFORE the assertion.
+    file: another file name beside RECORD (tests/row_bounds.py: row_kernel_parity.json); extra: further fields of the entry (a measured constant)"""
+    path = RECORD if file is None else os.path.join(os.path.dirname(RECORD), file)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
     rows = {}
-    if os.path.exists(RECORD):
+    if os.path.exists(path):
         try:
-            with open(RECORD) as f:
+            with open(path) as f:
                 rows = {(r["kernel"], r["case"]): r for r in json.load(f)}
         except (ValueError, KeyError):
             rows = {}
     rows[(kernel, case)] = {"kernel": kernel, "case": case, "max_err_over_bound": round(value, 4) if value == value and value != float("inf") else str(value),
                             "acc_widen": widen if widen is not None else ACC_WIDEN.get(kernel, 1.0)}
-    with open(RECORD, "w") as f:
+    if extra:
+        rows[(kernel, case)].update(extra)
+    with open(path, "w") as f:
         f.write("[\n" + ",\n".join(json.dumps(rows[k]) for k in sorted(rows)) + "\n]\n")
     return value
 
 
-def check(kernel, case, got, ref, bound):
-    r = record(kernel, case, ratio(got, ref, bound))
+def check(kernel, case, got, ref, bound, file=None, widen=None):
+    r = record(kernel, case, ratio(got, ref, bound), widen=widen, file=file)
     assert r <= 1.0, f"{kernel} [{case}]: max err/bound {r}"
 
 

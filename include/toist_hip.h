@@ -812,6 +812,29 @@ TOIST_API int toist_coco_match(const double* iou, const int64_t* iou_offset, con
                      int n_ranges, const double* iou_thresholds, int n_thresholds, int32_t* dt_match, uint8_t* dt_ignore,
                      uint8_t* gt_range_ignore, uint8_t* gt_taken, void* stream);
 
+/* The box side of COCOeval for a whole batch of PostProcess rows in one launch (csrc/evalbox.hip; datasets/coco_eval.py:291-305 convert_to_xywh, and
+ * what pycocotools' computeIoU asks of maskApi.c bbIou): the piece between toist_postprocess and toist_coco_match.  Nothing is read from the host, so
+ * the launch can sit in a captured hipGraph.  Row r < R owns scores [Q] f32 and boxes [Q, 4] f32 (x0, y0, x1, y1) -- toist_postprocess's outputs, read in
+ * place -- and names its ground truth by row_slot[r] (int32), a slot of the STAGED ground truth of a whole evaluation: slot s owns entries
+ * [slot_off[s], slot_off[s + 1]) of gt_xywh f64 [n_gt, 4] (x, y, w, h), gt_area f64 [n_gt] and gt_crowd u8 [n_gt]; slot_off = int64 [n_slots + 1].
+ * With G = the size of the row's slot and D = min(Q, max_det) the row writes
+ *   order    int32 [R, D]: the query index of its d-th kept detection -- stable, score-descending on the scores as doubles: NaN first (in index
+ *                          order), ties (-0.0 equals 0.0) to the lower index, i.e. torch.sort(descending=True, stable=True)
+ *   dt_score f64 [R, D]  : that query's score;  dt_area f64 [R, D]: (double)(x1 - x0) * (double)(y1 - y0), the differences formed in fp32
+ *   iou      f64 [D, G] row-major at iou_off[r]: bbIou in double on (x0, y0, x1 - x0, y1 - y0) widened: da = dw * dh, ga = gw * gh,
+ *                          w = min(dw + dx, gw + gx) - max(dx, gx), h likewise, i = w * h, u = gt_crowd ? da : da + ga - i; i / u where w > 0 and h > 0, else 0
+ *   out_gt_area f64, out_gt_crowd u8 [G] at gt_off[r]: the slot's entries, contiguous per row as toist_coco_match reads them
+ * iou_off / gt_off = DEVICE int64 [R + 1], built by the host per batch (exclusive prefix sums of D * G and G).  Every element of every row's extents
+ * is written and nothing else.  The caller checks the tables on the host before the launch (slots in range, offsets that agree with the slot sizes);
+ * the kernel never uses an out-of-range row_slot entry as an index: such a row, a row whose extents disagree with its slot, and a row whose extents
+ * leave iou_cap / gt_cap (the element capacities of iou and of out_gt_area / out_gt_crowd) write order, dt_score and dt_area only.
+ * Q <= TOIST_COCO_BOXES_MAX_Q (the scores of a row sit in LDS as doubles), checked on the host. */
+#define TOIST_COCO_BOXES_MAX_Q 1024
+TOIST_API int toist_coco_boxes(const float* scores, const float* boxes, int R, int Q, int max_det, const int32_t* row_slot, const int64_t* slot_off,
+                     int n_slots, const double* gt_xywh, const double* gt_area, const uint8_t* gt_crowd, long long n_gt, const int64_t* iou_off,
+                     const int64_t* gt_off, long long iou_cap, long long gt_cap, int32_t* order, double* dt_score, double* dt_area, double* iou,
+                     double* out_gt_area, uint8_t* out_gt_crowd, void* stream);
+
 /* ---- image preparation on the device (replaces the host pipeline between the decoded uint8 image and the model's input: datasets/tdod.py:301-335,
  * datasets/transforms.py:18-59 crop, 62-80 hflip, 83-138 resize = PIL Image.resize(BILINEAR), 244-273 ToTensor / Normalize, and the padding + mask of
  * util/misc.py:185-209 NestedTensor.from_tensor_list).  One launch per batch; every size comes from the device, so the launch can sit in a captured

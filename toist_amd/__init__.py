@@ -30,6 +30,7 @@ def __getattr__(name):
         "pack_mask_bits": ("preprocess", "pack_mask_bits"), "unpack_mask_bits": ("preprocess", "unpack_mask_bits"),
         "DevicePolygonMasks": ("preprocess", "DevicePolygonMasks"), "polygon_tables": ("preprocess", "polygon_tables"),
         "convert_coco_poly_to_mask": ("coco_eval", "convert_coco_poly_to_mask"),
+        "SweepEvaluator": ("coco_eval", "SweepEvaluator"), "StagedGroundTruth": ("coco_eval", "StagedGroundTruth"),
     }
     if name in table:
         mod, attr = table[name]

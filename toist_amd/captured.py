@@ -601,6 +601,7 @@ class CapturedSweepStep(_CapturedStep):
     (pair_image[p], pair_caption[p]) -- views into the bucket's output buffers, valid until the next step of that bucket; sweep.keyed_results keys
     them.  pairs: a list of (image, caption), at most the capacity; default every caption on every image, image-major.  The tables are padded to the
     capacity with the pair (0, 0); the padded rows are computed and never handed out.
+    step_rows(...) -> (out, pair_image, pair_caption, live): the same step without the per-row dicts, out = kernels.postprocess's dict of the bucket.
     The pair tables and the per-pair size table (each pair's original (h, w), gathered by pair_image on the host) sit at fixed addresses per bucket;
     they are uploaded when they CHANGE -- the full product of a whole evaluation is uploaded once.  The graph's assemble launch checks every entry it
     reads: its status word and the XCD-resident decoder's are read after every replay, where the results are handed out (one synchronisation).  A
@@ -643,9 +644,6 @@ class CapturedSweepStep(_CapturedStep):
         outputs = self.model.decode(mc)
         ent["out"] = kernels.postprocess(outputs["pred_logits"], outputs["pred_boxes"], ent["sizes"], outputs.get("pred_isfinal"), out=ent["out"])
 
-    def _results(self, ent, live):
-        return row_results(ent["out"], self.pairs, live, self.num_queries, self.device)
-
     def _handed_out(self, ent):
         """Read the assemble launch's status word where the results are handed out (it synchronises): a refused table entry raises ValueError."""
         try:
@@ -654,8 +652,15 @@ class CapturedSweepStep(_CapturedStep):
             ent["uploaded"] = None                         # whatever the device tables hold now, the next step uploads them afresh
             raise
 
-    @torch.no_grad()
     def step(self, samples, tokenized, orig_sizes, pairs=None):
+        out, pi, pc, live = self.step_rows(samples, tokenized, orig_sizes, pairs=pairs)
+        return row_results(out, self.pairs, live, self.num_queries, self.device), pi, pc, live
+
+    @torch.no_grad()
+    def step_rows(self, samples, tokenized, orig_sizes, pairs=None):
+        """step() without the per-row dicts -> (out, pair_image, pair_caption, live): out = the bucket's kernels.postprocess dict (scores [pairs, Q],
+        boxes [pairs, Q, 4]; rows from `live` on are padding), valid until the next step of that bucket -- what a consumer that takes a whole batch
+        of rows reads in place (coco_eval.SweepEvaluator.update_rows)."""
         from . import sweep
         if isinstance(tokenized, (list, tuple)) and len(tokenized) and isinstance(tokenized[0], str):
             tokenized = self.model.transformer._tokenize(list(tokenized), self.device)
@@ -672,8 +677,8 @@ class CapturedSweepStep(_CapturedStep):
         key = self.bucket_of(samples, tokenized)
         ent = self._entry(key)
         self._fill(ent, samples, tokenized, pi, pc, sizes)
-        results = self._replay_checked(ent, lambda: self._forward(ent), lambda: self._results(ent, live), lambda: self._handed_out(ent))
-        return results, pi, pc, live
+        out = self._replay_checked(ent, lambda: self._forward(ent), lambda: ent["out"], lambda: self._handed_out(ent))
+        return out, pi, pc, live
 
     __call__ = step
 

@@ -257,8 +257,20 @@ class IouTypeEval:
 
     def __init__(self, iou_type):
         self.iouType = iou_type
-        self.records = {}                 # image id -> per-image match tables
+        self._records = {}                # image id -> per-image match tables
+        self.drain = None                 # set by a row scorer (update_rows): files the match tables that are still on their way
         self.eval, self.stats = None, None
+
+    @property
+    def records(self):
+        """image id -> per-image match tables.  Every read first files what update_rows has in flight, so a reader sees what update() would have left."""
+        if self.drain is not None:
+            self.drain()
+        return self._records
+
+    @records.setter
+    def records(self, value):
+        self._records = value
 
     def accumulate(self):
         T, R, A, M = len(IOU_THRS), len(REC_THRS), len(AREA_RNG), len(MAX_DETS)
@@ -330,6 +342,7 @@ class TDODCocoEvaluator:
             raise RuntimeError("TDODCocoEvaluator runs its IoU and matching kernels on the GPU; there is no CPU path")
         self.coco_eval = {t: IouTypeEval(t) for t in iou_types}
         self.img_ids = []
+        self._scorer, self._staged_index = None, 0           # update_rows' device state, made at its first call (or attached by a SweepEvaluator)
         self._thr = torch.from_numpy(IOU_THRS).to(self.device)
         self._rng = torch.from_numpy(AREA_RNG).to(self.device)
 
@@ -351,6 +364,37 @@ class TDODCocoEvaluator:
             if iou_type not in ("bbox", "segm"):
                 raise ValueError("Unknown iou type {}".format(iou_type))
             self._evaluate(iou_type, img_ids, predictions)
+
+    def update_rows(self, out, image_ids, live=None):
+        """update() for a whole batch of PostProcess rows in two launches (toist_coco_boxes, toist_coco_match) and without a host synchronisation:
+        out = kernels.postprocess's dict (scores f32 [rows, Q], boxes f32 [rows, Q, 4], read in place), row i belongs to image_ids[i], the first
+        `live` rows are scored (default: one per image id).  The records it files are the ones update() files for the same rows -- same keys,
+        dtypes, shapes and bytes; the first evaluation of an image id wins, also inside one batch.  The match tables travel through a
+        staging.Mailbox and become records when they have arrived, oldest first; accumulate(), synchronize_between_processes() and any read of
+        .records drain everything.  The ground truth is staged on the device at the first call (StagedGroundTruth).  Only iou_types == ["bbox"]."""
+        if self.iou_types != ["bbox"]:
+            raise ValueError(f"update_rows serves iou_types == ['bbox'] (this evaluator has {self.iou_types}): masks go through update()")
+        ids = [int(i) if torch.is_tensor(i) else i for i in image_ids]
+        live = len(ids) if live is None else int(live)
+        if not 0 <= live <= len(ids):
+            raise ValueError(f"update_rows: {live} live rows but {len(ids)} image ids")
+        ids = ids[:live]
+        scorer, t = self._row_scorer()
+        ev = self.coco_eval["bbox"]
+        scorer.score(out, scorer.staged.slots([(t, i) for i in ids]), [(ev, i) for i in ids])
+        self.img_ids.extend(sorted(set(ids)))
+
+    def _row_scorer(self):
+        """(the _RowScorer that serves update_rows, this evaluator's index in its staged ground truth): its own, made at the first call, unless a
+        SweepEvaluator attached the one its evaluators share."""
+        if getattr(self, "_scorer", None) is None:
+            self._attach(_RowScorer(StagedGroundTruth([self.coco_gt], self.device, self.cat_ids), self.device), 0)
+        return self._scorer, self._staged_index
+
+    def _attach(self, scorer, index):
+        self._scorer, self._staged_index = scorer, index
+        for ev in self.coco_eval.values():
+            ev.drain = scorer.drain
 
     def _evaluate(self, iou_type, img_ids, predictions):
         dev = self.device
@@ -469,3 +513,207 @@ def _box_iou(dt, gt, crowd):
     inter = w * h
     union = torch.where(crowd.bool()[None], da[:, None].expand_as(inter), da[:, None] + ga[None] - inter)
     return torch.where((w > 0) & (h > 0), inter / union, torch.zeros_like(inter))
+
+
+# ---- a batch of PostProcess rows scored on the device (csrc/evalbox.hip) -------------------------------------------------------------
+class StagedGroundTruth:
+    """The device image of what COCOeval.evaluateImg reads of one or several CocoGroundTruth (a sweep has one per task), built once and uploaded
+    once (staging.Staging): per annotation of the evaluated categories its bbox [x, y, w, h], its area and its crowd flag (which is also its ignore
+    flag, as _evaluate passes it), grouped into SLOTS.  Slot 0 is empty and shared by every image a ground truth does not know -- update() gives such
+    an image a record without ground truth --; then, ground truth by ground truth, one slot per image id in the order of CocoGroundTruth.img_anns,
+    holding CocoGroundTruth.annotations(image, cat_ids) in that order (an image without annotations owns an empty slot).
+      slot_off int64 [slots + 1], gt_xywh f64 [N, 4], gt_area f64 [N], gt_crowd uint8 [N] on `device` (N at least 1: a padding entry no slot names)
+      slot_sizes: numpy int64 [slots], on the host; n_gt: the annotations staged
+      slots(keys): keys = (ground-truth index, image id) pairs -> numpy int64 slot per key"""
+
+    def __init__(self, ground_truths, device, cat_ids=(1,)):
+        from . import staging
+        if isinstance(ground_truths, (CocoGroundTruth, dict)):
+            ground_truths = [ground_truths]
+        self.ground_truths = [g if isinstance(g, CocoGroundTruth) else CocoGroundTruth(g) for g in ground_truths]
+        self.device, self.cat_ids = torch.device(device), None if cat_ids is None else tuple(cat_ids)
+        self._slot, sizes, anns = {}, [0], []
+        for t, gt in enumerate(self.ground_truths):
+            for img in gt.img_anns:
+                mine = gt.annotations(img, self.cat_ids)
+                self._slot[(t, img)] = len(sizes)
+                sizes.append(len(mine))
+                anns.extend(mine)
+        self.slot_sizes, self.n_gt = np.asarray(sizes, dtype=np.int64), len(anns)
+        S, N = len(sizes), max(len(anns), 1)
+        views, total = staging.typed_views([(torch.int64, (S + 1,)), (torch.float64, (N, 4)), (torch.float64, (N,)), (torch.uint8, (N,))])
+        stage = staging.Staging(torch.zeros(total, dtype=torch.uint8), self.device)
+        slot_off, xywh, area, crowd = views(stage.open())
+        slot_off[1:] = torch.from_numpy(np.cumsum(self.slot_sizes))
+        if anns:
+            xywh[:len(anns)] = torch.tensor([a["bbox"] for a in anns], dtype=torch.float64).view(-1, 4)
+            area[:len(anns)] = torch.tensor([float(a["area"]) for a in anns], dtype=torch.float64)
+            crowd[:len(anns)] = torch.tensor([int(a.get("iscrowd", 0)) for a in anns], dtype=torch.uint8)
+        self._arena = torch.empty(total, dtype=torch.uint8, device=self.device)
+        stage.upload((self._arena, stage.host))
+        self._stage = stage                                   # (keeps the pinned buffer until the copy has left it)
+        self.slot_off, self.gt_xywh, self.gt_area, self.gt_crowd = views(self._arena)
+
+    def slots(self, keys):
+        get = self._slot.get
+        return np.fromiter((get(key, 0) for key in keys), dtype=np.int64)
+
+
+def row_tables(slots, slot_sizes, D):
+    """The host-built tables of one batch of rows for toist_coco_boxes / toist_coco_match: slots = each row's slot, slot_sizes = the staged ground
+    truth's, D = the detections kept per row -> (row_slot int32 [R], iou_off int64 [R + 1], gt_off int64 [R + 1]) as numpy arrays: exclusive prefix
+    sums of D * G_r and of G_r.  ValueError for a slot outside the staged ground truth: the check the launch relies on."""
+    slots, sizes = np.asarray(slots, dtype=np.int64).reshape(-1), np.asarray(slot_sizes, dtype=np.int64)
+    bad = np.flatnonzero((slots < 0) | (slots >= sizes.size))
+    if bad.size:
+        raise ValueError(f"row {int(bad[0])}: slot {int(slots[bad[0]])} is outside the staged ground truth's {sizes.size} slots")
+    G = sizes[slots]
+    iou_off, gt_off = np.zeros(slots.size + 1, dtype=np.int64), np.zeros(slots.size + 1, dtype=np.int64)
+    np.cumsum(G * int(D), out=iou_off[1:])
+    np.cumsum(G, out=gt_off[1:])
+    return slots.astype(np.int32), iou_off, gt_off
+
+
+class _RowScorer:
+    """What update_rows runs per batch, for one evaluator or for all of a SweepEvaluator's: the per-batch tables through one staging.Staging, the two
+    launches, and the match tables on their way to the host in a staging.Mailbox with the bookkeeping that turns them into records.  All state
+    hangs off the evaluator that owns the scorer: no process-wide cache, nothing keyed by table contents."""
+
+    def __init__(self, staged, device):
+        from . import staging
+        self.staged, self.device = staged, torch.device(device)
+        self.mail = staging.Mailbox()
+        self._meta = []                   # one entry per posted batch, oldest first: (D, [(IouTypeEval, image id, G) per row])
+        self._rows, self._stage, self._tables, self._views = 0, None, None, None
+        self._thr = torch.from_numpy(IOU_THRS).to(self.device)
+        self._rng = torch.from_numpy(AREA_RNG).to(self.device)
+
+    def _grow(self, R):
+        from . import staging
+        if R > self._rows:
+            self._views, total = staging.typed_views([(torch.int32, (R,)), (torch.int64, (R + 1,)), (torch.int64, (R + 1,)), (torch.int64, (R + 1,))])
+            self._stage = staging.Staging(torch.zeros(total, dtype=torch.uint8), self.device)
+            self._tables = torch.empty(total, dtype=torch.uint8, device=self.device)
+            self._rows = R
+
+    def score(self, out, slots, targets):
+        """Score the first len(targets) rows of `out`: slots = each row's slot (numpy), targets = each row's (IouTypeEval, image id)."""
+        scores, boxes = out["scores"], out["boxes"]
+        R = len(targets)
+        if scores.dim() != 2 or R > scores.shape[0] or len(slots) != R:
+            raise ValueError(f"update_rows: {R} rows to score, {len(slots)} slots, scores of shape {tuple(scores.shape)}")
+        D = min(int(scores.shape[1]), MAX_DETS[-1])
+        row_slot, iou_off, gt_off = row_tables(slots, self.staged.slot_sizes, D)              # ValueError before anything is launched
+        self.drain(wait=False)
+        if R == 0:
+            return
+        if not scores.is_cuda:
+            raise RuntimeError("update_rows scores its rows on the GPU (toist_coco_boxes, toist_coco_match); there is no CPU path")
+        self._grow(R)
+        h_slot, h_iou, h_gt, h_dt = self._views(self._stage.open())
+        h_slot[:R], h_iou[:R + 1], h_gt[:R + 1] = torch.from_numpy(row_slot), torch.from_numpy(iou_off), torch.from_numpy(gt_off)
+        h_dt[:R + 1] = torch.arange(R + 1, dtype=torch.int64) * D
+        self._stage.upload((self._tables, self._stage.host))
+        d_slot, d_iou, d_gt, d_dt = (v[:n] for v, n in zip(self._views(self._tables), (R, R + 1, R + 1, R + 1)))
+        st = self.staged
+        got = k.coco_boxes(scores[:R], boxes[:R], MAX_DETS[-1], d_slot, st.slot_off, st.gt_xywh, st.gt_area, st.gt_crowd, d_iou, d_gt,
+                           int(iou_off[-1]), int(gt_off[-1]))
+        dt_match, dt_ignore, gt_flag = k.coco_match(got["iou"], d_iou, got["dt_area"], d_dt, got["gt_area"], got["gt_crowd"], got["gt_crowd"], d_gt,
+                                                    self._rng, self._thr)
+        packed = torch.cat([got["dt_score"].view(torch.uint8), dt_match.view(torch.uint8), dt_ignore, gt_flag])
+        G = (gt_off[1:] - gt_off[:-1]).tolist()
+        self.post(packed, (D, [(ev, img, g) for (ev, img), g in zip(targets, G)]))
+
+    def post(self, packed, meta):
+        """Queue one batch's tables (uint8: dt_score f64 [R * D], dt_match int32 [A * T * R * D], dt_ignore [A * T * R * D], gt_flag [A * sum G]) with what
+        files them."""
+        queued = len(self.mail)
+        self.mail.post(packed)
+        if len(self.mail) != queued + 1:
+            raise RuntimeError("update_rows: the match tables could not be queued for the host (a host tensor, or a stream that is capturing)")
+        self._meta.append(meta)
+
+    def drain(self, wait=True):
+        """File the batches whose tables have arrived, oldest first (wait=True: all of them)."""
+        for host in self.mail.drain(wait=wait, ordered=True):
+            self._file(host.numpy().copy(), *self._meta.pop(0))              # (a copy: the records do not hold on to pinned memory)
+
+    @staticmethod
+    def _file(buf, D, rows):
+        A, T, R = len(AREA_RNG), len(IOU_THRS), len(rows)
+        n_dt, n_gt = R * D, sum(g for _, _, g in rows)
+        cut = np.cumsum([0, 8 * n_dt, 4 * A * T * n_dt, A * T * n_dt, A * n_gt])
+        if buf.size != cut[-1]:
+            raise RuntimeError(f"update_rows: {buf.size} bytes arrived for a batch whose tables hold {int(cut[-1])}")
+        scores, dt_match = buf[cut[0]:cut[1]].view(np.float64), buf[cut[1]:cut[2]].view(np.int32)
+        dt_ignore, gt_flag = buf[cut[2]:cut[3]].astype(bool), buf[cut[3]:cut[4]].astype(bool)
+        g0 = 0
+        for r, (ev, img, G) in enumerate(rows):
+            d0 = r * D
+            rec = {"image_id": img, "scores": scores[d0:d0 + D],
+                   "dt_match": dt_match[A * T * d0:A * T * (d0 + D)].reshape(A, T, D),
+                   "dt_ignore": dt_ignore[A * T * d0:A * T * (d0 + D)].reshape(A, T, D),
+                   "gt_ignore": gt_flag[A * g0:A * (g0 + G)].reshape(A, G)}
+            ev._records.setdefault(img, rec)                                  # first evaluation of an image wins, also inside a batch
+            g0 += G
+
+
+class SweepEvaluator:
+    """A task sweep scored on the device: one TDODCocoEvaluator(gt, ["bbox"]) per task over ONE StagedGroundTruth, all rows of a batch in two launches.
+    ground_truths = {task name: CocoGroundTruth or COCO-format dict}.  COCO-Tasks' number is mAP@0.5 per task and its mean over the tasks:
+    summarize() -> {"tasks": {name: the 12 stats}, "mAP50": mean over the tasks of stats[1], "mAP": mean of stats[0]} (plain means over every task,
+    a task without ground truth counts with pycocotools' -1)."""
+
+    def __init__(self, ground_truths, device="cuda"):
+        self.device = torch.device(device)
+        gts = {name: g if isinstance(g, CocoGroundTruth) else CocoGroundTruth(g) for name, g in ground_truths.items()}
+        if not gts:
+            raise ValueError("SweepEvaluator needs at least one task")
+        self.evaluators = {name: TDODCocoEvaluator(g, ["bbox"], device=self.device) for name, g in gts.items()}
+        self.staged = StagedGroundTruth(list(gts.values()), self.device)
+        self._scorer = _RowScorer(self.staged, self.device)
+        self._index = {name: t for t, name in enumerate(gts)}
+        for name, t in self._index.items():
+            self.evaluators[name]._attach(self._scorer, t)
+
+    def update_rows(self, out, image_ids, task_names, pair_image, pair_caption, live=None):
+        """Score the first `live` rows of out = kernels.postprocess's dict: row p is caption task_names[pair_caption[p]] on image
+        image_ids[pair_image[p]] (the tables of sweep.pair_tables / CapturedSweepStep.step_rows).  Every task named by a live row must be one of
+        this evaluator's.  No host synchronisation: see TDODCocoEvaluator.update_rows."""
+        from .sweep import _index_list
+        pi, pc = _index_list(pair_image, "pair_image"), _index_list(pair_caption, "pair_caption")
+        live = len(pi) if live is None else int(live)
+        if len(pc) != len(pi) or not 0 <= live <= len(pi):
+            raise ValueError(f"update_rows: tables of {len(pi)} and {len(pc)} pairs, {live} of them live")
+        ids = [int(i) if torch.is_tensor(i) else i for i in image_ids]
+        keys, targets, seen = [], [], {}
+        for p in range(live):
+            name = task_names[pc[p]]
+            if name not in self._index:
+                raise ValueError(f"update_rows: pair {p} names task {name!r}, which this SweepEvaluator has no ground truth for")
+            img = ids[pi[p]]
+            keys.append((self._index[name], img))
+            targets.append((self.evaluators[name].coco_eval["bbox"], img))
+            seen.setdefault(name, set()).add(img)
+        self._scorer.score(out, self.staged.slots(keys), targets)
+        for name, imgs in seen.items():
+            self.evaluators[name].img_ids.extend(sorted(imgs))
+
+    def synchronize_between_processes(self):
+        self._scorer.drain()
+        for ev in self.evaluators.values():
+            ev.synchronize_between_processes()
+
+    def accumulate(self):
+        self._scorer.drain()
+        for ev in self.evaluators.values():
+            ev.accumulate()
+
+    def summarize(self, verbose=False):
+        tasks = {}
+        for name, ev in self.evaluators.items():
+            if verbose:
+                print(f"task {name}")
+            ev.summarize(verbose)
+            tasks[name] = ev.coco_eval["bbox"].stats
+        return {"tasks": tasks, "mAP50": float(np.mean([s[1] for s in tasks.values()])), "mAP": float(np.mean([s[0] for s in tasks.values()]))}

@@ -235,7 +235,8 @@ def _captured_eval_batch(captured, batch):
 
 
 @torch.no_grad()
-def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criterion=None, captured=None, max_pairs=None, tokenized=None, observe=None):
+def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criterion=None, captured=None, max_pairs=None, tokenized=None, observe=None,
+                   evaluator=None):
     """Task-sweep inference: every task's caption on every image of every batch, at the cost of ONE image pass per image and ONE text pass per
     caption for the whole loop (the reference's loader makes one sample per (image, task): engine.py:253-342 runs the ResNet and RoBERTa once per pair).
     tasks: [(name, caption[, dataset_name])]; batches yield dicts with "samples", "image_ids", "orig_sizes" ((h, w) per image, host values) and
@@ -247,7 +248,11 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
     tasks' dataset names, and captions that answer char_to_token (strings through the model's tokenizer, or tokenized= a BatchEncoding of them).
     captured: a CapturedSweepStep built around `model` -- image stage, text stage, assembly, decode and post-processing of a batch are one graph
     replay; it takes no cluster criterion.  tokenized: the T captions already tokenized (offline use; else the strings go through the tokenizer).
-    observe: callable(memory_cache, outputs, pair_image, pair_caption) called after every eager pair stage (tests, logging)."""
+    observe: callable(memory_cache, outputs, pair_image, pair_caption) called after every eager pair stage (tests, logging).
+    evaluator: a coco_eval.SweepEvaluator holding every task's ground truth -- each pair stage's rows are scored on the device inside the loop
+    (update_rows: two launches per stage, read in place, so the captured step's reused output buffers are consumed before the next replay), no keyed
+    results are kept, and the function returns evaluator.summarize() after synchronize_between_processes() and accumulate(): {"tasks": {name: the
+    12 COCO stats}, "mAP50", "mAP"}."""
     from . import kernels, sweep
     tasks = [tuple(t) for t in tasks]
     if not tasks or any(len(t) not in (2, 3) for t in tasks):
@@ -272,6 +277,10 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
         if len(orig) != B or samples.tensors.shape[0] != B:
             raise ValueError(f"a batch of {samples.tensors.shape[0]} images with {B} image ids and {len(orig)} original sizes")
         pi, pc, live = sweep.pair_tables(B, T, batch.get("pairs"))
+        if captured is not None and evaluator is not None:
+            rows, pi, pc, live = captured.step_rows(samples, text, orig, pairs=batch.get("pairs"))
+            evaluator.update_rows(rows, image_ids, names, pi, pc, live)
+            continue
         if captured is not None:
             results, pi, pc, live = captured.step(samples, text, orig, pairs=batch.get("pairs"))
             out.update(sweep.keyed_results(results, image_ids, names, pi, pc, live))
@@ -292,9 +301,17 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
             results = postprocessor(outputs, sizes)
             if observe is not None:
                 observe(mc, outputs, gi, gc)
-            out.update(sweep.keyed_results(results, image_ids, names, gi, gc))
+            if evaluator is not None:                           # the postprocessor's rows, stacked: what kernels.postprocess's dict holds
+                rows = {"scores": torch.stack([r["scores"] for r in results]), "boxes": torch.stack([r["boxes"] for r in results])}
+                evaluator.update_rows(rows, image_ids, names, gi, gc)
+            else:
+                out.update(sweep.keyed_results(results, image_ids, names, gi, gc))
         kernels.sweep_check()     # (one 4-byte read: it synchronises) a pair table entry the launch refused
         kernels.xdec_check()      # an XCD-resident decoder launch whose groups were not co-resident
+    if evaluator is not None:
+        evaluator.synchronize_between_processes()
+        evaluator.accumulate()
+        return evaluator.summarize()
     return out
 
 

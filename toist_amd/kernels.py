@@ -1273,3 +1273,53 @@ def coco_match(iou, iou_off, dt_area, dt_off, gt_area, gt_ignore, gt_crowd, gt_o
                                            n_img, _p(area_rng, torch.float64), A, _p(thrs, torch.float64), T, _p(dt_match), _p(dt_ignore),
                                            _p(gt_flag), _p(taken), _stream()), "toist_coco_match")
     return dt_match, dt_ignore, gt_flag
+
+
+COCO_BOXES_MAX_Q = _lib.CONSTANTS["TOIST_COCO_BOXES_MAX_Q"]     # queries per row that toist_coco_boxes ranks in LDS
+
+
+def coco_boxes(scores, boxes, max_det, row_slot, slot_off, gt_xywh, gt_area, gt_crowd, iou_off, gt_off, n_iou, n_gt, out=None):
+    """The box side of COCOeval for R PostProcess rows in one launch (include/toist_hip.h: toist_coco_boxes; csrc/evalbox.hip).  scores f32 [R, Q] and
+    boxes f32 [R, Q, 4] = kernels.postprocess's buffers (or their first R rows), read in place; row_slot int32 [R]; the staged ground truth slot_off
+    int64 [slots + 1], gt_xywh f64 [N, 4], gt_area f64 [N], gt_crowd uint8 [N]; iou_off / gt_off int64 [R + 1]: everything ON THE DEVICE.  n_iou, n_gt:
+    host ints, the batch's totals iou_off[R] and gt_off[R] (they size the outputs; nothing is read back).
+    -> dict(order int32 [R, D], dt_score f64 [R * D], dt_area f64 [R * D], iou f64 [>= n_iou], gt_area f64 [>= n_gt], gt_crowd uint8 [>= n_gt]),
+    D = min(Q, max_det); `out` = such a dict to write into (fixed addresses for a captured graph; iou / gt_area / gt_crowd may be larger: a capacity).
+    The tables are the caller's to check on the host (coco_eval.row_tables); the launch writes nothing outside the rows' extents."""
+    for name, t in (("scores", scores), ("boxes", boxes), ("row_slot", row_slot), ("slot_off", slot_off), ("gt_xywh", gt_xywh), ("gt_area", gt_area),
+                    ("gt_crowd", gt_crowd), ("iou_off", iou_off), ("gt_off", gt_off)):
+        if not t.is_cuda:
+            raise RuntimeError(f"coco_boxes: {name} is a CPU tensor; the kernel runs on the GPU and there is no CPU path")
+        if not t.is_contiguous():
+            raise ValueError(f"coco_boxes: {name} must be contiguous")
+    if scores.dim() != 2 or tuple(boxes.shape) != (*scores.shape, 4):
+        raise ValueError(f"coco_boxes: scores [R, Q] and boxes [R, Q, 4] (got {tuple(scores.shape)} and {tuple(boxes.shape)})")
+    R, Q = scores.shape
+    max_det, n_iou, n_gt = int(max_det), int(n_iou), int(n_gt)
+    if Q > COCO_BOXES_MAX_Q:
+        raise ValueError(f"coco_boxes: {Q} queries per row exceed the kernel's capacity of {COCO_BOXES_MAX_Q}")
+    if max_det < 0 or n_iou < 0 or n_gt < 0:
+        raise ValueError("coco_boxes: max_det, n_iou and n_gt are non-negative")
+    D, N, dev = min(Q, max_det), gt_area.numel(), scores.device
+    if row_slot.numel() != R or iou_off.numel() != R + 1 or gt_off.numel() != R + 1 or slot_off.numel() < 2:
+        raise ValueError("coco_boxes: row_slot [R], iou_off / gt_off [R + 1] and slot_off [slots + 1] must match the rows")
+    if tuple(gt_xywh.shape) != (N, 4) or gt_crowd.numel() != N:
+        raise ValueError("coco_boxes: the staged ground truth is gt_xywh [N, 4], gt_area [N], gt_crowd [N]")
+    if out is None:
+        out = {"order": torch.empty(R, D, dtype=torch.int32, device=dev), "dt_score": torch.empty(R * D, dtype=torch.float64, device=dev),
+               "dt_area": torch.empty(R * D, dtype=torch.float64, device=dev), "iou": torch.empty(n_iou, dtype=torch.float64, device=dev),
+               "gt_area": torch.empty(n_gt, dtype=torch.float64, device=dev), "gt_crowd": torch.empty(n_gt, dtype=torch.uint8, device=dev)}
+    if any(not out[name].is_contiguous() for name in ("order", "dt_score", "dt_area", "iou", "gt_area", "gt_crowd")):
+        raise ValueError("coco_boxes: every output must be contiguous")
+    if out["order"].numel() != R * D or out["dt_score"].numel() != R * D or out["dt_area"].numel() != R * D:
+        raise ValueError(f"coco_boxes: order, dt_score and dt_area hold R * D = {R * D} elements")
+    if out["iou"].numel() < n_iou or out["gt_area"].numel() < n_gt or out["gt_crowd"].numel() != out["gt_area"].numel():
+        raise ValueError(f"coco_boxes: iou holds at least {n_iou} elements, gt_area and gt_crowd at least {n_gt} (and as many as each other)")
+    ptr = lambda t, dtype: _p(t, dtype) if t.numel() else None
+    _lib.check(_lib.lib().toist_coco_boxes(ptr(scores, torch.float32), ptr(boxes, torch.float32), R, Q, max_det, ptr(row_slot, torch.int32),
+                                           _p(slot_off, torch.int64), slot_off.numel() - 1, ptr(gt_xywh, torch.float64), ptr(gt_area, torch.float64),
+                                           ptr(gt_crowd, torch.uint8), N, _p(iou_off, torch.int64), _p(gt_off, torch.int64), out["iou"].numel(),
+                                           out["gt_area"].numel(), ptr(out["order"], torch.int32), ptr(out["dt_score"], torch.float64),
+                                           ptr(out["dt_area"], torch.float64), ptr(out["iou"], torch.float64), ptr(out["gt_area"], torch.float64),
+                                           ptr(out["gt_crowd"], torch.uint8), _stream()), "toist_coco_boxes")
+    return out

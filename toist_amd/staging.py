@@ -95,9 +95,10 @@ class Mailbox:
         ev.record()
         self._queue.append((host, ev))
 
-    def drain(self, wait=True):
+    def drain(self, wait=True, ordered=False):
         """Yield the host copies, oldest first, taking each out of the queue as it is yielded: all of them, each waited for (wait=True), or those
-        that have arrived -- the others stay queued, in order.  A caller that stops midway leaves the rest queued; clear() drops them."""
+        that have arrived -- the others stay queued, in order.  ordered: stop at the first copy that has not arrived, for an owner whose copies
+        mean something only in posting order.  A caller that stops midway leaves the rest queued; clear() drops them."""
         i = 0
         while i < len(self._queue):
             host, ev = self._queue[i]
@@ -105,6 +106,8 @@ class Mailbox:
                 del self._queue[i]
                 ev.synchronize()
                 yield host
+            elif ordered:
+                return
             else:
                 i += 1
 

@@ -835,6 +835,31 @@ TOIST_API int toist_coco_boxes(const float* scores, const float* boxes, int R, i
                      const int64_t* gt_off, long long iou_cap, long long gt_cap, int32_t* order, double* dt_score, double* dt_area, double* iou,
                      double* out_gt_area, uint8_t* out_gt_crowd, void* stream);
 
+/* The mask side of COCOeval for a whole batch of rows in one launch (csrc/evalrows.hip; datasets/coco_eval.py:307-332, and what pycocotools' computeIoU
+ * asks of maskApi.c rleIou): the piece between toist_mask_resize_pack_batch / toist_coco_boxes and a second toist_coco_match.  Nothing is read from the
+ * host, nothing is allocated and nothing synchronises, so the launch can sit in a captured hipGraph.  Row r < R owns Q column-major bit planes
+ * [w_r][ceil(h_r / 64)] (the layout of csrc/evalmask.hip) from word r * capacity_words of `bits`, plane q at + q * w_r * ceil(h_r / 64) -- the buffer
+ * toist_mask_resize_pack_batch fills; the words behind a row's Q planes are not the row's and are never read.  row_hw = int64 [R, 2] = (h, w) per row.
+ * order int32 [R, D] = toist_coco_boxes' output: the query index of the row's d-th kept detection, so "segm" ranks as "bbox" does.  The row names its
+ * ground truth by row_slot[r], a slot of the STAGED ground truth (slot_off int64 [n_slots + 1] as for toist_coco_boxes): entry n of the staged tables
+ * owns the plane at word gt_plane_off[n] of gt_bits (gt_words words in all; gt_plane_off = int64 [n_gt + 1]), its popcount gt_parea[n] (u32 -- NOT the
+ * annotation's "area") and its crowd flag gt_crowd[n]; slot_hw int32 [n_slots, 2] = the (h, w) of a slot's planes.  With G = the size of the row's slot:
+ *   dt_area f64 [R, D]  : popcount of plane order[r, d]
+ *   iou     f64 [D, G] row-major at iou_off[r]: i = popcount(dt & gt); 0.0 when i == 0, else (double)i / u with
+ *                         u = gt_crowd ? (double)area_d : (double)area_d + (double)area_g - (double)i  -- toist_mask_iou's arithmetic, exact in any order
+ * iou_off = DEVICE int64 [R + 1] (exclusive prefix sums of D * G), iou_cap = the element capacity of `iou`.  Every element of every row's extents is
+ * written and nothing else.  The caller checks the tables on the host (coco_eval.mask_row_tables); the kernel never uses an unchecked value as an
+ * index.  A row is BAD when h or w is not positive, Q * w * ceil(h / 64) exceeds capacity_words, its slot lies outside [0, n_slots), G > 0 and
+ * slot_hw differs from (h, w), its extents disagree with the slot or leave iou_cap, a plane offset leaves gt_words, or an order entry lies outside
+ * [0, Q): such a row writes dt_area only (0 for an entry whose plane it could not read) and no IoU, and reads nothing out of range.
+ * Refused on the host before any launch: null tables, negative extents, D > Q, R > 65535.  R == 0 returns 0.
+ * TOIST_COCO_MASKS_CHUNK_WORDS: the words of a detection plane one workgroup holds in LDS at a time (a plane is streamed from HBM once). */
+#define TOIST_COCO_MASKS_CHUNK_WORDS 4096
+TOIST_API int toist_coco_masks(const uint64_t* bits, long long capacity_words, const int64_t* row_hw, int R, int Q, int D, const int32_t* order,
+                     const int32_t* row_slot, const int64_t* slot_off, int n_slots, const uint64_t* gt_bits, long long gt_words,
+                     const int64_t* gt_plane_off, const int32_t* slot_hw, const uint32_t* gt_parea, const uint8_t* gt_crowd, long long n_gt,
+                     const int64_t* iou_off, long long iou_cap, double* dt_area, double* iou, void* stream);
+
 /* ---- image preparation on the device (replaces the host pipeline between the decoded uint8 image and the model's input: datasets/tdod.py:301-335,
  * datasets/transforms.py:18-59 crop, 62-80 hflip, 83-138 resize = PIL Image.resize(BILINEAR), 244-273 ToTensor / Normalize, and the padding + mask of
  * util/misc.py:185-209 NestedTensor.from_tensor_list).  One launch per batch; every size comes from the device, so the launch can sit in a captured

@@ -467,6 +467,8 @@ class CapturedEvalStep(_CapturedStep):
     pred_isfinal), with a mask head "mask_bits" int64 [Q, w_i, ceil(h_i/64)] + "mask_size" (h_i, w_i) -- TDODCocoEvaluator.update takes them unchanged.
     Every tensor is a view into the bucket's output buffers, valid until the next step of that bucket.  dense_masks=True replaces the packed planes by
     the reference's "masks" bool [Q, 1, h_i, w_i] on the host.
+    step_rows(...) -> (out, masks): the same step without the per-image dicts, out = kernels.postprocess's dict of the bucket, masks = a
+    coco_eval.RowMasks over its bit planes (None without a mask head): what TDODCocoEvaluator.update_rows(masks=) scores in place.
     orig_sizes / sizes: (h, w) per image as HOST values (lists, or host tensors): they travel to the device in one fixed-address int64 table per bucket
     that the two post-processing kernels read (csrc/postproc.hip, csrc/evalmask.hip), so nothing is read back before the launch.
 
@@ -567,8 +569,26 @@ class CapturedEvalStep(_CapturedStep):
         return results
 
     # -- the step -------------------------------------------------------------------------------------------------------------------
-    @torch.no_grad()
     def step(self, samples, tokenized, orig_sizes, sizes, dataset_names=None, captions=None):
+        return self._step(samples, tokenized, orig_sizes, sizes, dataset_names, captions, self._results)
+
+    def step_rows(self, samples, tokenized, orig_sizes, sizes, dataset_names=None, captions=None):
+        """step() without the per-image dicts -> (out, masks): out = the bucket's kernels.postprocess dict (scores [B, Q], boxes [B, Q, 4]), masks = a
+        coco_eval.RowMasks over the bucket's bit planes and the (h, w) rows of its size table (None without a mask head) -- views, valid until the
+        next step of that bucket: what a consumer that takes a whole batch of rows reads in place (TDODCocoEvaluator.update_rows(masks=), issued on
+        the stream of the step, so the next replay on that stream overwrites the rows only when they have been scored).  Not with dense_masks=True."""
+        if self.dense_masks:
+            raise ValueError("CapturedEvalStep.step_rows hands out the packed planes: build the step with dense_masks=False")
+        return self._step(samples, tokenized, orig_sizes, sizes, dataset_names, captions, self._rows)
+
+    def _rows(self, ent, orig):
+        if not self.masks:
+            return ent["out"], None
+        from .coco_eval import RowMasks
+        return ent["out"], RowMasks(ent["bits"], self.capacity_words, ent["sizes"][:2 * self.batch].view(self.batch, 2), orig)
+
+    @torch.no_grad()
+    def _step(self, samples, tokenized, orig_sizes, sizes, dataset_names, captions, results):
         if isinstance(tokenized, (list, tuple)) and len(tokenized) and isinstance(tokenized[0], str):
             if captions is None:
                 captions = list(tokenized)
@@ -586,7 +606,7 @@ class CapturedEvalStep(_CapturedStep):
             self.model.eval()
         ent = self._entry(key)
         self._fill(ent, samples, tokenized, orig, crop, dataset_names, captions)
-        return self._replay_checked(ent, lambda: self._forward(ent, key), lambda: self._results(ent, orig))
+        return self._replay_checked(ent, lambda: self._forward(ent, key), lambda: results(ent, orig))
 
     __call__ = step
 

@@ -365,30 +365,44 @@ class TDODCocoEvaluator:
                 raise ValueError("Unknown iou type {}".format(iou_type))
             self._evaluate(iou_type, img_ids, predictions)
 
-    def update_rows(self, out, image_ids, live=None):
+    def update_rows(self, out, image_ids, live=None, masks=None):
         """update() for a whole batch of PostProcess rows in two launches (toist_coco_boxes, toist_coco_match) and without a host synchronisation:
         out = kernels.postprocess's dict (scores f32 [rows, Q], boxes f32 [rows, Q, 4], read in place), row i belongs to image_ids[i], the first
         `live` rows are scored (default: one per image id).  The records it files are the ones update() files for the same rows -- same keys,
         dtypes, shapes and bytes; the first evaluation of an image id wins, also inside one batch.  The match tables travel through a
         staging.Mailbox and become records when they have arrived, oldest first; accumulate(), synchronize_between_processes() and any read of
-        .records drain everything.  The ground truth is staged on the device at the first call (StagedGroundTruth).  Only iou_types == ["bbox"]."""
-        if self.iou_types != ["bbox"]:
-            raise ValueError(f"update_rows serves iou_types == ['bbox'] (this evaluator has {self.iou_types}): masks go through update()")
+        .records drain everything.  The ground truth is staged on the device at the first call (StagedGroundTruth).
+        masks=None: only iou_types == ["bbox"].  masks = a RowMasks over the rows' bit planes (CapturedEvalStep.step_rows hands one out; RowMasks.pack
+        builds one): any iou_types within ("bbox", "segm") -- "segm" adds toist_coco_masks (the IoU block and the popcount areas of the whole batch in
+        one launch, against ground-truth planes staged once) and a second toist_coco_match.  Everything is launched on the current stream, behind
+        whatever wrote `out` and the planes there, so a replay issued afterwards on that stream overwrites them only when they have been read."""
+        if masks is None:
+            if self.iou_types != ["bbox"]:
+                raise ValueError(f"update_rows without masks serves iou_types == ['bbox'] (this evaluator has {self.iou_types}): pass masks=RowMasks, "
+                                 "or send masks through update()")
+        elif not self.iou_types or any(t not in ("bbox", "segm") for t in self.iou_types):
+            raise ValueError(f"update_rows serves iou_types within ('bbox', 'segm') (this evaluator has {self.iou_types})")
+        elif not isinstance(masks, RowMasks):
+            raise TypeError(f"update_rows: masks is a coco_eval.RowMasks (got {type(masks).__name__})")
         ids = [int(i) if torch.is_tensor(i) else i for i in image_ids]
         live = len(ids) if live is None else int(live)
         if not 0 <= live <= len(ids):
             raise ValueError(f"update_rows: {live} live rows but {len(ids)} image ids")
         ids = ids[:live]
         scorer, t = self._row_scorer()
-        ev = self.coco_eval["bbox"]
-        scorer.score(out, scorer.staged.slots([(t, i) for i in ids]), [(ev, i) for i in ids])
+        if masks is None:
+            ev = self.coco_eval["bbox"]
+            scorer.score(out, scorer.staged.slots([(t, i) for i in ids]), [(ev, i) for i in ids])
+        else:
+            scorer.score(out, scorer.staged.slots([(t, i) for i in ids]), [(self.coco_eval, i) for i in ids], masks=masks, types=tuple(self.iou_types))
         self.img_ids.extend(sorted(set(ids)))
 
     def _row_scorer(self):
         """(the _RowScorer that serves update_rows, this evaluator's index in its staged ground truth): its own, made at the first call, unless a
         SweepEvaluator attached the one its evaluators share."""
         if getattr(self, "_scorer", None) is None:
-            self._attach(_RowScorer(StagedGroundTruth([self.coco_gt], self.device, self.cat_ids), self.device), 0)
+            staged = StagedGroundTruth([self.coco_gt], self.device, self.cat_ids, planes="segm" in self.iou_types)
+            self._attach(_RowScorer(staged, self.device), 0)
         return self._scorer, self._staged_index
 
     def _attach(self, scorer, index):
@@ -524,35 +538,91 @@ class StagedGroundTruth:
     holding CocoGroundTruth.annotations(image, cat_ids) in that order (an image without annotations owns an empty slot).
       slot_off int64 [slots + 1], gt_xywh f64 [N, 4], gt_area f64 [N], gt_crowd uint8 [N] on `device` (N at least 1: a padding entry no slot names)
       slot_sizes: numpy int64 [slots], on the host; n_gt: the annotations staged
-      slots(keys): keys = (ground-truth index, image id) pairs -> numpy int64 slot per key"""
+      slots(keys): keys = (ground-truth index, image id) pairs -> numpy int64 slot per key
+    planes=True (what "segm" rows need: toist_coco_masks) also stages every annotation's mask, once: CocoGroundTruth.planes of every slot packed into
+    ONE int64 arena, with
+      gt_bits int64 [words], gt_plane_off int64 [N + 1] (word offset per annotation), slot_hw int32 [slots, 2] (the (h, w) of CocoGroundTruth.imgs; slot 0
+      and a slot without annotations of a size-less image: (0, 0)), gt_parea int32 [N] (the popcount of each plane: one kernels.mask_area per slot)
+      slot_hw_host: numpy int32 [slots, 2]; plane_bytes: the arena's size
+    The arena's size is known from the image sizes alone: above max_plane_bytes (default 8 GiB -- a guard, not a measurement: a 480 x 640 plane is
+    40 KB, so it holds about 200 000 annotations) the constructor raises ValueError naming both numbers before anything is allocated."""
 
-    def __init__(self, ground_truths, device, cat_ids=(1,)):
+    def __init__(self, ground_truths, device, cat_ids=(1,), planes=False, max_plane_bytes=8 << 30):
         from . import staging
         if isinstance(ground_truths, (CocoGroundTruth, dict)):
             ground_truths = [ground_truths]
         self.ground_truths = [g if isinstance(g, CocoGroundTruth) else CocoGroundTruth(g) for g in ground_truths]
         self.device, self.cat_ids = torch.device(device), None if cat_ids is None else tuple(cat_ids)
-        self._slot, sizes, anns = {}, [0], []
+        self._slot, sizes, anns, owners = {}, [0], [], [None]
         for t, gt in enumerate(self.ground_truths):
             for img in gt.img_anns:
                 mine = gt.annotations(img, self.cat_ids)
                 self._slot[(t, img)] = len(sizes)
                 sizes.append(len(mine))
+                owners.append((gt, img))
                 anns.extend(mine)
         self.slot_sizes, self.n_gt = np.asarray(sizes, dtype=np.int64), len(anns)
         S, N = len(sizes), max(len(anns), 1)
-        views, total = staging.typed_views([(torch.int64, (S + 1,)), (torch.float64, (N, 4)), (torch.float64, (N,)), (torch.uint8, (N,))])
+        self.has_planes, self.plane_bytes = bool(planes), 0
+        segments = [(torch.int64, (S + 1,)), (torch.float64, (N, 4)), (torch.float64, (N,)), (torch.uint8, (N,))]
+        if self.has_planes:
+            hw, plane_off = self._plane_layout(owners, N)
+            self.plane_bytes = 8 * int(plane_off[-1])
+            if self.plane_bytes > int(max_plane_bytes):
+                raise ValueError(f"StagedGroundTruth: the ground-truth planes of {len(anns)} annotations take {self.plane_bytes} bytes, above "
+                                 f"max_plane_bytes = {int(max_plane_bytes)}")
+            segments += [(torch.int64, (N + 1,)), (torch.int32, (S, 2))]
+        views, total = staging.typed_views(segments)
         stage = staging.Staging(torch.zeros(total, dtype=torch.uint8), self.device)
-        slot_off, xywh, area, crowd = views(stage.open())
+        slot_off, xywh, area, crowd = views(stage.open())[:4]
         slot_off[1:] = torch.from_numpy(np.cumsum(self.slot_sizes))
         if anns:
             xywh[:len(anns)] = torch.tensor([a["bbox"] for a in anns], dtype=torch.float64).view(-1, 4)
             area[:len(anns)] = torch.tensor([float(a["area"]) for a in anns], dtype=torch.float64)
             crowd[:len(anns)] = torch.tensor([int(a.get("iscrowd", 0)) for a in anns], dtype=torch.uint8)
+        if self.has_planes:
+            h_off, h_hw = views(stage.host)[4:]
+            h_off.copy_(torch.from_numpy(plane_off))
+            h_hw.copy_(torch.from_numpy(hw))
+            self.slot_hw_host = hw
         self._arena = torch.empty(total, dtype=torch.uint8, device=self.device)
         stage.upload((self._arena, stage.host))
         self._stage = stage                                   # (keeps the pinned buffer until the copy has left it)
-        self.slot_off, self.gt_xywh, self.gt_area, self.gt_crowd = views(self._arena)
+        self.slot_off, self.gt_xywh, self.gt_area, self.gt_crowd = views(self._arena)[:4]
+        if self.has_planes:
+            self.gt_plane_off, self.slot_hw = views(self._arena)[4:]
+            self._pack_planes(owners, hw, plane_off, N)
+
+    def _plane_layout(self, owners, N):
+        """(slot_hw int32 [slots, 2], plane_off int64 [N + 1]) from the image sizes alone: nothing is allocated on the device."""
+        hw, plane_off, n = np.zeros((len(owners), 2), dtype=np.int32), np.zeros(N + 1, dtype=np.int64), 0
+        for s, (owner, G) in enumerate(zip(owners, self.slot_sizes.tolist())):
+            im = None if owner is None else owner[0].imgs.get(owner[1])
+            if im is not None:
+                hw[s] = (int(im["height"]), int(im["width"]))
+            if G:
+                if im is None or hw[s, 0] <= 0 or hw[s, 1] <= 0:
+                    raise ValueError(f"StagedGroundTruth: image {owner[1]} has annotations but no positive height and width: its planes have no size")
+                words = int(hw[s, 1]) * ((int(hw[s, 0]) + 63) // 64)
+                plane_off[n + 1:n + G + 1] = plane_off[n] + words * np.arange(1, G + 1, dtype=np.int64)
+                n += G
+        plane_off[n + 1:] = plane_off[n]
+        return hw, plane_off
+
+    def _pack_planes(self, owners, hw, plane_off, N):
+        self.gt_bits = torch.empty(int(plane_off[-1]), dtype=torch.int64, device=self.device)
+        self.gt_parea = torch.zeros(N, dtype=torch.int32, device=self.device)
+        n = 0
+        for s, (owner, G) in enumerate(zip(owners, self.slot_sizes.tolist())):
+            if not G:
+                continue
+            h, w = int(hw[s, 0]), int(hw[s, 1])
+            planes = owner[0].planes(owner[1], self.cat_ids, self.device)
+            if tuple(planes.shape) != (G, w, (h + 63) // 64):
+                raise ValueError(f"image {owner[1]}: ground-truth planes of shape {tuple(planes.shape)}, the image is {h}x{w} with {G} annotations")
+            self.gt_bits[int(plane_off[n]):int(plane_off[n + G])] = planes.reshape(-1)
+            self.gt_parea[n:n + G] = k.mask_area(planes, h, w)
+            n += G
 
     def slots(self, keys):
         get = self._slot.get
@@ -572,6 +642,64 @@ def row_tables(slots, slot_sizes, D):
     np.cumsum(G * int(D), out=iou_off[1:])
     np.cumsum(G, out=gt_off[1:])
     return slots.astype(np.int32), iou_off, gt_off
+
+
+def mask_row_tables(slots, slot_sizes, slot_hw, row_hw, Q, capacity_words, D=None):
+    """The host check of one batch of rows for toist_coco_masks, and its tables: slots = each row's slot, slot_sizes / slot_hw = the staged ground
+    truth's (StagedGroundTruth.slot_sizes, .slot_hw_host), row_hw = each row's (h, w), Q = the planes per row, capacity_words = the words between two
+    rows' planes, D = the detections kept per row (default min(Q, MAX_DETS[-1])) -> (row_slot int32 [R], iou_off int64 [R + 1], row_hw int64 [R, 2]) as
+    numpy arrays.  ValueError for everything the launch relies on: a slot outside the staged ground truth, fewer planes than kept detections, a size
+    that is not positive (or with 2^32 pixels or more: the counts are 32-bit), planes that overflow the capacity, and a row WITH ground truth whose
+    planes are of another size than the ground truth's (a row without may be of any size, as in update())."""
+    Q, capacity_words = int(Q), int(capacity_words)
+    D = min(Q, MAX_DETS[-1]) if D is None else int(D)
+    if Q < 0 or D < 0 or Q < D:
+        raise ValueError(f"mask rows: {D} kept detections of {Q} planes per row")
+    row_slot, iou_off, _ = row_tables(slots, slot_sizes, D)
+    hw = np.asarray(row_hw, dtype=np.int64).reshape(-1, 2)
+    slot_hw = np.asarray(slot_hw, dtype=np.int64).reshape(-1, 2)
+    sizes = np.asarray(slot_sizes, dtype=np.int64)
+    if hw.shape[0] != row_slot.size or slot_hw.shape[0] != sizes.size:
+        raise ValueError(f"mask rows: {row_slot.size} slots for {hw.shape[0]} row sizes, {slot_hw.shape[0]} slot sizes for {sizes.size} slots")
+    for r in range(hw.shape[0]):
+        h, w = int(hw[r, 0]), int(hw[r, 1])
+        if h <= 0 or w <= 0 or h * w >= 1 << 32:
+            raise ValueError(f"row {r}: predicted masks of size {h}x{w}")
+        if Q * w * ((h + 63) // 64) > capacity_words:
+            raise ValueError(f"row {r}: {Q} planes of {h}x{w} take {Q * w * ((h + 63) // 64)} words, the capacity is {capacity_words}")
+        s = int(row_slot[r])
+        if sizes[s] > 0 and (int(slot_hw[s, 0]), int(slot_hw[s, 1])) != (h, w):
+            raise ValueError(f"row {r}: predicted masks are {h}x{w}, the ground truth is {int(slot_hw[s, 0])}x{int(slot_hw[s, 1])}")
+    return row_slot, iou_off, hw
+
+
+class RowMasks:
+    """The bit planes of a batch of rows where toist_coco_masks reads them: bits int64 [>= rows * capacity_words] on the device, row r's Q planes
+    [Q, w_r, ceil(h_r/64)] from word r * capacity_words; hw_dev int64 [rows, 2] = (h, w) per row on the device; hw_host = the same as a list of int
+    pairs.  CapturedEvalStep.step_rows hands out views of its bucket; pack() builds one from per-row planes."""
+
+    def __init__(self, bits, capacity_words, hw_dev, hw_host):
+        self.bits, self.capacity_words, self.hw_dev = bits, int(capacity_words), hw_dev
+        self.hw_host = [(int(h), int(w)) for h, w in hw_host]
+
+    @classmethod
+    def pack(cls, planes_list, sizes, capacity_words=None):
+        """planes_list: per row an int64 [Q, w, ceil(h/64)] device tensor (kernels.mask_pack, PostProcessSegm(packed=True)), sizes: per row (h, w)."""
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        if not planes_list or len(planes_list) != len(sizes):
+            raise ValueError(f"RowMasks.pack: {len(planes_list)} rows of planes, {len(sizes)} sizes")
+        for p, (h, w) in zip(planes_list, sizes):
+            if p.dim() != 3 or tuple(p.shape[1:]) != (w, (h + 63) // 64) or p.dtype != torch.int64:
+                raise ValueError(f"RowMasks.pack: planes of shape {tuple(p.shape)} ({p.dtype}) for a row of size {h}x{w}")
+        need = max(int(p.numel()) for p in planes_list)
+        cap = need if capacity_words is None else int(capacity_words)
+        if cap < need:
+            raise ValueError(f"RowMasks.pack: a row of {need} words, the capacity is {cap}")
+        dev = planes_list[0].device
+        bits = torch.zeros(len(sizes) * cap, dtype=torch.int64, device=dev)
+        for r, p in enumerate(planes_list):
+            bits[r * cap:r * cap + p.numel()] = p.reshape(-1)
+        return cls(bits, cap, torch.tensor(sizes, dtype=torch.int64).to(dev), sizes)
 
 
 class _RowScorer:
@@ -596,14 +724,24 @@ class _RowScorer:
             self._tables = torch.empty(total, dtype=torch.uint8, device=self.device)
             self._rows = R
 
-    def score(self, out, slots, targets):
-        """Score the first len(targets) rows of `out`: slots = each row's slot (numpy), targets = each row's (IouTypeEval, image id)."""
+    def score(self, out, slots, targets, masks=None, types=("bbox",)):
+        """Score the first len(targets) rows of `out`: slots = each row's slot (numpy), targets = each row's (IouTypeEval, image id) -- or, for several
+        `types`, ({iou type: IouTypeEval}, image id).  "segm" needs masks = the rows' RowMasks and a ground truth staged with planes=True."""
         scores, boxes = out["scores"], out["boxes"]
         R = len(targets)
         if scores.dim() != 2 or R > scores.shape[0] or len(slots) != R:
             raise ValueError(f"update_rows: {R} rows to score, {len(slots)} slots, scores of shape {tuple(scores.shape)}")
-        D = min(int(scores.shape[1]), MAX_DETS[-1])
+        Q = int(scores.shape[1])
+        D = min(Q, MAX_DETS[-1])
         row_slot, iou_off, gt_off = row_tables(slots, self.staged.slot_sizes, D)              # ValueError before anything is launched
+        segm = "segm" in types
+        if segm:
+            st = self.staged
+            if masks is None or not getattr(st, "has_planes", False):
+                raise ValueError("update_rows: 'segm' rows need masks=RowMasks and a ground truth staged with its planes (StagedGroundTruth(planes=True))")
+            if len(masks.hw_host) < R or masks.hw_dev.dim() != 2 or masks.hw_dev.shape[0] < R:
+                raise ValueError(f"update_rows: {R} rows to score, masks of {len(masks.hw_host)} rows")
+            mask_row_tables(slots, st.slot_sizes, st.slot_hw_host, masks.hw_host[:R], Q, masks.capacity_words, D)
         self.drain(wait=False)
         if R == 0:
             return
@@ -618,11 +756,21 @@ class _RowScorer:
         st = self.staged
         got = k.coco_boxes(scores[:R], boxes[:R], MAX_DETS[-1], d_slot, st.slot_off, st.gt_xywh, st.gt_area, st.gt_crowd, d_iou, d_gt,
                            int(iou_off[-1]), int(gt_off[-1]))
-        dt_match, dt_ignore, gt_flag = k.coco_match(got["iou"], d_iou, got["dt_area"], d_dt, got["gt_area"], got["gt_crowd"], got["gt_crowd"], d_gt,
-                                                    self._rng, self._thr)
-        packed = torch.cat([got["dt_score"].view(torch.uint8), dt_match.view(torch.uint8), dt_ignore, gt_flag])
         G = (gt_off[1:] - gt_off[:-1]).tolist()
-        self.post(packed, (D, [(ev, img, g) for (ev, img), g in zip(targets, G)]))
+        pick = lambda ev, t: ev[t] if isinstance(ev, dict) else ev
+        for t in types:
+            if t == "bbox":
+                iou, dt_area = got["iou"], got["dt_area"]
+            elif t == "segm":
+                mk = k.coco_masks(masks.bits, masks.capacity_words, masks.hw_dev[:R], Q, got["order"], d_slot, st.slot_off, st.gt_bits, st.gt_plane_off,
+                                  st.slot_hw, st.gt_parea, st.gt_crowd, d_iou, int(iou_off[-1]))
+                iou, dt_area = mk["iou"], mk["dt_area"]
+            else:
+                raise ValueError("Unknown iou type {}".format(t))
+            dt_match, dt_ignore, gt_flag = k.coco_match(iou, d_iou, dt_area, d_dt, got["gt_area"], got["gt_crowd"], got["gt_crowd"], d_gt, self._rng,
+                                                        self._thr)
+            packed = torch.cat([got["dt_score"].view(torch.uint8), dt_match.view(torch.uint8), dt_ignore, gt_flag])
+            self.post(packed, (D, [(pick(ev, t), img, g) for (ev, img), g in zip(targets, G)]))
 
     def post(self, packed, meta):
         """Queue one batch's tables (uint8: dt_score f64 [R * D], dt_match int32 [A * T * R * D], dt_ignore [A * T * R * D], gt_flag [A * sum G]) with what
@@ -660,6 +808,7 @@ class _RowScorer:
 
 class SweepEvaluator:
     """A task sweep scored on the device: one TDODCocoEvaluator(gt, ["bbox"]) per task over ONE StagedGroundTruth, all rows of a batch in two launches.
+    Boxes only: a sweep has no mask head, so its update_rows takes no masks and its ground truth is staged without planes.
     ground_truths = {task name: CocoGroundTruth or COCO-format dict}.  COCO-Tasks' number is mAP@0.5 per task and its mean over the tasks:
     summarize() -> {"tasks": {name: the 12 stats}, "mAP50": mean over the tasks of stats[1], "mAP": mean of stats[0]} (plain means over every task,
     a task without ground truth counts with pycocotools' -1)."""

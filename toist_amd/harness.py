@@ -221,8 +221,8 @@ def synthetic_ground_truth(batches):
     return {"images": images, "annotations": anns, "categories": [{"id": 1, "name": "preferred"}]}
 
 
-def _captured_eval_batch(captured, batch):
-    """One batch of evaluate(captured=...): forward + post-processing from the CapturedEvalStep.  The sizes are taken from batch["orig_sizes"] /
+def _captured_eval_batch(captured, batch, rows=False):
+    """One batch of evaluate(captured=...): forward + post-processing from the CapturedEvalStep (rows: step_rows' (out, masks) instead of step's dicts).  The sizes are taken from batch["orig_sizes"] /
     batch["sizes"] (host lists of (h, w), what a loader has) when present, else read back from the targets' tensors."""
     targets = batch["targets"]
     text = batch["tokenized"] if "tokenized" in batch else [t["caption"] for t in targets]
@@ -231,7 +231,8 @@ def _captured_eval_batch(captured, batch):
     names = captions = None
     if captured.cluster_criterion is not None:
         names, captions = [t["dataset_name"] for t in targets], [t["caption"] for t in targets]
-    return captured.step(batch["samples"], text, orig, sizes, dataset_names=names, captions=captions)
+    step = captured.step_rows if rows else captured.step
+    return step(batch["samples"], text, orig, sizes, dataset_names=names, captions=captions)
 
 
 @torch.no_grad()
@@ -338,7 +339,7 @@ def _sweep_groups(pair_image, pair_caption, B, T, max_pairs, product):
 
 
 @torch.no_grad()
-def evaluate(model, criterion, cluster_criterion, postprocessors, weight_dict, batches, evaluator_list, device, args, captured=None):
+def evaluate(model, criterion, cluster_criterion, postprocessors, weight_dict, batches, evaluator_list, device, args, captured=None, score_rows=False):
     """The reference's evaluation loop: per batch encode -> (prototype choice) -> decode -> losses for logging -> PostProcess
     (-> PostProcessSegm) -> evaluator.update; then gather across ranks, accumulate, summarize.  `batches` yields dicts with
     "samples", "tokenized" (or captions), "targets", "positive_map"; returns {"loss": ..., "coco_eval_bbox": [12 numbers],
@@ -346,9 +347,18 @@ def evaluate(model, criterion, cluster_criterion, postprocessors, weight_dict, b
     captured: a CapturedEvalStep built around `model` -- forward and post-processing of every batch then come from its hipGraphs (one upload + one
     graph launch per batch).  The losses for logging still need an eager forward and are computed only when `criterion` is given; with
     criterion=None the loop is graph replays + evaluator updates.  (With a cluster criterion AND a criterion the prototype choice runs twice per batch;
-    k-means restarted from converged centres leaves them where they are.)"""
+    k-means restarted from converged centres leaves them where they are.)
+    score_rows=True (needs `captured` and coco_eval.TDODCocoEvaluator evaluators; ValueError otherwise): every batch is captured.step_rows + each
+    evaluator's update_rows(out, image_ids, masks=masks) -- boxes and masks of the whole batch scored on the device, read in place on the stream of
+    the replay, no per-image dicts and no keyed results; the returned stats are the same."""
     from . import dist as tdist
     from .mdetr import weighted_total
+    if score_rows:
+        from .coco_eval import TDODCocoEvaluator
+        if captured is None or not hasattr(captured, "step_rows"):
+            raise ValueError("evaluate(score_rows=True) scores the rows a captured step leaves on the device: pass captured=CapturedEvalStep")
+        if any(not isinstance(e, TDODCocoEvaluator) for e in evaluator_list):
+            raise ValueError("evaluate(score_rows=True) needs coco_eval.TDODCocoEvaluator evaluators (update_rows)")
     model.eval()
     if criterion is not None:
         criterion.eval()
@@ -369,6 +379,12 @@ def evaluate(model, criterion, cluster_criterion, postprocessors, weight_dict, b
                 sums[name] = sums.get(name, 0.0) + float(v)
             sums["loss"] = sums.get("loss", 0.0) + float(weighted_total(loss_dict, weight_dict))
         n += 1
+        if score_rows:
+            out, masks = _captured_eval_batch(captured, batch, rows=True)
+            image_ids = [int(t["image_id"]) for t in targets]
+            for evaluator in evaluator_list:
+                evaluator.update_rows(out, image_ids, masks=masks)
+            continue
         if captured is not None:
             results = _captured_eval_batch(captured, batch)         # (reads the XCD-resident decoder's status itself before it returns)
         else:

@@ -1323,3 +1323,46 @@ def coco_boxes(scores, boxes, max_det, row_slot, slot_off, gt_xywh, gt_area, gt_
                                            ptr(out["dt_area"], torch.float64), ptr(out["iou"], torch.float64), ptr(out["gt_area"], torch.float64),
                                            ptr(out["gt_crowd"], torch.uint8), _stream()), "toist_coco_boxes")
     return out
+
+
+COCO_MASKS_CHUNK_WORDS = _lib.CONSTANTS["TOIST_COCO_MASKS_CHUNK_WORDS"]     # words of a detection plane toist_coco_masks holds in LDS at a time
+
+
+def coco_masks(bits, capacity_words, row_hw, Q, order, row_slot, slot_off, gt_bits, gt_plane_off, slot_hw, gt_parea, gt_crowd, iou_off, n_iou, out=None):
+    """The mask side of COCOeval for R rows in one launch (include/toist_hip.h: toist_coco_masks; csrc/evalrows.hip).  bits int64 [>= R *
+    capacity_words]: row r's Q planes [Q, w_r, ceil(h_r/64)] from word r * capacity_words (CapturedEvalStep's buffer); row_hw int64 [R, 2] = (h, w);
+    order int32 [R, D] = coco_boxes' ranking; row_slot int32 [R]; slot_off int64 [slots + 1]; the staged planes gt_bits int64 [words], gt_plane_off int64
+    [N + 1], slot_hw int32 [slots, 2], gt_parea int32 [N] (popcounts), gt_crowd uint8 [N]; iou_off int64 [R + 1]: everything ON THE DEVICE.  n_iou: the
+    host int iou_off[R] (it sizes the output; nothing is read back).
+    -> dict(dt_area f64 [R * D], iou f64 [>= n_iou]); `out` = such a dict to write into (fixed addresses for a captured graph; iou may be larger).
+    The tables are the caller's to check on the host (coco_eval.mask_row_tables); the launch writes nothing outside the rows' extents."""
+    for name, t in (("bits", bits), ("row_hw", row_hw), ("order", order), ("row_slot", row_slot), ("slot_off", slot_off), ("gt_bits", gt_bits),
+                    ("gt_plane_off", gt_plane_off), ("slot_hw", slot_hw), ("gt_parea", gt_parea), ("gt_crowd", gt_crowd), ("iou_off", iou_off)):
+        if not t.is_cuda:
+            raise RuntimeError(f"coco_masks: {name} is a CPU tensor; the kernel runs on the GPU and there is no CPU path")
+        if not t.is_contiguous():
+            raise ValueError(f"coco_masks: {name} must be contiguous")
+    if order.dim() != 2 or row_hw.dim() != 2 or tuple(row_hw.shape) != (order.shape[0], 2):
+        raise ValueError(f"coco_masks: order [R, D] and row_hw [R, 2] (got {tuple(order.shape)} and {tuple(row_hw.shape)})")
+    R, D = order.shape
+    Q, capacity_words, n_iou = int(Q), int(capacity_words), int(n_iou)
+    N, S, dev = gt_crowd.numel(), slot_off.numel() - 1, bits.device
+    if Q < D or capacity_words < 0 or n_iou < 0:
+        raise ValueError(f"coco_masks: {D} kept detections of {Q} queries, capacity_words = {capacity_words}, n_iou = {n_iou}")
+    if bits.numel() < R * capacity_words:
+        raise ValueError(f"coco_masks: bits holds {bits.numel()} words, {R} x {capacity_words} are needed")
+    if row_slot.numel() != R or iou_off.numel() != R + 1 or S < 1 or tuple(slot_hw.shape) != (S, 2):
+        raise ValueError("coco_masks: row_slot [R], iou_off [R + 1], slot_off [slots + 1] and slot_hw [slots, 2] must match the rows and each other")
+    if gt_plane_off.numel() != N + 1 or gt_parea.numel() != N:
+        raise ValueError("coco_masks: the staged planes are gt_plane_off [N + 1], gt_parea [N], gt_crowd [N]")
+    if out is None:
+        out = {"dt_area": torch.empty(R * D, dtype=torch.float64, device=dev), "iou": torch.empty(n_iou, dtype=torch.float64, device=dev)}
+    if not out["dt_area"].is_contiguous() or not out["iou"].is_contiguous() or out["dt_area"].numel() != R * D or out["iou"].numel() < n_iou:
+        raise ValueError(f"coco_masks: contiguous outputs, dt_area of R * D = {R * D} elements and iou of at least {n_iou}")
+    ptr = lambda t, dtype: _p(t, dtype) if t.numel() else None
+    _lib.check(_lib.lib().toist_coco_masks(ptr(bits, torch.int64), capacity_words, ptr(row_hw, torch.int64), R, Q, D, ptr(order, torch.int32),
+                                           ptr(row_slot, torch.int32), _p(slot_off, torch.int64), S, ptr(gt_bits, torch.int64), gt_bits.numel(),
+                                           ptr(gt_plane_off, torch.int64), _p(slot_hw, torch.int32), ptr(gt_parea, torch.int32), ptr(gt_crowd, torch.uint8),
+                                           N, _p(iou_off, torch.int64), out["iou"].numel(), ptr(out["dt_area"], torch.float64),
+                                           ptr(out["iou"], torch.float64), _stream()), "toist_coco_masks")
+    return out

@@ -131,6 +131,25 @@ def test_arena_growth_flushes_first_and_keeps_the_old_buffer_until_the_launch():
     assert [rd.out for rd in batches[1]] == [a.data_ptr(), b.data_ptr()]
 
 
+@pytest.mark.parametrize("capturing", [True, False])
+def test_an_arena_handed_out_under_capture_outlives_the_regrow_through_the_keep_seam(capturing):
+    kept = []
+    q = FoldQueue(launch=lambda descs: None, stream_key=lambda: 7, keep=lambda buf: (kept.append(buf) if capturing else None, buf)[1])
+    old = weakref.ref(q.acquire(1 << 26, CPU, (out_tensor(),))._base)       # the whole first arena, handed out and let go
+    assert q.acquire(1, CPU, (out_tensor(),))._base.numel() == 2 << 26      # the regrow drops the queue's reference to the first
+    assert (old() is not None) == capturing and all(buf.numel() == (1 << 26) << i for i, buf in enumerate(kept))
+    del kept[:]
+    assert old() is None
+
+
+def test_the_default_keep_seam_is_devcache_keep(monkeypatch):
+    from toist_amd import devcache
+    monkeypatch.setattr(devcache, "_capturing", lambda: True)
+    with devcache.keeping() as kept:
+        ws = FoldQueue(launch=lambda descs: None, stream_key=lambda: 7).acquire(64, CPU, (out_tensor(),))
+    assert [buf.data_ptr() for buf in kept] == [ws._base.data_ptr()]
+
+
 @pytest.mark.parametrize("kwargs", [dict(now=True), dict(when_busy="now")])
 def test_fold_at_once_launches_one_descriptor_beside_the_queue(kwargs):
     q, batches = make_queue()

@@ -18,6 +18,7 @@ from .knobs import knob
 from . import engine, functions
 from . import kernels as k
 from . import ops
+from .devcache import DeviceCache
 from .misc import NestedTensor
 from .position_encoding import build_position_encoding
 
@@ -313,7 +314,7 @@ class BackboneBase(nn.Module):
         return out
 
 
-_NEAREST_IDX = {}
+_NEAREST_IDX = DeviceCache()
 
 
 def nearest_mask(mask, hw):
@@ -321,13 +322,12 @@ def nearest_mask(mask, hw):
     (size, device) pair are computed once on the host."""
     H, W = mask.shape[-2:]
     h, w = hw
-    key = (H, W, h, w, str(mask.device))
-    idx = _NEAREST_IDX.get(key)
-    if idx is None:
+    def make():
         iy = torch.div(torch.arange(h) * H, h, rounding_mode="floor")
         ix = torch.div(torch.arange(w) * W, w, rounding_mode="floor")
-        idx = _NEAREST_IDX[key] = ((iy[:, None] * W + ix[None, :]).reshape(-1).to(mask.device),)
-    return mask.reshape(mask.shape[0], H * W).index_select(1, idx[0]).view(mask.shape[0], h, w)
+        return (iy[:, None] * W + ix[None, :]).reshape(-1).to(mask.device)
+    idx = _NEAREST_IDX.get((H, W, h, w, str(mask.device)), make)
+    return mask.reshape(mask.shape[0], H * W).index_select(1, idx).view(mask.shape[0], h, w)
 
 
 class Backbone(BackboneBase):

@@ -8,11 +8,13 @@ from collections import OrderedDict
 
 import torch
 
-from . import kernels, staging
+from . import devcache, kernels, staging
 from .misc import NestedTensor
 from .transformer import TokenizedText
 
-_NO_GRAPH = {"graph": None, "loss": None, "xdec": False}       # the capture state of a bucket entry: what _eager_then_capture sets and _void_graphs resets
+# the capture state of a bucket entry: what _eager_then_capture sets and _void_graphs resets.  kept: the devcache.Keep of the capture -- every cached
+# table and scratch buffer the graph's launches read or write, released together with the graph and never before
+_NO_GRAPH = {"graph": None, "kept": None, "loss": None, "xdec": False}
 
 
 def _is_distributed():
@@ -98,10 +100,7 @@ def row_results(out, rows, live, num_queries, device):
     """PostProcess's dict for each of the first `live` of the `rows` rows of kernels.postprocess's output `out`: views into it, and into the cached
     all-ones labels tensor of that shape."""
     from .postprocessors import PostProcess
-    lkey = (str(device), rows, num_queries)
-    labels = PostProcess._LABELS.get(lkey)
-    if labels is None:
-        labels = PostProcess._LABELS[lkey] = torch.ones(rows, num_queries, dtype=torch.int64, device=device)
+    labels = PostProcess._LABELS.get((str(device), rows, num_queries), lambda: torch.ones(rows, num_queries, dtype=torch.int64, device=device))
     results = []
     for i in range(live):
         r = {"scores": out["scores"][i], "labels": labels[i], "boxes": out["boxes"][i]}
@@ -191,7 +190,8 @@ class _CapturedStep:
         """The first batch of a bucket: body() eagerly -- a real step -- on the object's own stream, the stream the graph is captured on right afterwards,
         so that every per-stream cache of the launchers (split-K scratch, reduction arena) exists before the capture begins instead of being allocated
         inside it; then the capture of the same call sequence on the static inputs (nothing executes during capture), with the pointer tables of grouped
-        launches beside the graph: filled once, not on every replay.  upload() runs first on that stream, reset() before each of the two passes.
+        launches beside the graph: filled once, not on every replay.  The capture hits those caches, so the graph holds their tensors' addresses:
+        ent["kept"] keeps them alive beside the graph, whatever the caches evict or regrow later.  upload() runs first on that stream, reset() before each of the two passes.
         -> what the eager body() returned; what the captured one returned stays in ent["loss"]."""
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
@@ -208,10 +208,10 @@ class _CapturedStep:
                     reset()
                 launches = kernels.XDEC_LAUNCHES
                 graph = torch.cuda.CUDAGraph()
-                with kernels.tables_beside_graph():
+                with devcache.keeping() as kept, kernels.tables_beside_graph():
                     with torch.cuda.graph(graph, stream=side):
                         ent["loss"] = body()
-                ent["graph"], ent["xdec"] = graph, kernels.XDEC_LAUNCHES != launches      # xdec: the graph holds an XCD-resident launch
+                ent["graph"], ent["kept"], ent["xdec"] = graph, kept, kernels.XDEC_LAUNCHES != launches      # xdec: the graph holds an XCD-resident launch
                 self.captures += 1
         torch.cuda.current_stream().wait_stream(side)
         return result

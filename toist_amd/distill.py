@@ -7,14 +7,13 @@ replacement assignment (mdetr.py:98-103) runs on the HIP LSAP kernel instead of 
 is a handful of device tensor ops per iteration ([1024, 256] bank, 3 centres), and nothing calls `.cpu()`.
 Buffer names and shapes equal the reference's, so a reference checkpoint of the criterion loads unchanged.
 """
-import collections
-
 import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import staging
+from .devcache import DeviceCache
 from .matcher import linear_sum_assignment_batch
 
 
@@ -56,7 +55,7 @@ def span_positions(tokenized, batch_index, spans, length):
 # Caption-driven index tables of a batch (token weights, substitution masks, task columns) are built once on the host and kept on the device while the
 # batch's objects are alive: the steps that use them issue no host -> device copy and read nothing back, so the launch queue never drains inside a
 # training step (every small pageable upload is a stream synchronisation).  Keyed by object identity; the entry holds the objects, so an id cannot be reused.
-_TABLES = collections.OrderedDict()
+_TABLES = DeviceCache(limit=64, lru=True)
 
 
 def _tok_ref(tokenized):
@@ -75,15 +74,7 @@ def _cached_table(kind, refs, extra, make):
     # identity + in-place version of tensor refs: a caller that refills a static input_ids buffer in place (a captured step's feed) bumps
     # Tensor._version, so a table built for the previous contents is not served again
     key = (kind, tuple((id(r), r._version) if torch.is_tensor(r) else id(r) for r in refs), extra)
-    ent = _TABLES.get(key)
-    if ent is not None:
-        _TABLES.move_to_end(key)
-        return ent[1]
-    val = make()
-    _TABLES[key] = (refs, val)
-    while len(_TABLES) > 64:
-        _TABLES.popitem(last=False)
-    return val
+    return _TABLES.get(key, make, pin=refs)
 
 
 def span_tables(tokenized, targets, L):
@@ -343,18 +334,13 @@ class ClusterCriterion(nn.Module):
         self.feature_bank /= world
         self.cluster_centers /= world
 
-    _MEMBERS = {}
+    _MEMBERS = DeviceCache(limit=512)
 
     @staticmethod
     def _members(tasks, t, device):
         """int64 device indices of the rows whose task is t, cached per task signature (no upload in steady state)"""
-        key = (tuple(tasks), t, str(device))
-        ent = ClusterCriterion._MEMBERS.get(key)
-        if ent is None:
-            if len(ClusterCriterion._MEMBERS) > 512:
-                ClusterCriterion._MEMBERS.clear()
-            ent = ClusterCriterion._MEMBERS[key] = torch.tensor([i for i, x in enumerate(tasks) if x == t], dtype=torch.int64, device=device)
-        return ent
+        return ClusterCriterion._MEMBERS.get((tuple(tasks), t, str(device)),
+                                             lambda: torch.tensor([i for i, x in enumerate(tasks) if x == t], dtype=torch.int64, device=device))
 
     def update_memory_queue(self, feature_idx, tasks_host=None):
         """feature_idx [B, d+1]: feature | task index (-1 = none).  All ranks' rows enter every rank's bank in rank
@@ -393,7 +379,7 @@ class ClusterCriterion(nn.Module):
                 bank[cols] = torch.where(status[0] == 0, new[rows], bank[cols])
 
     # ---- device path: every sample of the batch in ONE launch, no host read (csrc/kmeans.hip) -------------------------------
-    _INDEX_TABLES = {}
+    _INDEX_TABLES = DeviceCache(limit=256)
 
     def cluster_batch(self, features, tasks):
         """memory_cluster for all samples of a batch at once.  features [B, d] (device), tasks: host list, one task index per
@@ -407,14 +393,9 @@ class ClusterCriterion(nn.Module):
         full = self._full_host()
         if any(not full[t] for _, t in live):
             return None
-        key = (tuple(tasks), str(features.device))
-        ent = ClusterCriterion._INDEX_TABLES.get(key)
-        if ent is None:
-            if len(ClusterCriterion._INDEX_TABLES) > 256:
-                ClusterCriterion._INDEX_TABLES.clear()
-            ent = ClusterCriterion._INDEX_TABLES[key] = tuple(torch.tensor(v, dtype=torch.int32, device=features.device)
-                                                              for v in task_groups([-1 if t is None else t for t in tasks]))
-        group_task, group_off, members = ent
+        group_task, group_off, members = ClusterCriterion._INDEX_TABLES.get(
+            (tuple(tasks), str(features.device)),
+            lambda: tuple(torch.tensor(v, dtype=torch.int32, device=features.device) for v in task_groups([-1 if t is None else t for t in tasks])))
         B, d = features.shape
         pick = torch.zeros(B, dtype=torch.int32, device=features.device)
         chosen = torch.zeros(B, d, dtype=torch.float32, device=features.device)
@@ -458,7 +439,7 @@ class ClusterCriterion(nn.Module):
         return center
 
     # ---- hipGraph replay for ANY batch: every per-batch index comes from a DistillTables image (fixed addresses) ----------------------------
-    _CONST = {}
+    _CONST = DeviceCache()
 
     def _static_ok(self, training=False):
         """training: the captured distillation step, which serves a run from step 0 under either memory policy (toist_bank_fifo, toist_kmeans_init) and
@@ -533,12 +514,10 @@ class ClusterCriterion(nn.Module):
         from .matcher import check_lsap_status
         B, d = rows.shape
         N, dev = self.memory_size, rows.device
-        key = ("bank", B, N, str(dev))
-        const = ClusterCriterion._CONST.get(key)
-        if const is None:
+        def make():
             slot = torch.arange(B * B, dtype=torch.int64, device=dev)
-            const = ClusterCriterion._CONST[key] = (torch.full((B,), N, dtype=torch.int32, device=dev), torch.arange(B, dtype=torch.int64, device=dev) * B, slot // B, slot % B)
-        cols, out_off, g_of, s_of = const
+            return torch.full((B,), N, dtype=torch.int32, device=dev), torch.arange(B, dtype=torch.int64, device=dev) * B, slot // B, slot % B
+        cols, out_off, g_of, s_of = ClusterCriterion._CONST.get(("bank", B, N, str(dev)), make)
         mem = tb.members.to(torch.int64)
         off = tb.group_off.to(torch.int64)
         rs = rows.index_select(0, mem).contiguous()                                  # rows in group order

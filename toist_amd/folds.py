@@ -5,6 +5,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .devcache import keep as _keep
 
 
 def _raw_stream():
@@ -28,10 +29,10 @@ class _Lane:
 
 
 class FoldQueue:
-    """launch(list of ReduceDesc) and stream_key() can be replaced so that tests run the bookkeeping without a device."""
+    """launch(list of ReduceDesc), stream_key() and keep(arena) can be replaced so that tests run the bookkeeping without a device."""
 
-    def __init__(self, launch=_launch, stream_key=_raw_stream):
-        self._launch, self._stream_key, self._lanes = launch, stream_key, {}
+    def __init__(self, launch=_launch, stream_key=_raw_stream, keep=_keep):
+        self._launch, self._stream_key, self._keep, self._lanes = launch, stream_key, keep, {}
 
     def _lane(self, device):
         key = (device, self._stream_key())
@@ -50,9 +51,9 @@ class FoldQueue:
         if lane.buf is None or lane.used + elems > lane.buf.numel():
             self.flush()                        # queued descriptors point into the old arena
             size = max(elems, 1 << 26 if lane.buf is None else 2 * lane.buf.numel())
-            lane.buf = torch.empty(size, dtype=torch.float32, device=device)
+            lane.buf = torch.empty(size, dtype=torch.float32, device=device)       # a graph that wrote the old arena keeps it
         lane.used += elems
-        return lane.buf[lane.used - elems:lane.used]
+        return self._keep(lane.buf)[lane.used - elems:lane.used]
 
     def queue(self, ws, out, splits, M, N, ldc, rscale=None, alpha=1.0, accumulate=True, keep=(), now=False, when_busy="raise"):
         """Queue out[M, N] (row stride ldc) = alpha * rscale[row] * the sum of `splits` slices [M, N] at address `ws`, in slice order (+ out when

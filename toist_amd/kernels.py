@@ -10,6 +10,7 @@ import os
 import torch
 
 from . import _lib
+from .devcache import DeviceCache, keep
 from .folds import FOLDS, _raw_stream
 from .knobs import knob
 from ._lib import (A_CONV, A_CONVT, A_KROW, A_ROWK, ACT_GELU, ACT_GELU_BWD, ACT_MASK_POS, ACT_NONE, ACT_RELU,
@@ -44,9 +45,8 @@ def _workspace(elems, device):
     key = (device, _raw_stream())  # one scratch per stream: launches on different streams overlap
     ws = _WS.get(key)
     if ws is None or ws.numel() < elems:
-        ws = torch.empty(max(elems, 1 << 22), dtype=torch.float32, device=device)
-        _WS[key] = ws
-    return ws
+        ws = _WS[key] = torch.empty(max(elems, 1 << 22), dtype=torch.float32, device=device)     # a graph that wrote the old one keeps it
+    return keep(ws)
 
 
 # ---- deferred split-K reductions -----------------------------------------------------------------------------
@@ -66,20 +66,20 @@ def flush_reductions():
 GROUP_MAX = 64
 
 
-_GROUP_TABLES = {}      # (device, rows) -> filled device table
+_GROUP_TABLES = DeviceCache(limit=1024)      # (device, rows) -> filled device table
 
 
 def group_table(rows, device):
     """Device toist_group table from host rows [a_ptr, b_ptr, c_off, rscale_off, colsum_off] (csrc/gemm.hip: the rows travel as kernel
     arguments).  Tables are kept: a training loop presents the same pointers step after step (always under hipGraph replay, nearly
     always with the caching allocator), so the 25 fill launches of a step run once -- a table filled before a capture is simply read
-    by the captured launches.  A table needed DURING a capture is filled beside the graph (see below)."""
+    by the captured launches, which keep it (devcache).  A table needed DURING a capture is filled beside the graph (see below)."""
     key = (str(device), tuple(int(v) for r in rows for v in (list(r) + [0] * (6 - len(r)))))
-    hit = _GROUP_TABLES.get(key)
-    if hit is not None:
-        return hit
-    n = len(rows)
-    flat = (ctypes.c_int64 * (6 * n))(*key[1])
+    return _GROUP_TABLES.get(key, lambda: _fill_group_table(key[1], len(rows), device))
+
+
+def _fill_group_table(values, n, device):
+    flat = (ctypes.c_int64 * (6 * n))(*values)
     if torch.cuda.is_current_stream_capturing() and FILL_TABLES_OUTSIDE_GRAPH:
         # The pointers in `rows` are fixed for the life of the graph being captured, so the table is filled NOW, by a launch on a
         # stream that is not capturing, instead of by a kernel node that would re-write the same 48 bytes per row on every replay
@@ -94,10 +94,6 @@ def group_table(rows, device):
             return dev
     dev = torch.empty(n, 6, dtype=torch.int64, device=device)
     _lib.check(_lib.lib().toist_group_fill(ctypes.cast(flat, ctypes.c_void_p), n, _p(dev), _stream()), "toist_group_fill")
-    if not torch.cuda.is_current_stream_capturing():
-        if len(_GROUP_TABLES) >= 1024:
-            _GROUP_TABLES.clear()
-        _GROUP_TABLES[key] = dev
     return dev
 
 
@@ -108,14 +104,13 @@ FILL_TABLES_OUTSIDE_GRAPH = False
 _TABLE_ARENAS = {}      # device -> [int64 tensor [rows, 6] allocated outside any capture, rows used]
 _TABLE_ARENA_ROWS = 1 << 16     # 3 MB: ~2000 tables of 32 problems
 _FILL_STREAMS = {}
-_RETIRED_ARENAS = []
 
 
 def _arena_table(dev_key, n):
     ar = _TABLE_ARENAS.get(dev_key)
     if ar is None or ar[1] + n > ar[0].shape[0]:
         return None
-    t = ar[0][ar[1]:ar[1] + n]
+    t = keep(ar[0])[ar[1]:ar[1] + n]       # a graph that took tables from an arena keeps that arena
     ar[1] += n
     return t
 
@@ -125,8 +120,6 @@ def _arena_prepare(device):
     key = str(device)
     ar = _TABLE_ARENAS.get(key)
     if ar is None or ar[1] + 4096 > ar[0].shape[0]:
-        if ar is not None:
-            _RETIRED_ARENAS.append(ar[0])       # captured graphs read their tables from it for as long as they live
         _TABLE_ARENAS[key] = [torch.empty(_TABLE_ARENA_ROWS, 6, dtype=torch.int64, device=device), 0]
 
 

@@ -10,6 +10,7 @@ from torch import nn
 
 from . import kernels as k
 from . import staging
+from .devcache import DeviceCache
 
 TOKEN_MASK_WORDS = 4      # 64-bit words of a target's token-span mask: 256 tokens = the reference's max_text_len (csrc/contrastive.hip: CA_MW)
 
@@ -44,7 +45,7 @@ class MatchResult:
         return [(s[a:b].clone(), t[a:b].clone()) for a, b in zip(self.match_off[:-1], self.match_off[1:])]
 
 
-_ARANGES = {}
+_ARANGES = DeviceCache()
 
 
 def pair_slots(match_off, L, B, cap):
@@ -53,9 +54,7 @@ def pair_slots(match_off, L, B, cap):
     [match_off[i], match_off[i + 1]) holds j, match_off as int64), the first four [L * cap]; dead slots carry clamped, in-range values.  No shape or launch
     parameter depends on the batch's counts, so the same launches serve a StaticTargets image (cap = its capacity) and a list-path MatchResult (cap = Mtot)."""
     dev = match_off.device
-    p = _ARANGES.get((L * cap, str(dev)))
-    if p is None:
-        p = _ARANGES[(L * cap, str(dev))] = torch.arange(L * cap, dtype=torch.int64, device=dev)
+    p = _ARANGES.get((L * cap, str(dev)), lambda: torch.arange(L * cap, dtype=torch.int64, device=dev))
     mo = match_off.to(torch.int64)
     mtot = mo[B]
     if L == 1:
@@ -243,7 +242,7 @@ class HungarianMatcher(nn.Module):
         super().__init__()
         self.cost_class, self.cost_bbox, self.cost_giou = cost_class, cost_bbox, cost_giou
         assert cost_class != 0 or cost_bbox != 0 or cost_giou != 0, "all costs cant be 0"
-        self._offsets = {}
+        self._offsets = DeviceCache(limit=64)
 
     @torch.no_grad()
     def match_layers(self, logits, boxes, targets, positive_map):
@@ -255,16 +254,11 @@ class HungarianMatcher(nn.Module):
         res_counts = [min(Q, s) for s in sizes]
         # prefix sums live on the device; cached per batch signature so a steady-state step issues no
         # host->device copy (and stays hipGraph-capturable)
-        key = (tuple(sizes), Q, str(dev))
-        ent = self._offsets.get(key)
-        if ent is None:
-            if len(self._offsets) > 64:
-                self._offsets.clear()
+        def make():
             tgt_off = torch.tensor([0] + [sum(sizes[:i + 1]) for i in range(B)], dtype=torch.int32)
             m_off = torch.tensor([0] + [sum(res_counts[:i + 1]) for i in range(B)], dtype=torch.int32)
-            ent = (tgt_off.to(dev), m_off.to(dev), int(m_off[-1]), int(tgt_off[-1]))
-            self._offsets[key] = ent
-        tgt_off, m_off, mtot, ttot = ent
+            return tgt_off.to(dev), m_off.to(dev), int(m_off[-1]), int(tgt_off[-1])
+        tgt_off, m_off, mtot, ttot = self._offsets.get((tuple(sizes), Q, str(dev)), make)
         src = torch.zeros(L, max(mtot, 1), dtype=torch.int64, device=dev)[:, :mtot]
         tgt = torch.zeros(L, max(mtot, 1), dtype=torch.int64, device=dev)[:, :mtot]
         status = torch.zeros(L * B, dtype=torch.int32, device=dev)
@@ -301,21 +295,17 @@ def build_matcher(args):
     return HungarianMatcher(cost_class=args.set_cost_class, cost_bbox=args.set_cost_bbox, cost_giou=args.set_cost_giou)
 
 
-_LSAP_META = {}
+_LSAP_META = DeviceCache(limit=64)
 
 
 def _lsap_meta(shapes, offsets, dev):
     """Device copies of the per-problem tables, cached per signature (a steady-state step uploads nothing)."""
-    key = (tuple(shapes), tuple(offsets), str(dev))
-    ent = _LSAP_META.get(key)
-    if ent is None:
-        if len(_LSAP_META) > 64:
-            _LSAP_META.clear()
+    def make():
         pairs = [min(r, c) for r, c in shapes]
         out_off = [sum(pairs[:i]) for i in range(len(pairs))]
-        ent = _LSAP_META[key] = (torch.tensor(list(offsets), dtype=torch.int64, device=dev), torch.tensor([r for r, _ in shapes], dtype=torch.int32, device=dev),
-                                 torch.tensor([c for _, c in shapes], dtype=torch.int32, device=dev), torch.tensor(out_off, dtype=torch.int64, device=dev), out_off, pairs)
-    return ent
+        return (torch.tensor(list(offsets), dtype=torch.int64, device=dev), torch.tensor([r for r, _ in shapes], dtype=torch.int32, device=dev),
+                torch.tensor([c for _, c in shapes], dtype=torch.int32, device=dev), torch.tensor(out_off, dtype=torch.int64, device=dev), out_off, pairs)
+    return _LSAP_META.get((tuple(shapes), tuple(offsets), str(dev)), make)
 
 
 _LSAP_MAIL = staging.Mailbox()      # the status vectors of deferred checks on their way to the host

@@ -15,6 +15,7 @@ from torch import nn
 from . import dist, engine, functions, matcher, staging
 from . import kernels as k
 from .backbone import build_backbone, nearest_mask
+from .devcache import DeviceCache
 from .matcher import StaticTargets, build_matcher, pair_slots
 from .misc import NestedTensor
 from .transformer import build_transformer
@@ -726,13 +727,16 @@ def _nsthl2(feats_noun, feats_sth, keep):
     return (diff ** 2).mean(1).sum() / keep.sum().clamp(min=1)
 
 
+_INDEX_CACHE = DeviceCache(limit=128)       # constant index tables (functions of shapes alone), kept on the device
+
+
 def _softkd_tables(L, B, Q, dev):
     """Constant tables of the L * B LSAP problems with Q pair slots each: slot, layer and image of every slot; cost offset and first slot of every problem."""
     def make():
         s = torch.arange(L * B * Q, dtype=torch.int64, device=dev)
         prob = s // Q
         return (s % Q, prob // B, prob % B, torch.arange(L * B, dtype=torch.int64, device=dev) * (Q * Q), torch.arange(L * B, dtype=torch.int64, device=dev) * Q)
-    return _cached(("softkd", L, B, Q, str(dev)), make)
+    return _INDEX_CACHE.get(("softkd", L, B, Q, str(dev)), make)
 
 
 def _softkd(noun, sth, match_off, cap, solve=None):
@@ -819,19 +823,6 @@ def _paired_giou_matrix(a, b):
     return iou - (area - union) / area
 
 
-_INDEX_CACHE = {}
-
-
-def _cached(key, make):
-    """Constant index tables (functions of shapes alone), kept on the device."""
-    ent = _INDEX_CACHE.get(key)
-    if ent is None:
-        if len(_INDEX_CACHE) > 128:
-            _INDEX_CACHE.clear()
-        ent = _INDEX_CACHE[key] = make()
-    return ent
-
-
 def _layer_key(name, l, L):
     """The reference's key of decoder layer l of L: the main (last) layer keeps the bare name, auxiliary layer l gets the suffix _l (mdetr.py:1009-1019)."""
     return name if l == L - 1 else f"{name}_{l}"
@@ -865,7 +856,14 @@ class LossDict(dict):
         return self
 
 
-_WEIGHT_VECTORS = {}
+_WEIGHT_VECTORS = DeviceCache()
+
+
+def _weight_vector(n, weights, device):
+    host = torch.zeros(n, dtype=torch.float32)
+    for i, v in weights:
+        host[i] = v
+    return host.to(device)
 
 
 def weighted_total(loss_dict, weight_dict):
@@ -877,12 +875,7 @@ def weighted_total(loss_dict, weight_dict):
         covered.update(index)
         if not key[2]:           # none of the group's keys is weighted: no term (and no backward pass through the group's graph for a sum of zeros)
             continue
-        w = _WEIGHT_VECTORS.get(key)
-        if w is None:
-            host = torch.zeros(flat.numel(), dtype=torch.float32)
-            for i, v in key[2]:
-                host[i] = v
-            w = _WEIGHT_VECTORS[key] = host.to(flat.device)
+        w = _WEIGHT_VECTORS.get(key, lambda: _weight_vector(flat.numel(), key[2], flat.device))
         term = (flat.float() * w).sum()        # (torch.dot would put a rocBLAS launch into the replayed step)
         total = term if total is None else total + term
     for k_, v in loss_dict.items():

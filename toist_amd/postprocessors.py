@@ -10,6 +10,7 @@ from torch import nn
 
 from . import box_ops
 from . import kernels as k
+from .devcache import DeviceCache
 
 
 class PostProcess(nn.Module):
@@ -32,7 +33,7 @@ class PostProcess(nn.Module):
                 r["scores_refexp"] = s
         return results
 
-    _LABELS = {}
+    _LABELS = DeviceCache()
 
     @torch.no_grad()
     def forward_static(self, outputs, sizes_dev, out=None):
@@ -42,10 +43,7 @@ class PostProcess(nn.Module):
         logits = outputs["pred_logits"]
         B, Q = logits.shape[:2]
         got = k.postprocess(logits, outputs["pred_boxes"], sizes_dev, outputs.get("pred_isfinal"), out=out)
-        key = (str(logits.device), B, Q)
-        labels = PostProcess._LABELS.get(key)
-        if labels is None:
-            labels = PostProcess._LABELS[key] = torch.ones(B, Q, dtype=torch.int64, device=logits.device)
+        labels = PostProcess._LABELS.get((str(logits.device), B, Q), lambda: torch.ones(B, Q, dtype=torch.int64, device=logits.device))
         results = [{"scores": got["scores"][i], "labels": labels[i], "boxes": got["boxes"][i]} for i in range(B)]
         if "scores_refexp" in got:
             for i, r in enumerate(results):

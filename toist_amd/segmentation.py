@@ -20,6 +20,7 @@ from . import engine, functions
 from . import kernels as k
 from . import ops
 from .backbone import nearest_mask
+from .devcache import DeviceCache
 from .matcher import pair_slots
 from .misc import NestedTensor
 
@@ -88,16 +89,13 @@ class _MatchedRows:
         self.version = -1
 
 
-_ZERO = {}
+_ZERO = DeviceCache()
 
 
 def _zero_sentinel(dev):
     """One f32 zero per device.  `z.expand(shape)` is the gradient autograd carries when only the matched rows are non-zero: no kernel ever
     reads or writes it (the 82 MB `zeros_like(pred)` of round 5 is gone), and anything autograd adds to it lands in a NEW dense tensor."""
-    z = _ZERO.get(str(dev))
-    if z is None:
-        z = _ZERO[str(dev)] = torch.zeros(1, dtype=torch.float32, device=dev)
-    return z
+    return _ZERO.get(str(dev), lambda: torch.zeros(1, dtype=torch.float32, device=dev))
 
 
 def _krsc_bf16(w):

@@ -6,7 +6,7 @@ key_pad [B, S] (non-zero = padding) and per layer a dict with the 18 parameter t
 norm1 branch, cross-attention, norm3 branch, hidden, norm4 branch).  Every tensor the launch saves comes back under the descriptor's field name,
 stacked over the layers.  Row statistics of the attentions are (maximum of the raw dot products over live keys, 1 / sum exp(scale (s - max))).
 
-Dropout masks are the kernels' two counter hashes restated in integer torch ops: `pair_hash` (csrc/attn2.hip: one 32-bit value per two adjacent keys
+Dropout masks are the kernels' two counter hashes restated in integer torch ops: `pair_hash` (csrc/common.h: one 32-bit value per two adjacent keys
 of a score row, pair index (row * round8(Sk) + key) >> 1) and `hash_u32` (csrc/common.h: element m * 256 + n of a [M, 256] tensor, m * 2048 + n of
 the hidden activations).
 
@@ -34,7 +34,7 @@ PARAMS = ("w_in", "b_in", "w_os", "b_os", "g1", "be1", "w_q", "b_q", "w_oc", "b_
 
 # ------------------------------------------------------------------------------------------------------------------ dropout hashes
 def pair_hash(pair, seed):
-    """csrc/attn2.hip pair_hash in int64 arithmetic (values kept below 2^32)"""
+    """csrc/common.h pair_hash in int64 arithmetic (values kept below 2^32)"""
     s0 = seed & M32
     s1 = ((seed >> 32) ^ ((seed & M32) * 0x9E3779B9)) & M32
     a = (pair ^ s0) & M32

@@ -172,7 +172,7 @@ def a2_inputs(Sq, Sk, p, pad):
 
 
 def a2_keep(BH, Sq, Sk, p, seed, ld=None):
-    """keep mask [BH, Sq, Sk] of csrc/attn2.hip from oracle.xdec_ref.pair_hash: element row * round8(Sk) + key, one hash per element pair, the 16-bit
+    """keep mask [BH, Sq, Sk] of csrc/attn2.hip from oracle.xdec_ref.pair_hash (csrc/common.h pair_hash): element row * round8(Sk) + key, one hash per element pair, the 16-bit
     field of the element's parity >= round(p * 2^16).  ld: another row pitch (a mutant of the emulation)"""
     if p <= 0:
         return torch.ones(BH, Sq, Sk, dtype=torch.bool)

@@ -21,53 +21,7 @@
 // (row maximum, 1 / row sum): P = exp2((s - m) c) / sum, the expression of the forward pass, and the keep mask from the same hash.
 #include "common.h"
 
-#include <type_traits>
-
 namespace toist {
-
-namespace {
-
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
-
-constexpr float LOG2E = 1.4426950408889634f;
-
-// One 32-bit hash decides two adjacent keys of a score row: element (row, key) -> pair (row * ld + key) >> 1, field key & 1 (bits 0-15 /
-// 16-31), kept when field >= round(p * 65536).  Two multiply rounds on the full-rate 24-bit multiplier (v_mad_u32_u24; a 32-bit
-// v_mul_lo_u32 occupies the vector pipe four times as long); keep rate, field / neighbour / stride correlations measured in
-// tools/r4/hash_quality.py.
-__device__ __forceinline__ unsigned pair_hash(unsigned pair, unsigned s0, unsigned s1) {
-    unsigned a = pair ^ s0;
-    a ^= a >> 12;               // the 24-bit multiply below only sees bits 0-23: fold the upper bits in first (pairs 2^24 apart otherwise share 99.9 % of their masks)
-    unsigned h = __umul24(a, 0x9E3779u) + s1;
-    h ^= h >> 15;
-    h = __umul24(h, 0x85EBCBu) + (a >> 8);
-    h ^= h >> 13;
-    return h;
-}
-
-__device__ __forceinline__ bf16x8_t tr_pair(const bf16_t* lo_ptr, const bf16_t* hi_ptr) {
-    const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)lo_ptr);
-    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)hi_ptr);
-    return __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
-__device__ __forceinline__ bf16x8_t frag_of(unsigned a, unsigned b, unsigned c, unsigned d) {
-    const u32x4_t u = {a, b, c, d};
-    return __builtin_bit_cast(bf16x8_t, u);
-}
-
-template <int N, typename F>
-__device__ __forceinline__ void unrolled(F&& f) {
-    if constexpr (N > 0) {
-        unrolled<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
-}  // namespace
 
 constexpr int A2_SKB = 512;     // keys staged in LDS at a time (forward)
 

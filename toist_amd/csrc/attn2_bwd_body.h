@@ -1,41 +1,16 @@
 // Body of the key-owning attention backward (see csrc/attn2.hip for the algorithm): shared by attn2_bwd_kernel (one launch per attention block)
 // and by the XCD-resident decoder backward of csrc/xdec.hip, which runs it as a phase of a persistent launch -- workgroup = (head, key split)
 // of ONE image, `a2_smem` = a region of the launch's LDS, FRESH_DCTX = the context gradient was written by another CU of the same launch.
-// Include inside namespace toist, after bf16_t / bf16x8_t / f32x4_t / pack2bf are visible.
+// Include inside namespace toist, after common.h: the vector types, LOG2E, pack2bf, pair_hash (the forward's own), tr_pair and frag_of come from there.
 #pragma once
 
 namespace a2b {
 
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
-
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int A2_TS = 24;      // row stride (bf16) of a wave's [32 keys][16 queries] dS tile
 constexpr int A2_KS = 40;      // row stride (bf16) of a wave's [32 keys][32 features] K tile (start-up transpose)
 constexpr int A2_NG = 2;       // query groups per workgroup: tiles are dealt round-robin to A2_NG sets of four waves (two waves per SIMD)
 constexpr size_t A2_BWD_LDS = (size_t)A2_NG * 2 * 32 * 32 * 2 * 2 + (size_t)A2_NG * 4 * 2 * 32 * A2_TS * 2 + (size_t)A2_NG * 2 * 32 * 4 + (size_t)A2_NG * 2 * 64 * 4 +
                               (size_t)A2_NG * 2 * 4 * 32 * 32 * 4;
-
-__device__ __forceinline__ unsigned pair_hash(unsigned pair, unsigned s0, unsigned s1) {
-    unsigned a = pair ^ s0;
-    a ^= a >> 12;               // the 24-bit multiply below only sees bits 0-23: fold the upper bits in first (pairs 2^24 apart otherwise share 99.9 % of their masks)
-    unsigned h = __umul24(a, 0x9E3779u) + s1;
-    h ^= h >> 15;
-    h = __umul24(h, 0x85EBCBu) + (a >> 8);
-    h ^= h >> 13;
-    return h;
-}
-__device__ __forceinline__ bf16x8_t tr_pair(const bf16_t* lo_ptr, const bf16_t* hi_ptr) {
-    const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)lo_ptr);
-    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)hi_ptr);
-    return __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-__device__ __forceinline__ bf16x8_t frag_of(unsigned a, unsigned b, unsigned c, unsigned d) {
-    const u32x4_t u = {a, b, c, d};
-    return __builtin_bit_cast(bf16x8_t, u);
-}
 
 template <bool FRESH_DCTX>
 __device__ __forceinline__ void attn2_bwd_body(unsigned char* const a2_smem, const int split, const int bh,

@@ -23,18 +23,6 @@ static constexpr int CA_MAX_TOK = 64 * CA_MW;   // 256 = the reference's max_tex
 static constexpr int CA_LDS_MAX = 160 * 1024 - 256;   // dynamic LDS the kernels may ask for (they also hold a few static words)
 static constexpr int CA_STAGE_TOK = 128; // token projections are staged in LDS up to this many tokens, read from L2 beyond (LDS: Q x T f32 logits)
 
-__device__ __forceinline__ float ca_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < CA_THREADS / 64; ++i) t += red[i];
-    return t;
-}
-
 // LIVE: the launch sits in a replayed graph whose captions are padded to Tpad tokens; *live_tokens (a device word refilled between replays) says how many
 // of them the batch really has.  T = clamp(*live_tokens, 0, Tpad) then takes the place of the token count in every loop below -- the launch computes
 // what the launch on proj_tokens[:, :T] computes, in the same order -- and the dead rows of the token gradient are written as zeros.  The LDS layout
@@ -132,7 +120,7 @@ __global__ __launch_bounds__(CA_THREADS) void contrastive_kernel(
     }
     const float inv_nb = 1.f / num_boxes[0];
     if (MODE == 0) {
-        const float tot = ca_block_sum(part, red);
+        const float tot = block_sum<CA_THREADS>(part, red);
         if (tid == 0) atomicAdd(losses + l, 0.5f * tot * inv_nb);
         return;
     }

@@ -13,18 +13,6 @@ namespace toist {
 
 static constexpr int CRIT_THREADS = 1024;   // 16 waves, one query per wave at a time (the kernel is latency-bound: 48 blocks)
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < CRIT_THREADS / 64; ++i) t += red[i];
-    return t;
-}
-
 struct GiouPair {
     float giou;
     float g[4];  // d(giou)/d(cx, cy, w, h) of the prediction
@@ -178,10 +166,10 @@ __global__ __launch_bounds__(CRIT_THREADS) void criterion_kernel(
         if (MODE == 0 && lane == 0 && arg != K - 1) card += 1.f;
     }
     if (MODE == 0) {
-        const float ce = block_sum(ce_acc, red);
-        const float l1 = block_sum(l1_acc, red);
-        const float gi = block_sum(gi_acc, red);
-        const float cd = block_sum(card, red);
+        const float ce = block_sum<CRIT_THREADS>(ce_acc, red);
+        const float l1 = block_sum<CRIT_THREADS>(l1_acc, red);
+        const float gi = block_sum<CRIT_THREADS>(gi_acc, red);
+        const float cd = block_sum<CRIT_THREADS>(card, red);
         if (tid == 0) {
             if (match_status != nullptr && match_status[lb] != 0) {   // SciPy raises here (matcher.py:85): poison instead of a host sync
                 const float nan = __int_as_float(0x7fc00000);

@@ -120,6 +120,7 @@ __global__ __launch_bounds__(EM_THREADS) void mask_unpack_kernel(const uint64_t*
     for (int b = 0; b < y_end; ++b) p[(size_t)(yw * 64 + b) * W + x] = (uint8_t)((word >> b) & 1);
 }
 
+// the wave step stays open-coded: through common.h's wave_sum(unsigned) the two callers schedule their LDS store differently
 __device__ __forceinline__ unsigned block_sum_u32(unsigned v) {
     __shared__ unsigned part[EM_THREADS / 64];
 #pragma unroll

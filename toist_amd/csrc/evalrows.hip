@@ -21,12 +21,6 @@ static constexpr int ER_WAVES = ER_THREADS / 64;
 static constexpr int ER_CHUNK = TOIST_COCO_MASKS_CHUNK_WORDS;
 static constexpr int ER_GROUP = 1024;                    // ground truths whose counters sit in LDS at a time; a row with more streams its plane once per group
 
-__device__ __forceinline__ unsigned er_wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // grid (D, R)
 __global__ __launch_bounds__(ER_THREADS) void coco_masks_kernel(const uint64_t* __restrict__ bits, long long capacity_words,
                                                                 const int64_t* __restrict__ row_hw, int Q, int D, const int32_t* __restrict__ order,
@@ -108,13 +102,13 @@ __global__ __launch_bounds__(ER_THREADS) void coco_masks_kernel(const uint64_t* 
                 unsigned acc = 0;
 #pragma unroll 4
                 for (int i = lo + lane; i < hi; i += 64) acc += __popcll(s_chunk[i] & gp[i]);
-                acc = er_wave_sum(acc);
+                acc = wave_sum(acc);
                 if (lane == 0 && acc) atomicAdd(&s_acc[gl], acc);
             }
         }
         __syncthreads();                                                     // every counter of the group is complete
         if (gg == 0) {
-            mine = er_wave_sum(mine);
+            mine = wave_sum(mine);
             if (lane == 0) s_part[wave] = mine;
             __syncthreads();
 #pragma unroll

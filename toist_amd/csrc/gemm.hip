@@ -14,7 +14,6 @@
 // turned into MFMA fragments by the LDS transpose read ds_read_b64_tr_b16.  The MFMA is issued as
 // D^T = B * A^T so each lane owns 4 consecutive output columns -> 8-byte packed bf16 stores.
 #include <cstdlib>
-#include <type_traits>
 
 #include "common.h"
 #include "gemm_route.h"
@@ -27,14 +26,6 @@ namespace toist {
 __device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad_f(float a) {
     return 0.5f * (1.f + erff(a * 0.70710678118654752f)) + a * 0.3989422804014327f * __expf(-0.5f * a * a);
-}
-
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
 }
 
 // One 1x8 output chunk (row m, columns n .. n+7; the accumulators reach it through an LDS transpose so that a
@@ -63,19 +54,12 @@ __device__ __forceinline__ EpiRow epi_row(const toist_gemm& p, const int m, cons
     return r;
 }
 
-__device__ __forceinline__ void unpack8(const uint4 u, float* x) {
-    x[0] = __uint_as_float(u.x << 16); x[1] = __uint_as_float(u.x & 0xffff0000u);
-    x[2] = __uint_as_float(u.y << 16); x[3] = __uint_as_float(u.y & 0xffff0000u);
-    x[4] = __uint_as_float(u.z << 16); x[5] = __uint_as_float(u.z & 0xffff0000u);
-    x[6] = __uint_as_float(u.w << 16); x[7] = __uint_as_float(u.w & 0xffff0000u);
-}
-
 // 8 bf16 of a row; whole 16-byte load when the chunk is complete and aligned
 __device__ __forceinline__ void load_row8(const bf16_t* rp, const int nv, float* x) {
     if (nv == 8 && ((((size_t)rp) & 15) == 0)) {
         unpack8(*reinterpret_cast<const uint4*>(rp), x);
     } else {
-        static_for<8>([&](auto jj) {
+        unrolled<8>([&](auto jj) {
             constexpr int j = decltype(jj)::value;
             x[j] = (j < nv) ? bf2f(rp[j]) : 0.f;
         });
@@ -95,7 +79,7 @@ __device__ __forceinline__ void store_row8_bf16(bf16_t* cp, const int nv, const 
         *reinterpret_cast<uint4*>(cp) = make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
 #endif
     } else {
-        static_for<8>([&](auto jj) {
+        unrolled<8>([&](auto jj) {
             constexpr int j = decltype(jj)::value;
             if (j < nv) cp[j] = f2bf(v[j]);
         });
@@ -121,7 +105,7 @@ __device__ __forceinline__ void load_cols8(const float* src, const int nv, float
         const float4 a = reinterpret_cast<const float4*>(src)[0], b = reinterpret_cast<const float4*>(src)[1];
         x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
     } else {
-        static_for<8>([&](auto jj) {
+        unrolled<8>([&](auto jj) {
             constexpr int j = decltype(jj)::value;
             x[j] = (j < nv) ? src[j] : fill;
         });
@@ -173,48 +157,46 @@ __device__ __forceinline__ void epilogue_row8(const toist_gemm& p, float* v, con
     const float* rsc = e.rscale;
     if (rsc && p.group) rsc += p.group[bz].rscale_off;
     const float rs = rsc ? e.alpha * rsc[m] : e.alpha;
-    static_for<8>([&](auto jj) { v[decltype(jj)::value] *= rs; });
-    if (e.scale) static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] *= cols.scale[j]; });
-    if (e.shift) static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] += cols.shift[j]; });
+    unrolled<8>([&](auto jj) { v[decltype(jj)::value] *= rs; });
+    if (e.scale) unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] *= cols.scale[j]; });
+    if (e.shift) unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] += cols.shift[j]; });
     const unsigned long long didx = ((unsigned long long)bz * M + m) * N + n;
     const unsigned long long dseed = e.drop_where ? e.drop_seed + (e.drop_seed_dev ? *e.drop_seed_dev : 0ull) : 0ull;
     if (e.drop_where == 1) {
         const unsigned th = (unsigned)(e.drop_p * 4294967296.0);
         const float sc = 1.f / (1.f - e.drop_p);
-        static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = dropout_keep(dseed, didx + j, th) ? v[j] * sc : 0.f; });
+        unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = dropout_keep(dseed, didx + j, th) ? v[j] * sc : 0.f; });
     }
-    if (e.res) static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] += xres[j]; });
+    if (e.res) unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] += xres[j]; });
     if (e.pre_out) store_row8_bf16((bf16_t*)e.pre_out + coff + r.crow * p.ldc + n, nv, v);
     switch (e.act) {
-        case TOIST_ACT_RELU: static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = fmaxf(v[j], 0.f); }); break;
-        case TOIST_ACT_GELU: static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = gelu_f(v[j]); }); break;
-        case TOIST_ACT_SIGMOID: static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = 1.f / (1.f + __expf(-v[j])); }); break;
-        case TOIST_ACT_MASK_POS: static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = xaux[j] > 0.f ? v[j] : 0.f; }); break;
-        case TOIST_ACT_GELU_BWD: static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] *= gelu_grad_f(xaux[j]); }); break;
-        case TOIST_ACT_SIGMOID_BWD: static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] *= xaux[j] * (1.f - xaux[j]); }); break;
+        case TOIST_ACT_RELU: unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = fmaxf(v[j], 0.f); }); break;
+        case TOIST_ACT_GELU: unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = gelu_f(v[j]); }); break;
+        case TOIST_ACT_SIGMOID: unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = 1.f / (1.f + __expf(-v[j])); }); break;
+        case TOIST_ACT_MASK_POS: unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = xaux[j] > 0.f ? v[j] : 0.f; }); break;
+        case TOIST_ACT_GELU_BWD: unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] *= gelu_grad_f(xaux[j]); }); break;
+        case TOIST_ACT_SIGMOID_BWD: unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] *= xaux[j] * (1.f - xaux[j]); }); break;
         default: break;
     }
     if (e.drop_where == 2) {
         const unsigned th = (unsigned)(e.drop_p * 4294967296.0);
         const float sc = 1.f / (1.f - e.drop_p);
-        static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = dropout_keep(dseed, didx + j, th) ? v[j] * sc : 0.f; });
+        unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; v[j] = dropout_keep(dseed, didx + j, th) ? v[j] * sc : 0.f; });
     }
     if (e.out_f32) {
         float* cp = (float*)p.c + coff + r.crow * p.ldc + n;
         if (e.accumulate) {  // the element is owned by this thread: plain read-modify-write
-            static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; if (j < nv) cp[j] += v[j]; });
+            unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; if (j < nv) cp[j] += v[j]; });
         } else if (nv == 8 && ((((size_t)cp) & 15) == 0)) {
             reinterpret_cast<float4*>(cp)[0] = make_float4(v[0], v[1], v[2], v[3]);
             reinterpret_cast<float4*>(cp)[1] = make_float4(v[4], v[5], v[6], v[7]);
         } else {
-            static_for<8>([&](auto jj) { constexpr int j = decltype(jj)::value; if (j < nv) cp[j] = v[j]; });
+            unrolled<8>([&](auto jj) { constexpr int j = decltype(jj)::value; if (j < nv) cp[j] = v[j]; });
         }
     } else {
         store_row8_bf16((bf16_t*)p.c + coff + r.crow * p.ldc + n, nv, v);
     }
 }
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
 __device__ __forceinline__ void add8(float* acc, const u32x4_t& v) {
     acc[0] += __uint_as_float(v[0] << 16); acc[1] += __uint_as_float(v[0] & 0xffff0000u);
@@ -393,7 +375,6 @@ __device__ __forceinline__ bf16x8_t fragment(const bf16_t* s, int r0, int ks, in
         const int k = ks * 32 + 8 * g + (c16 >> 2);
         const int rc = (r0 >> 3) + ((c16 & 3) >> 1);          // 16-byte chunk holding this lane's 4 rows
         const int sub = (c16 & 1) * 4;                         // element offset inside the chunk
-        typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
         const bf16_t* q0 = &s[k * ROWS + swz_m<ROWS>(k, rc) * 8 + sub];
         const bf16_t* q1 = &s[(k + 4) * ROWS + swz_m<ROWS>(k + 4, rc) * 8 + sub];
         const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(q0));
@@ -413,7 +394,6 @@ __device__ __forceinline__ bf16x8_t fragment_perm8(const bf16_t* s, int r0, int 
     const int k = ks * 32 + 8 * g + (c16 >> 2);
     const int rc = (r0 >> 3) + (c16 & 3);
     const int sub = j * 4;
-    typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
     const bf16_t* q0 = &s[k * ROWS + swz_m<ROWS>(k, rc) * 8 + sub];
     const bf16_t* q1 = &s[(k + 4) * ROWS + swz_m<ROWS>(k + 4, rc) * 8 + sub];
     const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(q0));
@@ -450,7 +430,7 @@ __device__ __forceinline__ void epilogue_request(const toist_gemm& p, const int 
                                                  EpiTile<BN, FM>& t) {
     constexpr int CPR = EpiTile<BN, FM>::CPR, CH = EpiTile<BN, FM>::CH;
     const int tid = threadIdx.x, M = p.M;
-    static_for<FM>([&](auto ii) {
+    unrolled<FM>([&](auto ii) {
         constexpr int i = decltype(ii)::value;
 #pragma unroll
         for (int q = 0; q < CH; ++q) {
@@ -481,11 +461,11 @@ __device__ __forceinline__ void epilogue_finish(const toist_gemm& p, f32x4_t (&a
     const int M = p.M, N = p.N;
     constexpr int LDT = BN + 4;                      // f32 band pitch: +4 keeps the float4 writes conflict-free
     float* ws = partial ? p.workspace + ((size_t)bz * p.split_k + ksl) * M * N : nullptr;   // [problem][k-slice][M][N]
-    static_for<FM>([&](auto ii) {
+    unrolled<FM>([&](auto ii) {
         constexpr int i = decltype(ii)::value;
         EpiRow (&rows)[CH] = t.rows[i];
         lds_barrier();                               // previous band (or the last k-tile / the colsum scratch) is consumed
-        static_for<FN>([&](auto jj) {
+        unrolled<FN>([&](auto jj) {
             constexpr int j = decltype(jj)::value;
             *reinterpret_cast<f32x4_t*>(band + (wm * 16 + c16) * LDT + wn * WN + j * 16 + g * 4) = acc[i][j];
         });
@@ -506,7 +486,7 @@ __device__ __forceinline__ void epilogue_finish(const toist_gemm& p, f32x4_t (&a
                         reinterpret_cast<float4*>(cp)[0] = make_float4(v[0], v[1], v[2], v[3]);
                         reinterpret_cast<float4*>(cp)[1] = make_float4(v[4], v[5], v[6], v[7]);
                     } else {
-                        static_for<8>([&](auto e8) { constexpr int j = decltype(e8)::value; if (j < r.nv) cp[j] = v[j]; });
+                        unrolled<8>([&](auto e8) { constexpr int j = decltype(e8)::value; if (j < r.nv) cp[j] = v[j]; });
                     }
                 } else {
                     float xres[8], xaux[8];
@@ -1154,7 +1134,6 @@ __global__ __launch_bounds__(256) void conv3_kernel(const toist_gemm p) {
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
                 if (DGRAD) {
-                    typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
                     union { struct { s16x4_t a, b; } h; bf16x8_t v; } u;
                     u.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(sB + b_frag[ks][j][0]));
                     u.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(sB + b_frag[ks][j][1]));
@@ -1317,7 +1296,6 @@ __global__ __launch_bounds__(512, 2) void gemm128_kernel(const toist_gemm p) {
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
             if (B_KM) {
-                typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
                 union { struct { s16x4_t a, b; } h; bf16x8_t v; } u;
                 u.h.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(lds_raw + b_base[j][0] + SLOT * G8_STAGE_BYTES));
                 u.h.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(lds_raw + b_base[j][1] + SLOT * G8_STAGE_BYTES));
@@ -1372,8 +1350,8 @@ __global__ __launch_bounds__(512, 2) void gemm128_kernel(const toist_gemm p) {
         else step(std::integral_constant<int, S % NS>{}, fb, fa);
     };
 #pragma unroll 1
-    while (t + U <= T) static_for<U>(run);
-    static_for<U - 1>([&](auto sc) { if (t < T) run(sc); });
+    while (t + U <= T) unrolled<U>(run);
+    unrolled<U - 1>([&](auto sc) { if (t < T) run(sc); });
     if (timing) T2 = cyc_now();
     wait_vm<0>();
     lds_barrier();                                       // every wave is done with the ring
@@ -1638,7 +1616,6 @@ __global__ __launch_bounds__(512, 2) void gemm128w_kernel(const toist_gemm p) {
     }
     auto load_frags = [&](G8Frags& f, auto slotc) {
         constexpr int SLOT = decltype(slotc)::value;
-        typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
             union { struct { s16x4_t a, b; } h; bf16x8_t v; } u;
@@ -1702,8 +1679,8 @@ __global__ __launch_bounds__(512, 2) void gemm128w_kernel(const toist_gemm p) {
         else step(std::integral_constant<int, S % NS>{}, fb, fa);
     };
 #pragma unroll 1
-    while (t + U <= T) static_for<U>(run);
-    static_for<U - 1>([&](auto sc) { if (t < T) run(sc); });
+    while (t + U <= T) unrolled<U>(run);
+    unrolled<U - 1>([&](auto sc) { if (t < T) run(sc); });
     wait_vm<0>();
     lds_barrier();
 
@@ -1884,7 +1861,6 @@ __global__ __launch_bounds__(512, 2) void gemm256w_kernel(const toist_gemm p) {
     }
     auto load_frags = [&](G8Frags& f, auto slotc) {
         constexpr int SLOT = decltype(slotc)::value;
-        typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
             union { struct { s16x4_t a, b; } h; bf16x8_t v; } u;
@@ -1939,8 +1915,8 @@ __global__ __launch_bounds__(512, 2) void gemm256w_kernel(const toist_gemm p) {
         else step(std::integral_constant<int, S % NS>{}, fb, fa);
     };
 #pragma unroll 1
-    while (t + NS <= T) static_for<NS>(run);
-    static_for<NS - 1>([&](auto sc) { if (t < T) run(sc); });
+    while (t + NS <= T) unrolled<NS>(run);
+    unrolled<NS - 1>([&](auto sc) { if (t < T) run(sc); });
 
     // ---- f32 rows straight from the fragments: lane = row c16, 4 consecutive columns (16 bytes) ----
     const toist_epilogue& e = p.epi;
@@ -2215,7 +2191,6 @@ __device__ __forceinline__ void store16_asm(const i32x4_t& r, const int byte_off
 constexpr int P2_HEAD = 0;     // ring stages start here (the epilogue needs no LDS band: fragments are finished where the MFMA left them)
 
 // 8 bytes of every lane (see store16_asm)
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 __device__ __forceinline__ void store8_asm(const i32x4_t& r, const int byte_off, const u32x2_t& v) {
     asm volatile("buffer_store_dwordx2 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(v), "v"(byte_off), "s"(r) : "memory");
 }
@@ -2795,7 +2770,7 @@ __global__ __launch_bounds__(512, 2) void conv_pair_kernel(const toist_conv_pair
     for (int c = 0; c < 8; ++c) {
         const int ncol = 128 * c + wn1 * 32 + g * 8;        // first of this lane's 8 columns of mid
         // ---- phase 1: chunk c of mid, k-tiles 2 u, 2 u + 1 per step ----
-        static_for<2>([&](auto uc) {
+        unrolled<2>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             const int s = c * 4 + u;
             step_top(s, uc);
@@ -2871,7 +2846,7 @@ __global__ __launch_bounds__(512, 2) void conv_pair_kernel(const toist_conv_pair
             }
         }
         // ---- phase 2: the chunk's two 64-deep k-tiles into the output accumulators ----
-        static_for<2>([&](auto ktc) {
+        unrolled<2>([&](auto ktc) {
             constexpr int kt = decltype(ktc)::value;
             const int s = c * 4 + 2 + kt;
             step_top(s, std::integral_constant<int, 2 + kt>{});      // (its barrier also publishes the LDS copy of the chunk)

@@ -10,16 +10,6 @@
 
 namespace toist {
 
-__device__ __forceinline__ void unpack8(const uint4& u, float* f) {
-    f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
-    f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-    f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
-    f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-    return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-}
-
 // ---------------------------------------------------------------------------------- LayerNorm
 constexpr int LN_MAXCH = 2;  // D <= 1024
 

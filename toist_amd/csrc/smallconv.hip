@@ -127,7 +127,6 @@ __global__ __launch_bounds__(256) void wgrad3_small_kernel(const bf16_t* __restr
     constexpr int XBLK = 32 * C, DBLK = 32 * CO;   // elements
     __shared__ __attribute__((aligned(16))) bf16_t smem[4][DBLK + 3 * XBLK];
     __shared__ float fold[4][16 * 16];
-    typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c16 = lane & 15;
     bf16_t* sD = smem[wave];
     bf16_t* sX = sD + DBLK;

@@ -21,8 +21,6 @@
 //     reductions are four shuffles, and every global access is 16 bytes.
 #include "common.h"
 
-#include <type_traits>
-
 namespace toist {
 
 namespace {
@@ -31,43 +29,12 @@ constexpr int RN = 256;        // output columns = d_model
 constexpr int RBM = 16;        // rows per workgroup
 constexpr int RCS = RN + 8;    // row stride of the f32 accumulator tile in LDS
 constexpr int RTS = 72;        // row stride (bf16) of a wave's [32 k][64 n] weight tile
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-
-template <int N, typename F>
-__device__ __forceinline__ void unrolled(F&& f) {      // f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>): indices stay compile-time
-    if constexpr (N > 0) {
-        unrolled<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
-__device__ __forceinline__ void unpack8f(const uint4 u, float* v) {
-    const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        v[2 * q] = __uint_as_float(w[q] << 16);
-        v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ uint4 pack8f(const float* v) {
-    return make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-}
-// sum over the 16 lanes of a row group (lanes 16 r .. 16 r + 15 of the wave)
-__device__ __forceinline__ float group16_sum(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    return v;
-}
 
 }  // namespace
 
 template <int BKIND, int EPI>
 __global__ __launch_bounds__(256) void rowgemm_kernel(const toist_rowgemm_desc p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
     const int K = p.K, AS = K + 8;                        // A rows padded by 16 bytes: 16 rows hit 16 different bank groups
     bf16_t* const sA = reinterpret_cast<bf16_t*>(smem_raw);                         // [16][K + 8]
     bf16_t* const sRing = sA + RBM * AS;                                           // wave-private weight tiles: B_KROW [4][2][32 k][RTS], B_ROWK [4][2][64 n][RTS]
@@ -126,12 +93,12 @@ __global__ __launch_bounds__(256) void rowgemm_kernel(const toist_rowgemm_desc p
                         float s8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                         for (int sp = 0; sp < p.fold_parts; ++sp) {
                             float t8[8];
-                            unpack8f(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.fold) + (size_t)sp * p.fold_stride +
+                            unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.fold) + (size_t)sp * p.fold_stride +
                                                                      (size_t)m * p.fold_cols + pc * 8), t8);
 #pragma unroll
                             for (int q = 0; q < 8; ++q) s8[q] += t8[q];
                         }
-                        v[i] = pack8f(s8);
+                        v[i] = pack8(s8);
                         *reinterpret_cast<uint4*>(const_cast<bf16_t*>(reinterpret_cast<const bf16_t*>(p.a)) + (size_t)m * p.lda + pc * 8) = v[i];
                     }
                 }
@@ -240,13 +207,13 @@ __global__ __launch_bounds__(256) void rowgemm_kernel(const toist_rowgemm_desc p
         const int c0 = (pl + 16 * h) * 8;
         if (p.res != nullptr && live) {
             float t8[8];
-            unpack8f(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.res) + mrow * p.ldr + c0), t8);
+            unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.res) + mrow * p.ldr + c0), t8);
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[h][q] += t8[q];
         }
         if (p.res2 != nullptr && live) {
             float t8[8];
-            unpack8f(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.res2) + mrow * p.ldr2 + c0), t8);
+            unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.res2) + mrow * p.ldr2 + c0), t8);
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[h][q] += t8[q];
         }
@@ -256,7 +223,7 @@ __global__ __launch_bounds__(256) void rowgemm_kernel(const toist_rowgemm_desc p
         if (live) {
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out) + mrow * p.ldo + (pl + 16 * h) * 8) = pack8f(v[h]);
+                *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out) + mrow * p.ldo + (pl + 16 * h) * 8) = pack8(v[h]);
         }
         return;
     }
@@ -267,9 +234,9 @@ __global__ __launch_bounds__(256) void rowgemm_kernel(const toist_rowgemm_desc p
         float s = 0.f;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const uint4 zp = pack8f(v[h]);
+            const uint4 zp = pack8(v[h]);
             if (live && p.z != nullptr) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.z) + mrow * RN + (pl + 16 * h) * 8) = zp;
-            unpack8f(zp, v[h]);
+            unpack8(zp, v[h]);
 #pragma unroll
             for (int q = 0; q < 8; ++q) s += v[h][q];
         }
@@ -291,15 +258,15 @@ __global__ __launch_bounds__(256) void rowgemm_kernel(const toist_rowgemm_desc p
                 *reinterpret_cast<float4*>(bt + 4) = *reinterpret_cast<const float4*>(p.beta + c0 + 4);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) o[q] = (v[h][q] - mean) * rstd * gm[q] + bt[q];
-                const uint4 yo = pack8f(o);
+                const uint4 yo = pack8(o);
                 *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out) + mrow * p.ldo + c0) = yo;
                 if (p.out2 != nullptr) {       // bf16(bf16(y) + add): what the stand-alone add kernel computed from the stored y
                     float a8[8], y8[8];
-                    unpack8f(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.add) + mrow * RN + c0), a8);
-                    unpack8f(yo, y8);
+                    unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.add) + mrow * RN + c0), a8);
+                    unpack8(yo, y8);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) y8[q] += a8[q];
-                    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out2) + mrow * RN + c0) = pack8f(y8);
+                    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out2) + mrow * RN + c0) = pack8(y8);
                 }
             }
             if (pl == 0) {
@@ -319,7 +286,7 @@ __global__ __launch_bounds__(256) void rowgemm_kernel(const toist_rowgemm_desc p
         for (int h = 0; h < 2; ++h) {
             const int c0 = (pl + 16 * h) * 8;
             float z8[8], gm[8];
-            unpack8f(live ? *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.z) + mrow * RN + c0) : make_uint4(0, 0, 0, 0), z8);
+            unpack8(live ? *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p.z) + mrow * RN + c0) : make_uint4(0, 0, 0, 0), z8);
             *reinterpret_cast<float4*>(gm) = *reinterpret_cast<const float4*>(p.gamma + c0);
             *reinterpret_cast<float4*>(gm + 4) = *reinterpret_cast<const float4*>(p.gamma + c0 + 4);
 #pragma unroll
@@ -340,14 +307,14 @@ __global__ __launch_bounds__(256) void rowgemm_kernel(const toist_rowgemm_desc p
 #pragma unroll
             for (int q = 0; q < 8; ++q) o[q] = rs * (gg[h][q] - s1 - xh[h][q] * s2);
             if (live) {
-                *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out) + mrow * p.ldo + c0) = pack8f(o);
+                *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out) + mrow * p.ldo + c0) = pack8(o);
                 if (p.out2 != nullptr) {       // the gradient of the dropout(branch) term: same mask as the forward pass
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const unsigned long long idx = (unsigned long long)m * RN + c0 + q;
                         o[q] = dropout_keep(seed, idx, thresh) ? o[q] * dscale : 0.f;
                     }
-                    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out2) + mrow * RN + c0) = pack8f(o);
+                    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out2) + mrow * RN + c0) = pack8(o);
                 }
             }
             if (p.partials != nullptr) {

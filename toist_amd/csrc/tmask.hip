@@ -21,8 +21,6 @@ static constexpr int TM_VEC = 16;                 // adjacent output bytes per t
 static constexpr int TM_ROWS = TM_H / (TM_THREADS / (TM_W / TM_VEC));        // output rows per thread
 static_assert(TM_W == TM_THREADS && TM_H <= TM_THREADS && TM_ROWS * (TM_THREADS / (TM_W / TM_VEC)) == TM_H, "tile shape");
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
-
 struct TmaskRow {        // one slot: TOIST_TMASK_DESC_WORDS int32 (include/toist_hip.h)
     int src_off, src_h, src_w, src_stride_words, out_h, out_w, tab_y, tab_x;
 };

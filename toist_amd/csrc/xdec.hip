@@ -22,16 +22,10 @@
 //                 dropout hash of element m * 256 + n; linear1: dropout(relu(.)) hashed on element m * 2048 + n (csrc/gemm.hip epilogue)
 #include "common.h"
 
-#include <type_traits>
-
 namespace toist {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-typedef __attribute__((address_space(3))) s16x4_t* lds_v4;
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 constexpr int XD = 256, XH = 8, XDH = 32, XFF = 2048;
@@ -42,7 +36,6 @@ constexpr int XCS = XD + 8;        // row stride (f32) of the accumulator rows i
 constexpr int XW2S = 72;           // row stride (bf16) of the [256 n][64 hidden] linear2 slice in LDS
 constexpr int XPR = 128;           // rows per (image, CU) slab of the linear2 partial sums
 constexpr unsigned XOOB = 0x80000000u;      // a byte offset beyond num_records: the buffer load returns zeros without touching memory
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr unsigned XSPIN_MAX = 1u << 20;    // ~0.3 s of polling: only a group that is not co-resident gets there
 
 // LDS carve (bytes, every offset a multiple of 16)
@@ -61,14 +54,6 @@ constexpr int L_TOTAL = L_W2 + XD * XW2S * 2;
 static_assert(L_TOTAL <= 160 * 1024, "xdec: LDS budget");
 static_assert(8 * 4 * XD * 4 <= 8 * 64 * XDH * 2, "xdec: the P7 sums alias the V tiles");
 
-template <int N, typename F>
-__device__ __forceinline__ void unrolled(F&& f) {
-    if constexpr (N > 0) {
-        unrolled<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
 __device__ __forceinline__ rsrc_t mkrs(const void* p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7ffffff0, 0x00020000); }
 // 16 bytes at byte offset `off` of the buffer; FRESH = written by another CU of this launch: sc1 (served by the XCD's L2, not by this CU's L1)
 template <bool FRESH>
@@ -86,44 +71,6 @@ __device__ __forceinline__ unsigned xcc_id() {
     unsigned v;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
     return v & 15u;
-}
-
-// attn2.hip's hash: one 32-bit value decides two adjacent keys of a score row
-__device__ __forceinline__ unsigned pair_hash(unsigned pair, unsigned s0, unsigned s1) {
-    unsigned a = pair ^ s0;
-    a ^= a >> 12;               // the 24-bit multiply below only sees bits 0-23: fold the upper bits in first (pairs 2^24 apart otherwise share 99.9 % of their masks)
-    unsigned h = __umul24(a, 0x9E3779u) + s1;
-    h ^= h >> 15;
-    h = __umul24(h, 0x85EBCBu) + (a >> 8);
-    h ^= h >> 13;
-    return h;
-}
-__device__ __forceinline__ bf16x8_t tr_pair(const bf16_t* lo_ptr, const bf16_t* hi_ptr) {
-    const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)lo_ptr);
-    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)hi_ptr);
-    return __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-__device__ __forceinline__ bf16x8_t frag_of(unsigned a, unsigned b, unsigned c, unsigned d) {
-    const u32x4_t u = {a, b, c, d};
-    return __builtin_bit_cast(bf16x8_t, u);
-}
-__device__ __forceinline__ void unpack8f(const uint4 u, float* v) {
-    const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        v[2 * q] = __uint_as_float(w[q] << 16);
-        v[2 * q + 1] = __uint_as_float(w[q] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ uint4 pack8f(const float* v) {
-    return make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-}
-__device__ __forceinline__ float group16_sum(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    return v;
 }
 
 // ---- XCD-local barrier ------------------------------------------------------------------------------------------------------------------
@@ -576,7 +523,7 @@ __global__ __launch_bounds__(XNT) void xdec_fwd_kernel(const toist_xdec_desc p) 
                     const float4 b0 = *reinterpret_cast<const float4*>(ly.b_q + pc * 8), b1 = *reinterpret_cast<const float4*>(ly.b_q + pc * 8 + 4);
                     v8[0] = lo.x + b0.x; v8[1] = lo.y + b0.y; v8[2] = lo.z + b0.z; v8[3] = lo.w + b0.w;
                     v8[4] = hi.x + b1.x; v8[5] = hi.y + b1.y; v8[6] = hi.z + b1.z; v8[7] = hi.w + b1.w;
-                    const uint4 o = pack8f(v8);
+                    const uint4 o = pack8(v8);
                     *reinterpret_cast<uint4*>(sQ + r * XAS + pc * 8) = o;
                     if (q0 + r < Q) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.qc) + (lrow + q0 + r) * XD + pc * 8) = o;
                 }
@@ -733,7 +680,7 @@ __global__ __launch_bounds__(XNT) void xdec_fwd_kernel(const toist_xdec_desc p) 
 #pragma unroll
                         for (int hh = 0; hh < 2; ++hh) {
                             float t8[8];
-                            unpack8f(pv[u][hh], t8);
+                            unpack8(pv[u][hh], t8);
 #pragma unroll
                             for (int q = 0; q < 8; ++q) sum[hh][q] += t8[q];
                         }
@@ -1074,7 +1021,7 @@ __global__ __launch_bounds__(XNT) void xdec_bwd_kernel(const toist_xdec_bwd_desc
 #pragma unroll
                         for (int hh = 0; hh < 2; ++hh) {
                             float t8[8];
-                            unpack8f(pv[u][hh], t8);
+                            unpack8(pv[u][hh], t8);
 #pragma unroll
                             for (int q = 0; q < 8; ++q) sum[hh][q] += t8[q];
                         }
@@ -1108,7 +1055,7 @@ __global__ __launch_bounds__(XNT) void xdec_bwd_kernel(const toist_xdec_bwd_desc
                     float v8[8];
                     const float4 lo = *reinterpret_cast<const float4*>(sC + r * XCS + pc * 8), hi = *reinterpret_cast<const float4*>(sC + r * XCS + pc * 8 + 4);
                     v8[0] = lo.x; v8[1] = lo.y; v8[2] = lo.z; v8[3] = lo.w; v8[4] = hi.x; v8[5] = hi.y; v8[6] = hi.z; v8[7] = hi.w;
-                    if (4 * slot + r < Q) *reinterpret_cast<uint4*>(dctx_c + (row0 + 4 * slot + r) * XD + pc * 8) = pack8f(v8);
+                    if (4 * slot + r < Q) *reinterpret_cast<uint4*>(dctx_c + (row0 + 4 * slot + r) * XD + pc * 8) = pack8(v8);
                 }
             }
             xstamp(p.prof, wgid, p.L, layer, 5);
@@ -1173,7 +1120,7 @@ __global__ __launch_bounds__(XNT) void xdec_bwd_kernel(const toist_xdec_bwd_desc
                     float v8[8];
                     const float4 lo = *reinterpret_cast<const float4*>(sC + r * XCS + pc * 8), hi = *reinterpret_cast<const float4*>(sC + r * XCS + pc * 8 + 4);
                     v8[0] = lo.x; v8[1] = lo.y; v8[2] = lo.z; v8[3] = lo.w; v8[4] = hi.x; v8[5] = hi.y; v8[6] = hi.z; v8[7] = hi.w;
-                    if (4 * slot + r < Q) *reinterpret_cast<uint4*>(dctx_s + (row0 + 4 * slot + r) * XD + pc * 8) = pack8f(v8);
+                    if (4 * slot + r < Q) *reinterpret_cast<uint4*>(dctx_s + (row0 + 4 * slot + r) * XD + pc * 8) = pack8(v8);
                 }
             }
             xstamp(p.prof, wgid, p.L, layer, 9);

@@ -1,4 +1,4 @@
-"""Statistical quality of csrc/attn2.hip's pair_hash (two 24-bit multiply rounds; one 32-bit word decides the dropout of two adjacent
+"""Statistical quality of csrc/common.h's pair_hash (two 24-bit multiply rounds; one 32-bit word decides the dropout of two adjacent
 keys).  CPU only (numpy).  Prints, per seed: the drop rate of both 16-bit fields at p = 0.1, the correlation between the two fields of
 a word, the autocorrelation of the keep mask at the strides an attention tile walks (neighbouring pairs, a 416-key row = 208 pairs,
 powers of two), and the spread of column / row means of a [rows, 208] mask against the binomial expectation.

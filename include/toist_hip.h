@@ -357,6 +357,16 @@ TOIST_API int toist_sum_queries(const void* in, int B, int Q, int64_t per, void*
 TOIST_API int toist_mask_stage_fwd(const void* src, const float* src_stats, const float* gamma, const float* beta, const void* fpn_conv, const void* w,
                         const float* bias, void* out, float* out_stats, int N, int Q, int H, int W, int c_in, int c_out, int w_rows, int gn_in, int up,
                         float eps, void* stream);
+/* The mask head of a task sweep: the maps are those of P (image, caption) PAIRS, Q per pair, and the per-IMAGE terms (fpn / fpn_conv [n_images, ...])
+ * belong to image pair_image[map / Q] -- a DEVICE int32 table of N / Q entries, so one captured launch serves any pairing.  Otherwise the arguments,
+ * the arithmetic and the results are those of toist_mask_stage_fwd (the two `up` stages (64,32) and (32,16,gn_in); out_lay has no image term) and of
+ * toist_resize_add with rows = NULL.  toist_sweep_assemble's rule for a table entry outside [0, n_images): it is never used as an index, that pair's
+ * image term counts as zero and *status = max(*status, pair + 1) (int32, atomicMax; the caller zeroes and reads it). */
+TOIST_API int toist_mask_stage_fwd_pairs(const void* src, const float* src_stats, const float* gamma, const float* beta, const void* fpn_conv, const void* w,
+                        const float* bias, void* out, float* out_stats, int N, int Q, int H, int W, int c_in, int c_out, int w_rows, int gn_in, int up,
+                        float eps, const int32_t* pair_image, int n_images, int32_t* status, void* stream);
+TOIST_API int toist_resize_add_pairs(const void* in, const void* fpn, const int32_t* pair_image, int n_images, int n, int Q, int H, int W, int OH, int OW,
+                        int C, void* out, int32_t* status, void* stream);
 TOIST_API int toist_sum_segments(const void* in, const int32_t* seg, int B, int rows, int64_t per, void* out, void* stream);
 TOIST_API int toist_mask_loss_fwd(const float* pred, const int32_t* pred_row, const uint8_t* gt, const int32_t* gt_row, int T, int h, int w,
                         int TH, int TW, float alpha, float* sums, const int32_t* valid_hw, void* stream);
@@ -946,6 +956,13 @@ TOIST_API int toist_sweep_assemble(const void* img_tok, const void* img_pos, con
  * backbone / frozen text side): that half is skipped.  Same extent rules as the forward: D % 8 == 0, 16-byte aligned arrays, P*S < 2^31. */
 TOIST_API int toist_sweep_assemble_bwd(const void* d_seq, const int32_t* pair_image, const int32_t* pair_caption, int P, int B, int HW, int T, int L,
                      int D, void* d_img, void* d_txt, void* stream);
+
+/* Rows gathered by a pair table, one launch: dst[p, :] = src[pair_image[p], :] for p < P, rows of row_bytes bytes of ANY count and alignment (the
+ * per-image key-padding bytes and lay1 terms that the mask head of a sweep needs per pair).  src [n_images, row_bytes], dst [P, row_bytes] bytes,
+ * pair_image DEVICE int32 [P].  A pure copy: EVERY output byte is written.  An entry outside [0, n_images) is never used as an index: that row is
+ * zeros and *status = max(*status, p + 1) (int32, atomicMax). */
+TOIST_API int toist_sweep_gather(const void* src, const int32_t* pair_image, int n_images, int P, long long row_bytes, void* dst, int32_t* status,
+                     void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedPairTrainStep, CapturedEvalStep, CapturedSweepStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
+"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedPairTrainStep, CapturedEvalStep, CapturedSweepStep, CapturedMaskSweepStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
 core they share: bucket keys, the static image / text inputs of a bucket and the upload into them, the pair tables of a pair-shaped bucket and
 their fill (pair_inputs / fill_pair_inputs), the LRU of buckets, the eager pass followed by the capture, the rule that voids captured graphs once
 the XCD-resident decoder launches have been turned off, and the bodies of a step on a filled bucket: _CapturedStep._train_tail and
@@ -70,21 +70,28 @@ def upload(ent, samples, tokenized):
     att[:, :L].copy_(tokenized["attention_mask"], non_blocking=True)
 
 
-def pair_inputs(captions, pairs, Lp, pad_id, device, sizes=False):
+def pair_inputs(captions, pairs, Lp, pad_id, device, sizes=False, crops=False):
     """What a pair-shaped bucket holds besides its images: text inputs for the CAPTIONS (not one row per image), the two int32 pair tables at fixed
-    device addresses (+ sizes: an int64 [pairs, 2] table of each pair's original (h, w)) and ONE staging buffer for them -- rows 0 .. P = pair_image,
-    P .. 2P = pair_caption, behind them the sizes -- so that fill_pair_inputs' copies travel under one fence."""
-    views, nbytes = staging.typed_views([(torch.int32, (2 * pairs,))] + ([(torch.int64, (pairs, 2))] if sizes else []))
+    device addresses (+ sizes: an int64 [pairs, 2] table of each pair's original (h, w); + crops, with sizes: an int64 [pairs, 4] table of each pair's
+    (crop_h, crop_w, h, w) for toist_mask_resize_pack_batch) and ONE staging buffer for them -- rows 0 .. P = pair_image, P .. 2P = pair_caption,
+    behind them the sizes and the crops -- so that fill_pair_inputs' copies travel under one fence."""
+    if crops and not sizes:
+        raise ValueError("pair_inputs: the crop table comes with the size table")
+    views, nbytes = staging.typed_views([(torch.int32, (2 * pairs,))] + ([(torch.int64, (pairs, 2))] if sizes else []) +
+                                        ([(torch.int64, (pairs, 4))] if crops else []))
     ent = {"tok": static_inputs(captions, 1, 1, Lp, pad_id, device)["tok"],
            "pair_image": torch.zeros(pairs, dtype=torch.int32, device=device), "pair_caption": torch.zeros(pairs, dtype=torch.int32, device=device),
            "stage": staging.Staging(torch.zeros(nbytes, dtype=torch.uint8), device), "stage_views": views}
     if sizes:
         ent["sizes"] = torch.ones(pairs, 2, dtype=torch.int64, device=device)
+    if crops:
+        ent["crops"] = torch.ones(pairs, 4, dtype=torch.int64, device=device)
     return ent
 
 
-def fill_pair_inputs(ent, pi, pc, sizes=None):
-    """Host tables (int32 [P] each, + a list of P (h, w) when the bucket holds sizes) into pair_inputs' device tables: two or three copies, one record."""
+def fill_pair_inputs(ent, pi, pc, sizes=None, crops=None):
+    """Host tables (int32 [P] each, + a list of P (h, w) when the bucket holds sizes, + a list of P (crop_h, crop_w, h, w) when it holds crops) into
+    pair_inputs' device tables: two to four copies, one record."""
     P = pi.numel()
     tables, *rest = ent["stage_views"](ent["stage"].open())
     tables[:P] = pi
@@ -93,6 +100,9 @@ def fill_pair_inputs(ent, pi, pc, sizes=None):
     if sizes is not None:
         rest[0].copy_(torch.tensor(sizes, dtype=torch.int64))
         copies.append((ent["sizes"], rest[0]))
+    if crops is not None:
+        rest[1].copy_(torch.tensor(crops, dtype=torch.int64))
+        copies.append((ent["crops"], rest[1]))
     ent["stage"].upload(*copies)
 
 
@@ -699,6 +709,119 @@ class CapturedSweepStep(_CapturedStep):
         self._fill(ent, samples, tokenized, pi, pc, sizes)
         out = self._replay_checked(ent, lambda: self._forward(ent), lambda: ent["out"], lambda: self._handed_out(ent))
         return out, pi, pc, live
+
+    __call__ = step
+
+
+class CapturedMaskSweepStep(CapturedSweepStep):
+    """Task-sweep inference WITH THE MASK HEAD replayed from hipGraphs: CapturedSweepStep's pairs, tables and buckets around a DETRsegm.  One graph per
+    bucket (Hp, Wp, Lp) holds the image stage with all four backbone levels, the text stage (a parallel branch), the toist_sweep_assemble launch, the
+    encoder, decode, the mask program -- an image's terms once, the per-map program in passes of `pairs_per_pass` pairs (DETRsegm.decode_mask_sweep)
+    --, kernels.postprocess and, pass by pass, kernels.mask_resize_pack_batch over the pass's rows, so the graph's pool holds the logits of one pass.
+
+    step(samples, tokenized, orig_sizes, sizes, pairs=None) -> (results, pair_image, pair_caption, live): results[p], p < live, carries PostProcess's
+    "scores" / "labels" / "boxes" of pair p plus "mask_bits" int64 [Q, w, ceil(h / 64)] and "mask_size" (h, w) of its image's original size -- what
+    PostProcessSegm(packed=True) hands out; views into the bucket's buffers, valid until the next step of that bucket.
+    step_rows(...) -> (out, masks, pair_image, pair_caption, live): out = kernels.postprocess's dict of the bucket, masks = a coco_eval.RowMasks over
+    its planes (row p's planes start at word p * capacity_words): what coco_eval.SweepEvaluator.update_rows(masks=) scores in place.
+    orig_sizes / sizes: (h, w) per IMAGE as host values; the per-pair tables -- originals for toist_postprocess, (crop_h, crop_w, h, w) for
+    toist_mask_resize_pack_batch -- are gathered by pair_image on the host and uploaded with the pair tables when any of them changes.  The first
+    resize target is the bucket's (Hp, Wp), as in CapturedEvalStep; capacity and size checks are CapturedEvalStep.check_sizes's, raised before
+    anything is launched.  The status words (the sweep launches' and the XCD-resident decoder's) are read where results are handed out.
+    No prototype choice inside the graph: a cluster criterion raises ValueError."""
+
+    def __init__(self, model, cluster_criterion=None, *, batch, captions, pairs=None, max_orig_hw=None, pairs_per_pass=8, threshold=0.5, pad_hw=64,
+                 pad_tokens=1, max_graphs=4, device=None):
+        from .sweep import pair_passes
+        if cluster_criterion is not None:
+            raise ValueError("CapturedMaskSweepStep takes no cluster criterion: the prototype choice of a sweep runs in harness.evaluate_sweep's eager loop")
+        if not hasattr(model, "detr") or not hasattr(model, "decode_mask_sweep"):
+            raise ValueError("CapturedMaskSweepStep needs a model with a mask head (DETRsegm); CapturedSweepStep serves a detection model")
+        if max_orig_hw is None:
+            raise ValueError("CapturedMaskSweepStep needs max_orig_hw = the largest original (h, w) its mask planes have to hold")
+        self.model = model
+        self.batch, self.captions = int(batch), int(captions)
+        self.pairs = self.batch * self.captions if pairs is None else int(pairs)
+        if self.batch <= 0 or self.captions <= 0 or self.pairs <= 0:
+            raise ValueError(f"CapturedMaskSweepStep: batch = {batch}, captions = {captions}, pairs = {pairs}")
+        self.pairs_per_pass = int(pairs_per_pass)
+        pair_passes(self.pairs, pairs_per_pass)                     # ValueError for a pass size that is not a positive integer
+        self.pad_hw, self.pad_tokens, self.max_graphs = int(pad_hw), int(pad_tokens), int(max_graphs)
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        self.num_queries = model.detr.query_embed.weight.shape[0]
+        self.masks, self.threshold = True, float(threshold)           # (masks: what CapturedEvalStep.check_sizes reads)
+        self.max_orig_hw = (int(max_orig_hw[0]), int(max_orig_hw[1]))
+        if self.max_orig_hw[0] <= 0 or self.max_orig_hw[1] <= 0:
+            raise ValueError(f"CapturedMaskSweepStep: max_orig_hw = {max_orig_hw}")
+        self.capacity_words = self.num_queries * self.max_orig_hw[1] * ((self.max_orig_hw[0] + 63) // 64)
+        self._init_capture_state()
+
+    check_sizes = CapturedEvalStep.check_sizes
+
+    def _static_inputs(self, key):
+        Hp, Wp, Lp = key
+        pad_id = _pad_id(self.model)
+        return {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, self.device),
+                **pair_inputs(self.captions, self.pairs, Lp, pad_id, self.device, sizes=True, crops=True), **_NO_GRAPH, "uploaded": None, "out": None,
+                "bits": torch.zeros(self.pairs * self.capacity_words, dtype=torch.int64, device=self.device)}
+
+    def _fill(self, ent, samples, tokenized, pi, pc, sizes, crops):
+        upload(ent, samples, tokenized)
+        tables = (pi.tolist(), pc.tolist(), sizes, crops)
+        if ent["uploaded"] != tables:
+            fill_pair_inputs(ent, pi, pc, sizes, crops)
+            ent["uploaded"] = tables
+
+    def _forward(self, ent, key):
+        """The launches of one batch on the bucket's static inputs (eagerly, and once more under capture)."""
+        cap = self.capacity_words
+
+        def pack(lo, hi, logits):                    # the planes of one pass's rows, while its logits exist
+            kernels.mask_resize_pack_batch(logits, (key[0], key[1]), ent["crops"][lo:hi], self.max_orig_hw, cap, ent["bits"][lo * cap:hi * cap], self.threshold)
+
+        state, text = self.model.mask_sweep_stages(ent["samples"], ent["tok"])
+        mc = self.model.mask_sweep_pairs(state, text, ent["pair_image"], ent["pair_caption"], check=False)          # (step reads the status word)
+        outputs = self.model.decode_mask_sweep(mc, self.pairs_per_pass, mask_sink=pack)
+        ent["out"] = kernels.postprocess(outputs["pred_logits"], outputs["pred_boxes"], ent["sizes"], outputs.get("pred_isfinal"), out=ent["out"])
+
+    def _planes(self, ent, p, hw):
+        h, w = hw
+        words = kernels.mask_words(h)
+        Q, cap = self.num_queries, self.capacity_words
+        return ent["bits"][p * cap:p * cap + Q * w * words].view(Q, w, words)
+
+    def step(self, samples, tokenized, orig_sizes, sizes, pairs=None):
+        ent, sizes_p, pi, pc, live = self._step(samples, tokenized, orig_sizes, sizes, pairs)
+        results = row_results(ent["out"], self.pairs, live, self.num_queries, self.device)
+        for p, r in enumerate(results):
+            r["mask_bits"], r["mask_size"] = self._planes(ent, p, sizes_p[p]), sizes_p[p]
+        return results, pi, pc, live
+
+    def step_rows(self, samples, tokenized, orig_sizes, sizes, pairs=None):
+        """step() without the per-row dicts -> (out, masks, pair_image, pair_caption, live); rows from `live` on are padding."""
+        from .coco_eval import RowMasks
+        ent, sizes_p, pi, pc, live = self._step(samples, tokenized, orig_sizes, sizes, pairs)
+        return ent["out"], RowMasks(ent["bits"], self.capacity_words, ent["sizes"], sizes_p), pi, pc, live
+
+    @torch.no_grad()
+    def _step(self, samples, tokenized, orig_sizes, sizes, pairs):
+        from . import sweep
+        if isinstance(tokenized, (list, tuple)) and len(tokenized) and isinstance(tokenized[0], str):
+            tokenized = self.model.detr.transformer._tokenize(list(tokenized), self.device)
+        if samples.tensors.shape[0] != self.batch or tokenized["input_ids"].shape[0] != self.captions:
+            raise ValueError(f"CapturedMaskSweepStep was built for {self.batch} images and {self.captions} captions "
+                             f"(got {samples.tensors.shape[0]} and {tokenized['input_ids'].shape[0]})")
+        key = self.bucket_of(samples, tokenized)
+        orig, crop = self.check_sizes(key, orig_sizes, sizes)                                            # ValueError before anything is launched
+        pi, pc, live = sweep.pair_tables(self.batch, self.captions, pairs, capacity=self.pairs)           # the same
+        rows = pi.tolist()
+        sizes_p, crops_p = [orig[i] for i in rows], [crop[i] + orig[i] for i in rows]
+        if self.model.training:
+            self.model.eval()
+        ent = self._entry(key)
+        self._fill(ent, samples, tokenized, pi, pc, sizes_p, crops_p)
+        self._replay_checked(ent, lambda: self._forward(ent, key), lambda: None, lambda: self._handed_out(ent))
+        return ent, sizes_p, pi, pc, live
 
     __call__ = step
 

@@ -807,44 +807,64 @@ class _RowScorer:
 
 
 class SweepEvaluator:
-    """A task sweep scored on the device: one TDODCocoEvaluator(gt, ["bbox"]) per task over ONE StagedGroundTruth, all rows of a batch in two launches.
-    Boxes only: a sweep has no mask head, so its update_rows takes no masks and its ground truth is staged without planes.
-    ground_truths = {task name: CocoGroundTruth or COCO-format dict}.  COCO-Tasks' number is mAP@0.5 per task and its mean over the tasks:
-    summarize() -> {"tasks": {name: the 12 stats}, "mAP50": mean over the tasks of stats[1], "mAP": mean of stats[0]} (plain means over every task,
-    a task without ground truth counts with pycocotools' -1)."""
+    """A task sweep scored on the device: one TDODCocoEvaluator(gt, iou_types) per task over ONE StagedGroundTruth, all rows of a batch in two launches
+    per iou type (+ toist_coco_masks for "segm").
+    ground_truths = {task name: CocoGroundTruth or COCO-format dict}.  iou_types: ("bbox",) -- the default, a detection model's sweep: update_rows
+    takes no masks and the ground truth is staged without planes -- or any of ("bbox", "segm"): with "segm" the ground truth is staged with its planes
+    (StagedGroundTruth(planes=True)) and update_rows needs masks = the RowMasks of the rows (CapturedMaskSweepStep.step_rows hands one out,
+    RowMasks.pack builds one from PostProcessSegm(packed=True)'s planes).  COCO-Tasks' number is mAP@0.5 per task and its mean over the tasks:
+    summarize() -> {"tasks": {name: the 12 box stats}, "mAP50": mean over the tasks of stats[1], "mAP": mean of stats[0]} (plain means over every
+    task, a task without ground truth counts with pycocotools' -1) and, with "segm", "segm": {"tasks", "mAP50", "mAP"} of the mask stats beside them
+    (iou_types == ("segm",): the top-level numbers are the mask numbers too)."""
 
-    def __init__(self, ground_truths, device="cuda"):
+    def __init__(self, ground_truths, device="cuda", iou_types=("bbox",)):
         self.device = torch.device(device)
+        if isinstance(iou_types, str) or not isinstance(iou_types, (list, tuple)):
+            raise ValueError(f"SweepEvaluator: iou_types is a tuple within ('bbox', 'segm') (got {iou_types!r})")
+        self.iou_types = tuple(iou_types)
+        if not self.iou_types or any(t not in ("bbox", "segm") for t in self.iou_types) or len(set(self.iou_types)) != len(self.iou_types):
+            raise ValueError(f"SweepEvaluator: iou_types is a non-empty tuple of distinct types within ('bbox', 'segm') (got {iou_types!r})")
         gts = {name: g if isinstance(g, CocoGroundTruth) else CocoGroundTruth(g) for name, g in ground_truths.items()}
         if not gts:
             raise ValueError("SweepEvaluator needs at least one task")
-        self.evaluators = {name: TDODCocoEvaluator(g, ["bbox"], device=self.device) for name, g in gts.items()}
-        self.staged = StagedGroundTruth(list(gts.values()), self.device)
+        self.evaluators = {name: TDODCocoEvaluator(g, list(self.iou_types), device=self.device) for name, g in gts.items()}
+        self.staged = StagedGroundTruth(list(gts.values()), self.device, planes="segm" in self.iou_types)
         self._scorer = _RowScorer(self.staged, self.device)
         self._index = {name: t for t, name in enumerate(gts)}
         for name, t in self._index.items():
             self.evaluators[name]._attach(self._scorer, t)
 
-    def update_rows(self, out, image_ids, task_names, pair_image, pair_caption, live=None):
+    def update_rows(self, out, image_ids, task_names, pair_image, pair_caption, live=None, masks=None):
         """Score the first `live` rows of out = kernels.postprocess's dict: row p is caption task_names[pair_caption[p]] on image
         image_ids[pair_image[p]] (the tables of sweep.pair_tables / CapturedSweepStep.step_rows).  Every task named by a live row must be one of
-        this evaluator's.  No host synchronisation: see TDODCocoEvaluator.update_rows."""
+        this evaluator's.  masks: the rows' RowMasks, needed by (and only read for) "segm".  No host synchronisation: see
+        TDODCocoEvaluator.update_rows."""
         from .sweep import _index_list
+        if "segm" in self.iou_types:
+            if masks is None:
+                raise ValueError("SweepEvaluator(iou_types with 'segm').update_rows needs masks = the rows' coco_eval.RowMasks")
+            if not isinstance(masks, RowMasks):
+                raise TypeError(f"update_rows: masks is a coco_eval.RowMasks (got {type(masks).__name__})")
         pi, pc = _index_list(pair_image, "pair_image"), _index_list(pair_caption, "pair_caption")
         live = len(pi) if live is None else int(live)
         if len(pc) != len(pi) or not 0 <= live <= len(pi):
             raise ValueError(f"update_rows: tables of {len(pi)} and {len(pc)} pairs, {live} of them live")
         ids = [int(i) if torch.is_tensor(i) else i for i in image_ids]
         keys, targets, seen = [], [], {}
+        boxes_only = self.iou_types == ("bbox",)
         for p in range(live):
             name = task_names[pc[p]]
             if name not in self._index:
                 raise ValueError(f"update_rows: pair {p} names task {name!r}, which this SweepEvaluator has no ground truth for")
             img = ids[pi[p]]
             keys.append((self._index[name], img))
-            targets.append((self.evaluators[name].coco_eval["bbox"], img))
+            evs = self.evaluators[name].coco_eval
+            targets.append((evs["bbox"] if boxes_only else evs, img))
             seen.setdefault(name, set()).add(img)
-        self._scorer.score(out, self.staged.slots(keys), targets)
+        if boxes_only:
+            self._scorer.score(out, self.staged.slots(keys), targets)
+        else:
+            self._scorer.score(out, self.staged.slots(keys), targets, masks=masks if "segm" in self.iou_types else None, types=self.iou_types)
         for name, imgs in seen.items():
             self.evaluators[name].img_ids.extend(sorted(imgs))
 
@@ -859,10 +879,17 @@ class SweepEvaluator:
             ev.accumulate()
 
     def summarize(self, verbose=False):
-        tasks = {}
         for name, ev in self.evaluators.items():
             if verbose:
                 print(f"task {name}")
             ev.summarize(verbose)
-            tasks[name] = ev.coco_eval["bbox"].stats
-        return {"tasks": tasks, "mAP50": float(np.mean([s[1] for s in tasks.values()])), "mAP": float(np.mean([s[0] for s in tasks.values()]))}
+
+        def numbers(iou_type):
+            tasks = {name: ev.coco_eval[iou_type].stats for name, ev in self.evaluators.items()}
+            return {"tasks": tasks, "mAP50": float(np.mean([s[1] for s in tasks.values()])), "mAP": float(np.mean([s[0] for s in tasks.values()]))}
+
+        iou_types = getattr(self, "iou_types", ("bbox",))
+        out = numbers("bbox" if "bbox" in iou_types else "segm")
+        if "segm" in iou_types:
+            out["segm"] = numbers("segm")
+        return out

@@ -43,11 +43,16 @@ __device__ __forceinline__ uint4 ms_pack8v(const ms_f2* f) {
     return make_uint4(pack2bf(f[0].x, f[0].y), pack2bf(f[1].x, f[1].y), pack2bf(f[2].x, f[2].y), pack2bf(f[3].x, f[3].y));
 }
 
-template <int CIN, int COUT, bool GNIN, bool UP, bool OUT1>
+// PAIRS (a task sweep's maps, UP stages only): map n belongs to pair n / Q and adds the term of image pair_image[n / Q] -- one load per workgroup.  An
+// entry outside [0, n_images) is never used as an index: that pair's image term counts as zero and pair + 1 goes into *status with atomicMax
+// (toist_sweep_assemble's rule).  PAIRS = false ignores the three arguments: the image is n / Q, the code of that instantiation is what it was.
+template <int CIN, int COUT, bool GNIN, bool UP, bool OUT1, bool PAIRS = false>
 __global__ __launch_bounds__(256, (CIN >= 64 ? 2 : 3)) void mask_stage_kernel(const bf16_t* __restrict__ src, const float* __restrict__ src_stats, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, const bf16_t* __restrict__ fpn_conv, const bf16_t* __restrict__ w,
                                                           const float* __restrict__ bias, bf16_t* __restrict__ out, float* __restrict__ out_stats,
-                                                          float* __restrict__ out1, int Q, int H, int W, int w_rows, float eps) {
+                                                          float* __restrict__ out1, int Q, int H, int W, int w_rows, float eps,
+                                                          const int32_t* __restrict__ pair_image, int n_images, int32_t* __restrict__ status) {
+    static_assert(!PAIRS || UP, "only a stage with an image term reads the pair table");
     constexpr int CH = CIN / 8;
     constexpr int TS = 16, HS = TS + 2;
     constexpr int SP = UP ? TS / 2 + 2 : HS;            // side of the LDS tile in source pixels: 10 x 10 under an upsampled tile, else the 18 x 18 halo tile
@@ -57,11 +62,11 @@ __global__ __launch_bounds__(256, (CIN >= 64 ? 2 : 3)) void mask_stage_kernel(co
     constexpr int KL = KM / 4;
     constexpr int NB = (COUT + 15) / 16;
     constexpr int CG = OUT1 ? 1 : COUT / 8;          // channels per output GroupNorm group
-    static_assert(OUT1 || CG == 2 || CG == 4 || CG == 8, "output groups of 2, 4 or 8 channels");
+    static_assert(OUT1 || CG == 2 || CG == 4, "output groups of 2 or 4 channels (a lane's channel quad lies in one group or spans two: the per-wave statistics slots rely on it)");
     static_assert(256 % CH == 0, "a thread keeps one channel chunk");
     typedef typename MsFrag<KM>::type frag_t;
     __shared__ __attribute__((aligned(16))) bf16_t tile[2][SP * SP * PX];     // two buffers: tile k+1 is written while slower waves still read tile k -> ONE barrier per tile
-    __shared__ float sacc[2][8];
+    __shared__ float sacc[4][2][8];                   // per wave: the strip's statistics are folded in wave order, the same sum in every run
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
     const int tiles_y = (H + TS - 1) / TS, tiles_x = (W + TS - 1) / TS;
@@ -111,13 +116,19 @@ __global__ __launch_bounds__(256, (CIN >= 64 ? 2 : 3)) void mask_stage_kernel(co
             cb[j >> 1][j & 1] = beta[c] - mean * a;
         }
     }
-    if (tid < 16) sacc[tid >> 3][tid & 7] = 0.f;
     float ssum[NB][2], ssq[NB][2];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { ssum[nb][0] = ssum[nb][1] = 0.f; ssq[nb][0] = ssq[nb][1] = 0.f; }
 
     const bf16_t* src_n = src + (size_t)n * SH * SW * CIN;
-    const bf16_t* res_b = UP ? fpn_conv + (size_t)(n / Q) * H * W * COUT : nullptr;
+    const bf16_t* res_b = UP ? fpn_conv + (size_t)(PAIRS ? 0 : n / Q) * H * W * COUT : nullptr;
+    bool res_ok = true;                               // PAIRS: this map's pair names an image that exists
+    if constexpr (PAIRS) {
+        const int pair = n / Q, img = pair_image[pair];
+        res_ok = (unsigned)img < (unsigned)n_images;
+        if (res_ok) res_b += (size_t)img * H * W * COUT;                 // (computed only from a checked index)
+        else if (tid == 0 && ty == 0 && n == pair * Q) atomicMax(status, pair + 1);
+    }
 
     // ---- fill-phase tasks of this thread, fixed for the whole strip (only the column origin moves): one pixel of the LDS tile x one channel chunk ----
     constexpr int NTASK = SP * SP * CH;
@@ -193,7 +204,7 @@ __global__ __launch_bounds__(256, (CIN >= 64 ? 2 : 3)) void mask_stage_kernel(co
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
                     fr[nb] = make_uint2(0, 0);
-                    if (live && nb * 16 + g * 4 < COUT) fr[nb] = *reinterpret_cast<const uint2*>(res_b + ((size_t)y * W + x) * COUT + nb * 16 + g * 4);
+                    if (live && res_ok && nb * 16 + g * 4 < COUT) fr[nb] = *reinterpret_cast<const uint2*>(res_b + ((size_t)y * W + x) * COUT + nb * 16 + g * 4);
                 }
             }
 #pragma unroll
@@ -242,7 +253,8 @@ __global__ __launch_bounds__(256, (CIN >= 64 ? 2 : 3)) void mask_stage_kernel(co
         }
     }
     if constexpr (!OUT1) {
-        // ---- statistics of this strip: fold the 16 pixel lanes of a channel quad, then the waves through LDS, then one atomic per (group, moment) ----
+        // ---- statistics of this strip: fold the 16 pixel lanes of a channel quad, then the waves through LDS IN WAVE ORDER (LDS atomics on one counter took
+        // them in arrival order: the statistics of a one-strip map differed in the last bit from run to run), then one atomic per (group, moment) ----
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -251,22 +263,27 @@ __global__ __launch_bounds__(256, (CIN >= 64 ? 2 : 3)) void mask_stage_kernel(co
 #pragma unroll
                 for (int m = 1; m < 16; m <<= 1) { s += __shfl_xor(s, m); q += __shfl_xor(q, m); }
                 const int c0 = nb * 16 + g * 4 + 2 * h;
-                if (c16 == 0 && c0 < COUT) {
-                    atomicAdd(&sacc[0][c0 / CG], s);
-                    atomicAdd(&sacc[1][c0 / CG], q);
+                if (c16 == 0 && c0 < COUT) {              // (nb, g, h) -> group is one to one: every wave writes each of its 16 counters exactly once
+                    sacc[wave][0][c0 / CG] = s;
+                    sacc[wave][1][c0 / CG] = q;
                 }
             }
         __syncthreads();
-        if (tid < 16) atomicAdd(out_stats + ((size_t)n * 8 + (tid & 7)) * 2 + (tid >> 3), sacc[tid >> 3][tid & 7]);
+        if (tid < 16) {
+            const int m = tid >> 3, gi = tid & 7;
+            atomicAdd(out_stats + ((size_t)n * 8 + gi) * 2 + m, ((sacc[0][m][gi] + sacc[1][m][gi]) + sacc[2][m][gi]) + sacc[3][m][gi]);
+        }
     }
 }
 
-template <int CIN, int COUT, bool GNIN, bool UP, bool OUT1>
+template <int CIN, int COUT, bool GNIN, bool UP, bool OUT1, bool PAIRS = false>
 static void launch_stage(const void* src, const float* src_stats, const float* gamma, const float* beta, const void* fpn_conv, const void* w, const float* bias,
-                         void* out, float* out_stats, int N, int Q, int H, int W, int w_rows, float eps, hipStream_t st) {
+                         void* out, float* out_stats, int N, int Q, int H, int W, int w_rows, float eps, hipStream_t st, const int32_t* pair_image = nullptr,
+                         int n_images = 0, int32_t* status = nullptr) {
     const int tiles_y = (H + 15) / 16;
-    hipLaunchKernelGGL((mask_stage_kernel<CIN, COUT, GNIN, UP, OUT1>), dim3((unsigned)(N * tiles_y)), dim3(256), 0, st, (const bf16_t*)src, src_stats, gamma, beta,
-                       (const bf16_t*)fpn_conv, (const bf16_t*)w, bias, OUT1 ? nullptr : (bf16_t*)out, out_stats, OUT1 ? (float*)out : nullptr, Q, H, W, w_rows, eps);
+    hipLaunchKernelGGL((mask_stage_kernel<CIN, COUT, GNIN, UP, OUT1, PAIRS>), dim3((unsigned)(N * tiles_y)), dim3(256), 0, st, (const bf16_t*)src, src_stats, gamma,
+                       beta, (const bf16_t*)fpn_conv, (const bf16_t*)w, bias, OUT1 ? nullptr : (bf16_t*)out, out_stats, OUT1 ? (float*)out : nullptr, Q, H, W,
+                       w_rows, eps, pair_image, n_images, status);
 }
 
 }  // namespace toist
@@ -298,4 +315,29 @@ extern "C" int toist_mask_stage_fwd(const void* src, const float* src_stats, con
         return TOIST_EINVAL;
     }
     return check_launch("toist_mask_stage_fwd");
+}
+
+// See include/toist_hip.h.  The two stages with an image term: (32, 16) with gn_in (lay5) and (64, 32) (lay4), both up; out_lay keeps toist_mask_stage_fwd.
+extern "C" int toist_mask_stage_fwd_pairs(const void* src, const float* src_stats, const float* gamma, const float* beta, const void* fpn_conv, const void* w,
+                                          const float* bias, void* out, float* out_stats, int N, int Q, int H, int W, int c_in, int c_out, int w_rows,
+                                          int gn_in, int up, float eps, const int32_t* pair_image, int n_images, int32_t* status, void* stream) {
+    TOIST_REQUIRE(src && w && out && out_stats && fpn_conv && N > 0 && Q > 0 && H > 0 && W > 0 && w_rows > 0, "toist_mask_stage_fwd_pairs: bad args");
+    TOIST_REQUIRE(pair_image && status && n_images > 0 && (N % Q) == 0, "toist_mask_stage_fwd_pairs: a pair table of N / Q entries, n_images > 0 and a status word");
+    TOIST_REQUIRE(!gn_in || (src_stats && gamma && beta), "toist_mask_stage_fwd_pairs: gn_in needs src_stats, gamma and beta");
+    TOIST_REQUIRE(up && (H % 2) == 0 && (W % 2) == 0, "toist_mask_stage_fwd_pairs: only the up stages have an image term (even output sizes)");
+    TOIST_REQUIRE((long long)N * ((H + 15) / 16) < (1ll << 31), "toist_mask_stage_fwd_pairs: too many strips");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(out_stats, 0, sizeof(float) * 16 * (size_t)N, st);
+    if (e != hipSuccess) { set_last_error("toist_mask_stage_fwd_pairs: memset: %s", hipGetErrorString(e)); return TOIST_EHIP; }
+    if (c_in == 32 && c_out == 16 && gn_in && w_rows == 16)
+        launch_stage<32, 16, true, true, false, true>(src, src_stats, gamma, beta, fpn_conv, w, bias, out, out_stats, N, Q, H, W, w_rows, eps, st, pair_image,
+                                                      n_images, status);
+    else if (c_in == 64 && c_out == 32 && !gn_in && w_rows == 32)
+        launch_stage<64, 32, false, true, false, true>(src, src_stats, gamma, beta, fpn_conv, w, bias, out, out_stats, N, Q, H, W, w_rows, eps, st, pair_image,
+                                                       n_images, status);
+    else {
+        set_last_error("toist_mask_stage_fwd_pairs: unsupported stage (c_in %d, c_out %d, w_rows %d, gn_in %d, up %d)", c_in, c_out, w_rows, gn_in, up);
+        return TOIST_EINVAL;
+    }
+    return check_launch("toist_mask_stage_fwd_pairs");
 }

@@ -82,11 +82,16 @@ __global__ __launch_bounds__(256) void attnmap_softmax_bwd_kernel(const bf16_t* 
 // handles channel chunk (t % c8) of pixel (t / c8) + k * (256 / c8), so its 8 channels -- and their groups -- are fixed
 // and every partial sum stays in registers until one LDS/global atomic per channel at the end.
 // stats[n][g] = {sum, sum of squares} over the (HW x C/G) elements of group g of sample n (f32 atomics).
+// Inside a block the order of the sum is FIXED: a wave adds into LDS counters of its own (its lanes' atomics arrive in lane and program order) and the
+// four waves' counters are added in wave order -- one counter for all four took the waves in the order they happened to arrive, so the statistics of
+// the same input differed in the last bit from run to run even where a sample is ONE block (every map of 8192 chunks or fewer).  Across the blocks
+// of a larger sample the global atomics still add in arrival order.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict__ x, int HW, int C, int G, float* __restrict__ stats) {
-    __shared__ float acc[2][16];
+    __shared__ float acc[4][2][16];
     const int n = blockIdx.y;
     const int Cg = C / G, c8 = C >> 3;
-    if (threadIdx.x < 32) acc[threadIdx.x >> 4][threadIdx.x & 15] = 0.f;
+    const int wv = threadIdx.x >> 6;
+    if (threadIdx.x < 128) acc[threadIdx.x >> 5][(threadIdx.x >> 4) & 1][threadIdx.x & 15] = 0.f;
     __syncthreads();
     const int ppi = 256 / c8;                      // pixels per block iteration
     const int cc = threadIdx.x % c8, pl = threadIdx.x / c8;
@@ -129,15 +134,16 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int g = (cc * 8 + j) / Cg;
-                atomicAdd(&acc[0][g], s[j]);
-                atomicAdd(&acc[1][g], q[j]);
+                atomicAdd(&acc[wv][0][g], s[j]);
+                atomicAdd(&acc[wv][1][g], q[j]);
             }
         }
     }
     __syncthreads();
     if (threadIdx.x < G) {
-        atomicAdd(stats + ((size_t)n * G + threadIdx.x) * 2, acc[0][threadIdx.x]);
-        atomicAdd(stats + ((size_t)n * G + threadIdx.x) * 2 + 1, acc[1][threadIdx.x]);
+        const int g = threadIdx.x;
+        atomicAdd(stats + ((size_t)n * G + g) * 2, ((acc[0][0][g] + acc[1][0][g]) + acc[2][0][g]) + acc[3][0][g]);
+        atomicAdd(stats + ((size_t)n * G + g) * 2 + 1, ((acc[0][1][g] + acc[1][1][g]) + acc[2][1][g]) + acc[3][1][g]);
     }
 }
 // y = relu((x - mean) * rstd * gamma + beta).  Work split of the reducing kernels above (round 5): a thread keeps ONE channel chunk and walks the
@@ -316,9 +322,12 @@ __device__ __forceinline__ int nearest_src(int dst, float scale, int in) {
     const int s = (int)floorf((float)dst * scale);
     return s < in - 1 ? s : in - 1;
 }
-template <bool twice>        // twice: OH = 2 H and OW = 2 W (image sides that are multiples of 32: the shift form, no float index arithmetic)
+// pairs (a task sweep's maps, rows == nullptr): map bq belongs to pair bq / Q, its image is pair_image[bq / Q] (device int32).  An entry outside
+// [0, n_images) is never used as an index: that pair's FPN term counts as zero and pair + 1 goes into *status with atomicMax (toist_sweep_assemble's rule)
+template <bool twice, bool pairs = false>        // twice: OH = 2 H and OW = 2 W (image sides that are multiples of 32: the shift form, no float index arithmetic)
 __global__ __launch_bounds__(256) void upsample_add_kernel(const bf16_t* __restrict__ in, const bf16_t* __restrict__ fpn, const long long* __restrict__ rows,
-                                                            int BQ, int Q, int H, int W, int OH, int OW, int C, bf16_t* __restrict__ out) {
+                                                            int BQ, int Q, int H, int W, int OH, int OW, int C, bf16_t* __restrict__ out,
+                                                            const int32_t* __restrict__ pair_image, int n_images, int32_t* __restrict__ status) {
     const int c8 = C >> 3;
     const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
     const long long total = (long long)BQ * OH * OW * c8;
@@ -331,8 +340,19 @@ __global__ __launch_bounds__(256) void upsample_add_kernel(const bf16_t* __restr
         const int ys = twice ? (Y >> 1) : nearest_src(Y, sy, H), xs = twice ? (X >> 1) : nearest_src(X, sx, W);
         float a[8], f[8];
         unpack8(*reinterpret_cast<const uint4*>(in + ((((size_t)bq * H + ys) * W + xs) * C) + cc * 8), a);
-        const int img = (int)((rows != nullptr ? rows[bq] : (long long)bq) / Q);
-        unpack8(*reinterpret_cast<const uint4*>(fpn + ((((size_t)img * OH + Y) * OW + X) * C) + cc * 8), f);
+        if constexpr (pairs) {
+            const int pair = bq / Q, img = pair_image[pair];
+            if ((unsigned)img < (unsigned)n_images) {
+                unpack8(*reinterpret_cast<const uint4*>(fpn + ((((size_t)img * OH + Y) * OW + X) * C) + cc * 8), f);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) f[j] = 0.f;
+                if (cc == 0 && X == 0 && Y == 0 && bq == pair * Q) atomicMax(status, pair + 1);
+            }
+        } else {
+            const int img = (int)((rows != nullptr ? rows[bq] : (long long)bq) / Q);
+            unpack8(*reinterpret_cast<const uint4*>(fpn + ((((size_t)img * OH + Y) * OW + X) * C) + cc * 8), f);
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) a[j] += f[j];
         *reinterpret_cast<uint4*>(out + (size_t)i * 8) = pack8(a);
@@ -674,10 +694,10 @@ static int launch_resize_add(const char* what, const void* in, const void* fpn, 
     TOIST_REQUIRE(in && fpn && out && n > 0 && Q > 0 && H > 0 && W > 0 && OH >= H && OW >= W && (C % 8) == 0 && (rows || (n % Q) == 0), "%s: bad shape", what);
     if (OH == 2 * H && OW == 2 * W)
         hipLaunchKernelGGL(upsample_add_kernel<true>, dim3(grid_cap((long long)n * OH * OW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)in, (const bf16_t*)fpn, (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out);
+                           (const bf16_t*)in, (const bf16_t*)fpn, (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out, nullptr, 0, nullptr);
     else
         hipLaunchKernelGGL(upsample_add_kernel<false>, dim3(grid_cap((long long)n * OH * OW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)in, (const bf16_t*)fpn, (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out);
+                           (const bf16_t*)in, (const bf16_t*)fpn, (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out, nullptr, 0, nullptr);
     return check_launch(what);
 }
 extern "C" int toist_upsample_add(const void* in, const void* fpn, int BQ, int Q, int H, int W, int C, void* out, void* stream) {
@@ -689,6 +709,19 @@ extern "C" int toist_upsample_add_rows(const void* in, const void* fpn, const in
 }
 extern "C" int toist_resize_add(const void* in, const void* fpn, const int64_t* rows, int n, int Q, int H, int W, int OH, int OW, int C, void* out, void* stream) {
     return launch_resize_add("toist_resize_add", in, fpn, rows, n, Q, H, W, OH, OW, C, out, stream);
+}
+extern "C" int toist_resize_add_pairs(const void* in, const void* fpn, const int32_t* pair_image, int n_images, int n, int Q, int H, int W, int OH, int OW,
+                                      int C, void* out, int32_t* status, void* stream) {
+    TOIST_REQUIRE(in && fpn && out && pair_image && status && n_images > 0 && n > 0 && Q > 0 && H > 0 && W > 0 && OH >= H && OW >= W && (C % 8) == 0 &&
+                      (n % Q) == 0, "toist_resize_add_pairs: bad shape");
+    const dim3 grid(grid_cap((long long)n * OH * OW * (C / 8), 8192));
+    if (OH == 2 * H && OW == 2 * W)
+        hipLaunchKernelGGL((upsample_add_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (const bf16_t*)fpn,
+                           (const long long*)nullptr, n, Q, H, W, OH, OW, C, (bf16_t*)out, pair_image, n_images, status);
+    else
+        hipLaunchKernelGGL((upsample_add_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (const bf16_t*)fpn,
+                           (const long long*)nullptr, n, Q, H, W, OH, OW, C, (bf16_t*)out, pair_image, n_images, status);
+    return check_launch("toist_resize_add_pairs");
 }
 static int launch_resize_add_bwd(const char* what, const void* dout, int BQ, int H, int W, int OH, int OW, int C, void* din, void* stream) {
     TOIST_REQUIRE(dout && din && BQ > 0 && H > 0 && W > 0 && OH >= H && OW >= W && (C % 8) == 0, "%s: bad shape", what);

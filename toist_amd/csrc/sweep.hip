@@ -96,9 +96,50 @@ __global__ __launch_bounds__(SW_THREADS) void sweep_assemble_bwd_kernel(const ui
     }
 }
 
+// Row gather by a pair table: dst[p, :] = src[pair_image[p], :] for rows of `words` elements of WORD (16, 4 or 1 bytes: the launcher takes the widest
+// that divides the row's byte count and both base addresses, so any row size and alignment is served).  One element per thread and trip, the
+// elements go round the grid in a stride loop; the table entry of a row comes out of the L1.  A pure copy: every output element is written, a pair
+// whose entry is outside [0, n_images) is never used as an index, becomes zeros and puts p + 1 into *status (atomicMax), as in the assembly above.
+template <typename WORD>
+__global__ __launch_bounds__(SW_THREADS) void sweep_gather_kernel(const WORD* __restrict__ src, const int32_t* __restrict__ pair_image, int n_images,
+                                                                   long long words, long long total, WORD* __restrict__ dst,
+                                                                   int32_t* __restrict__ status) {
+    for (long long e = (long long)blockIdx.x * SW_THREADS + threadIdx.x; e < total; e += (long long)gridDim.x * SW_THREADS) {
+        const long long p = e / words, c = e - p * words;
+        const int i = pair_image[p];
+        WORD v{};
+        if ((unsigned)i < (unsigned)n_images) v = src[(size_t)i * words + c];          // (computed only from a checked index)
+        else if (c == 0) atomicMax(status, (int)p + 1);
+        dst[e] = v;
+    }
+}
+
 }  // namespace toist
 
 using namespace toist;
+
+extern "C" int toist_sweep_gather(const void* src, const int32_t* pair_image, int n_images, int P, long long row_bytes, void* dst, int32_t* status,
+                                  void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    TOIST_REQUIRE(n_images > 0 && P >= 0 && row_bytes > 0, "toist_sweep_gather: bad extents n_images=%d P=%d row_bytes=%lld", n_images, P, row_bytes);
+    TOIST_REQUIRE(row_bytes < (1ll << 40) && (long long)n_images * row_bytes < (1ll << 46), "toist_sweep_gather: rows of %lld bytes are too long", row_bytes);
+    if (P == 0) return TOIST_OK;
+    TOIST_REQUIRE(src && pair_image && dst && status, "toist_sweep_gather: null pointer");
+    const uintptr_t low = (uintptr_t)src | (uintptr_t)dst | (uintptr_t)row_bytes;
+    const int wb = (low & 15) == 0 ? 16 : (low & 3) == 0 ? 4 : 1;
+    const long long words = row_bytes / wb, total = words * P;
+    const long long want = (total + SW_THREADS - 1) / SW_THREADS;
+    const dim3 grid((unsigned)(want < SW_MAX_BLOCKS ? want : SW_MAX_BLOCKS));
+    if (wb == 16)
+        hipLaunchKernelGGL(sweep_gather_kernel<uint4>, grid, dim3(SW_THREADS), 0, stream, (const uint4*)src, pair_image, n_images, words, total, (uint4*)dst, status);
+    else if (wb == 4)
+        hipLaunchKernelGGL(sweep_gather_kernel<uint32_t>, grid, dim3(SW_THREADS), 0, stream, (const uint32_t*)src, pair_image, n_images, words, total,
+                           (uint32_t*)dst, status);
+    else
+        hipLaunchKernelGGL(sweep_gather_kernel<uint8_t>, grid, dim3(SW_THREADS), 0, stream, (const uint8_t*)src, pair_image, n_images, words, total,
+                           (uint8_t*)dst, status);
+    return check_launch("toist_sweep_gather");
+}
 
 extern "C" int toist_sweep_assemble(const void* img_tok, const void* img_pos, const uint8_t* img_pad, int B, int HW, const void* txt_tok,
                                     const uint8_t* txt_pad, int T, int L, const int32_t* pair_image, const int32_t* pair_caption, int P, int D,

@@ -5,7 +5,8 @@ from types import SimpleNamespace
 
 import torch
 
-from .captured import CapturedDistillStep, CapturedEvalStep, CapturedPairTrainStep, CapturedSweepStep, CapturedTrainStep, size_pairs  # noqa: F401
+from .captured import (CapturedDistillStep, CapturedEvalStep, CapturedMaskSweepStep, CapturedPairTrainStep, CapturedSweepStep, CapturedTrainStep,  # noqa: F401
+                       size_pairs)
 from .transformer import TokenizedText
 
 
@@ -237,7 +238,7 @@ def _captured_eval_batch(captured, batch, rows=False):
 
 @torch.no_grad()
 def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criterion=None, captured=None, max_pairs=None, tokenized=None, observe=None,
-                   evaluator=None):
+                   evaluator=None, pairs_per_pass=8):
     """Task-sweep inference: every task's caption on every image of every batch, at the cost of ONE image pass per image and ONE text pass per
     caption for the whole loop (the reference's loader makes one sample per (image, task): engine.py:253-342 runs the ResNet and RoBERTa once per pair).
     tasks: [(name, caption[, dataset_name])]; batches yield dicts with "samples", "image_ids", "orig_sizes" ((h, w) per image, host values) and
@@ -253,8 +254,23 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
     evaluator: a coco_eval.SweepEvaluator holding every task's ground truth -- each pair stage's rows are scored on the device inside the loop
     (update_rows: two launches per stage, read in place, so the captured step's reused output buffers are consumed before the next replay), no keyed
     results are kept, and the function returns evaluator.summarize() after synchronize_between_processes() and accumulate(): {"tasks": {name: the
-    12 COCO stats}, "mAP50", "mAP"}."""
+    12 COCO stats}, "mAP50", "mAP"}.
+    A model with a mask head (DETRsegm): the pair stages go through mask_sweep_pairs / decode_mask_sweep -- an image's FPN terms computed once, the
+    per-map program in passes of `pairs_per_pass` pairs -- and PostProcessSegm(packed=True): every result gains "mask_bits" int64 [Q, w, ceil(h / 64)]
+    and "mask_size" (h, w).  The batches then also carry "sizes": each image's (h, w) inside the padded batch, host values.  postprocessor may be
+    the dict of build_postprocessors (its "segm" entry gives the threshold).  captured: a CapturedMaskSweepStep.  evaluator: a SweepEvaluator built
+    with iou_types holding "segm" scores the planes in place too, and summarize() carries the mask numbers under "segm"."""
     from . import kernels, sweep
+    from .postprocessors import PostProcessSegm
+    segm = hasattr(model, "decode_mask_sweep")
+    det = model.detr if segm else model
+    seg_post = None
+    if isinstance(postprocessor, dict):
+        seg_post, postprocessor = postprocessor.get("segm"), postprocessor["bbox"]
+    if segm:
+        seg_post = PostProcessSegm(threshold=seg_post.threshold if seg_post is not None else 0.5, packed=True)
+        if captured is not None and not isinstance(captured, CapturedMaskSweepStep):
+            raise ValueError("a model with a mask head sweeps through a CapturedMaskSweepStep (captured=)")
     tasks = [tuple(t) for t in tasks]
     if not tasks or any(len(t) not in (2, 3) for t in tasks):
         raise ValueError("tasks is a non-empty list of (name, caption) or (name, caption, dataset_name)")
@@ -278,33 +294,63 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
         if len(orig) != B or samples.tensors.shape[0] != B:
             raise ValueError(f"a batch of {samples.tensors.shape[0]} images with {B} image ids and {len(orig)} original sizes")
         pi, pc, live = sweep.pair_tables(B, T, batch.get("pairs"))
+        crop = None
+        if segm:
+            if "sizes" not in batch:
+                raise ValueError("a sweep with a mask head needs batch['sizes']: each image's (h, w) inside the padded batch")
+            crop = size_pairs(batch["sizes"])
+            if len(crop) != B:
+                raise ValueError(f"a batch of {B} images with {len(crop)} sizes")
         if captured is not None and evaluator is not None:
+            if segm:
+                rows, masks, pi, pc, live = captured.step_rows(samples, text, orig, crop, pairs=batch.get("pairs"))
+                evaluator.update_rows(rows, image_ids, names, pi, pc, live, masks=masks)
+                continue
             rows, pi, pc, live = captured.step_rows(samples, text, orig, pairs=batch.get("pairs"))
             evaluator.update_rows(rows, image_ids, names, pi, pc, live)
             continue
         if captured is not None:
-            results, pi, pc, live = captured.step(samples, text, orig, pairs=batch.get("pairs"))
+            if segm:
+                results, pi, pc, live = captured.step(samples, text, orig, crop, pairs=batch.get("pairs"))
+            else:
+                results, pi, pc, live = captured.step(samples, text, orig, pairs=batch.get("pairs"))
             out.update(sweep.keyed_results(results, image_ids, names, pi, pc, live))
             continue
         samples = samples.to(device)
         if not hasattr(text, "flat"):
-            text = model.sweep_text(text, device=device)          # once: the captions do not change
+            text = det.sweep_text(text, device=device)            # once: the captions do not change
             if text.key_pad.shape[0] != T:
                 raise ValueError(f"{T} tasks but {text.key_pad.shape[0]} tokenized captions")
-        state = model.sweep_images(samples)
+        state = det.sweep_images(samples, levels=(1, 2, 3, 4) if segm else (4,))
         for lo, hi in _sweep_groups(pi, pc, B, T, max_pairs, product=batch.get("pairs") is None):
             gi, gc = pi[lo:hi], pc[lo:hi]
-            mc = model.sweep_pairs(state, text, gi, gc)
+            mc = model.mask_sweep_pairs(state, text, gi, gc) if segm else model.sweep_pairs(state, text, gi, gc)
             if cluster_criterion is not None:
                 mc = cluster_criterion.infer_choice(mc, [dataset_names[t] for t in gc.tolist()], [captions[t] for t in gc.tolist()])
-            outputs = model.decode(mc)
-            sizes = torch.tensor([orig[i] for i in gi.tolist()], dtype=torch.int64).to(device, non_blocking=True)
+            outputs = model.decode_mask_sweep(mc, pairs_per_pass) if segm else model.decode(mc)
+            rows_hw = [orig[i] for i in gi.tolist()]
+            sizes = torch.tensor(rows_hw, dtype=torch.int64).to(device, non_blocking=True)
             results = postprocessor(outputs, sizes)
+            masks = None
+            if segm:                                            # one launch for the group's rows; the first resize target is the padded batch
+                Q = outputs["pred_masks"].shape[1]
+                cap_hw = (max(h for h, _ in rows_hw), max(w for _, w in rows_hw))
+                cap_words = Q * cap_hw[1] * kernels.mask_words(cap_hw[0])
+                table = torch.tensor([crop[i] + orig[i] for i in gi.tolist()], dtype=torch.int64).to(device, non_blocking=True)
+                bits = torch.empty(len(rows_hw) * cap_words, dtype=torch.int64, device=device)
+                results = seg_post.forward_static(results, outputs, table, rows_hw, tuple(samples.tensors.shape[-2:]), cap_hw, out=bits,
+                                                  capacity_words=cap_words)
+                if evaluator is not None and "segm" in getattr(evaluator, "iou_types", ()):
+                    from .coco_eval import RowMasks
+                    masks = RowMasks(bits, cap_words, sizes, rows_hw)
             if observe is not None:
                 observe(mc, outputs, gi, gc)
             if evaluator is not None:                           # the postprocessor's rows, stacked: what kernels.postprocess's dict holds
                 rows = {"scores": torch.stack([r["scores"] for r in results]), "boxes": torch.stack([r["boxes"] for r in results])}
-                evaluator.update_rows(rows, image_ids, names, gi, gc)
+                if masks is not None:
+                    evaluator.update_rows(rows, image_ids, names, gi, gc, masks=masks)
+                else:
+                    evaluator.update_rows(rows, image_ids, names, gi, gc)
             else:
                 out.update(sweep.keyed_results(results, image_ids, names, gi, gc))
         kernels.sweep_check()     # (one 4-byte read: it synchronises) a pair table entry the launch refused

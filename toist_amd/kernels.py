@@ -1203,6 +1203,86 @@ def sweep_assemble_bwd(d_seq, pair_image, pair_caption, B, HW, T, L, want_img=Tr
     return d_img, d_txt
 
 
+# -- the mask head of a sweep: per-image terms found through the pair table (csrc/maskstage.hip, csrc/segm.hip, csrc/sweep.hip).  All three share the
+# status word of sweep_assemble (sweep_check reads and clears it) and its rule for a table entry outside [0, n_images): never an index, a zero term
+def _pair_table(what, pair_image, pairs):
+    if not pair_image.is_cuda or pair_image.dtype != torch.int32 or pair_image.dim() != 1 or pair_image.numel() != pairs or not pair_image.is_contiguous():
+        raise ValueError(f"{what}: pair_image is a contiguous int32 vector of {pairs} entries on the device (got {pair_image.dtype} {tuple(pair_image.shape)})")
+    status = sweep_status(pair_image.device)
+    if status is None:
+        raise RuntimeError(f"{what}: the first sweep launch on a device cannot be captured (its status word is allocated outside any graph)")
+    return status
+
+
+def mask_stage_fwd_pairs(src, src_stats, gamma, beta, fpn_conv, w, bias, out, out_stats, N, Q, H, W, c_in, c_out, w_rows, gn_in, up, pair_image, eps=1e-5):
+    """mask_stage_fwd for the maps of a sweep's pairs (include/toist_hip.h: toist_mask_stage_fwd_pairs): fpn_conv is [n_images, H, W, c_out] and map n adds
+    the term of image pair_image[n // Q] (int32 [N // Q] ON THE DEVICE).  The two `up` stages, (64 -> 32) and (32 -> 16, gn_in); out_lay has no image
+    term and keeps mask_stage_fwd.  Shapes and contiguity are checked here, before the launch (ValueError)."""
+    what = "mask_stage_fwd_pairs"
+    N, Q, H, W = int(N), int(Q), int(H), int(W)
+    if not up or (c_in, c_out, bool(gn_in)) not in ((64, 32, False), (32, 16, True)) or w_rows != c_out:
+        raise ValueError(f"{what}: the stages with an image term are (64, 32, up) and (32, 16, gn_in, up) (got c_in {c_in}, c_out {c_out}, w_rows {w_rows}, gn_in {gn_in}, up {up})")
+    if N <= 0 or Q <= 0 or N % Q or H <= 0 or W <= 0 or H % 2 or W % 2:
+        raise ValueError(f"{what}: N = {N} maps of Q = {Q} per pair at {H} x {W}: N % Q == 0 and even sizes")
+    if fpn_conv.dim() != 4 or tuple(fpn_conv.shape[1:]) != (H, W, c_out) or fpn_conv.shape[0] < 1:
+        raise ValueError(f"{what}: fpn_conv is [n_images, {H}, {W}, {c_out}] (got {tuple(fpn_conv.shape)})")
+    if src.numel() != N * (H // 2) * (W // 2) * c_in or out.numel() != N * H * W * c_out or out_stats.numel() != N * 16 or tuple(w.shape) != (c_out, 3, 3, c_in):
+        raise ValueError(f"{what}: src [{N}, {H // 2}, {W // 2}, {c_in}], w [{c_out}, 3, 3, {c_in}], out [{N}, {H}, {W}, {c_out}] and out_stats [{N}, 8, 2] "
+                         f"(got {tuple(src.shape)}, {tuple(w.shape)}, {tuple(out.shape)}, {tuple(out_stats.shape)})")
+    if gn_in and (src_stats is None or src_stats.numel() != N * 16 or gamma is None or gamma.numel() != c_in or beta is None or beta.numel() != c_in):
+        raise ValueError(f"{what}: gn_in needs src_stats [{N}, 8, 2] and gamma / beta [{c_in}]")
+    if bias is not None and bias.numel() != c_out:
+        raise ValueError(f"{what}: bias is [{c_out}]")
+    for t in (src, src_stats, gamma, beta, fpn_conv, w, bias, out, out_stats):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{what}: every tensor must be contiguous")
+    status = _pair_table(what, pair_image, N // Q)
+    _lib.check(_lib.lib().toist_mask_stage_fwd_pairs(_p(src, BF16), _p(src_stats, F32), _p(gamma, F32), _p(beta, F32), _p(fpn_conv, BF16), _p(w, BF16),
+                                                     _p(bias, F32), _p(out, BF16), _p(out_stats, F32), N, Q, H, W, c_in, c_out, w_rows, 1 if gn_in else 0,
+                                                     1, eps, _p(pair_image, torch.int32), int(fpn_conv.shape[0]), _p(status, torch.int32), _stream()),
+               "toist_mask_stage_fwd_pairs")
+
+
+def resize_add_pairs(inp, fpn, pair_image, n, Q, H, W, OH, OW, C, out):
+    """resize_add (rows = None) for the maps of a sweep's pairs (include/toist_hip.h: toist_resize_add_pairs): out [n, OH, OW, C] = fpn[pair_image[map // Q]]
+    + nearest-resized inp [n, H, W, C]; fpn holds n_images terms of OH * OW * C elements, pair_image int32 [n // Q] ON THE DEVICE."""
+    what = "resize_add_pairs"
+    n, Q, H, W, OH, OW, C = (int(v) for v in (n, Q, H, W, OH, OW, C))
+    if n <= 0 or Q <= 0 or n % Q or H <= 0 or W <= 0 or OH < H or OW < W or C <= 0 or C % 8:
+        raise ValueError(f"{what}: n = {n} maps of Q = {Q} per pair, {H} x {W} -> {OH} x {OW}, C = {C}: n % Q == 0, a target no smaller than the source, C % 8 == 0")
+    per = OH * OW * C
+    if inp.numel() != n * H * W * C or out.numel() != n * per or fpn.numel() == 0 or fpn.numel() % per:
+        raise ValueError(f"{what}: inp [{n}, {H}, {W}, {C}], fpn [n_images, {OH}, {OW}, {C}] and out [{n}, {OH}, {OW}, {C}] "
+                         f"(got {tuple(inp.shape)}, {tuple(fpn.shape)}, {tuple(out.shape)})")
+    if not (inp.is_contiguous() and fpn.is_contiguous() and out.is_contiguous()):
+        raise ValueError(f"{what}: every tensor must be contiguous")
+    status = _pair_table(what, pair_image, n // Q)
+    _lib.check(_lib.lib().toist_resize_add_pairs(_p(inp, BF16), _p(fpn, BF16), _p(pair_image, torch.int32), fpn.numel() // per, n, Q, H, W, OH, OW, C,
+                                                 _p(out, BF16), _p(status, torch.int32), _stream()), "toist_resize_add_pairs")
+
+
+def sweep_gather(src, pair_image, out=None):
+    """out[p] = src[pair_image[p]] in one launch (include/toist_hip.h: toist_sweep_gather): src [n_images, ...] of any dtype, row size and alignment,
+    pair_image int32 [P] ON THE DEVICE -> [P, ...]; `out` = such a tensor to write into.  Every output byte is written; a refused pair's row is zeros
+    and the status word says so (sweep_check) -- unlike torch.index_select, whose device-side assert aborts the process."""
+    what = "sweep_gather"
+    if src.dim() < 1 or src.shape[0] < 1 or not src.is_contiguous():
+        raise ValueError(f"{what}: src is a contiguous [n_images, ...] tensor (got {tuple(src.shape)})")
+    P = int(pair_image.numel())
+    shape = (P,) + tuple(src.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=src.dtype, device=src.device)
+    if tuple(out.shape) != shape or out.dtype != src.dtype or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f"{what}: out is a contiguous {src.dtype} tensor of shape {shape} beside src (got {out.dtype} {tuple(out.shape)})")
+    row_bytes = src[0].numel() * src.element_size()
+    if row_bytes <= 0:
+        raise ValueError(f"{what}: rows of no bytes")
+    status = _pair_table(what, pair_image, P)
+    _lib.check(_lib.lib().toist_sweep_gather(_p(src), _p(pair_image, torch.int32), int(src.shape[0]), P, row_bytes, _p(out), _p(status, torch.int32),
+                                             _stream()), "toist_sweep_gather")
+    return out
+
+
 def mask_pack(dense):
     """[n, h, w] bool / uint8 -> bit planes."""
     n, h, w = dense.shape

@@ -313,13 +313,17 @@ class MDETR(nn.Module):
         if tensor is not None and not tensor.is_cuda:
             raise RuntimeError("the task sweep needs device tensors (got a CPU tensor); there is no CPU fallback")
 
-    def sweep_images(self, samples):
-        """The image stage: backbone, input_proj, position tokens (no caption tail), mask -> sweep.SweepImages, reusable for any captions."""
+    def sweep_images(self, samples, levels=(4,)):
+        """The image stage: backbone, input_proj, position tokens (no caption tail), mask -> sweep.SweepImages, reusable for any captions.
+        levels: the backbone levels kept in SweepImages.feats, the last one C5 (a mask head reads (1, 2, 3, 4): DETRsegm.mask_sweep_stages)."""
         from .sweep import SweepImages
         if not isinstance(samples, NestedTensor):
             samples = NestedTensor.from_tensor_list(samples)
+        levels = tuple(levels)
+        if not levels or levels[-1] != 4:
+            raise ValueError(f"sweep_images: levels = {levels} must end with 4 (C5 feeds input_proj)")
         self._sweep_ready(samples.tensors)
-        feats = self._backbone_stage(samples)
+        feats = self._backbone_stage(samples, levels, premasked=(len(levels) - 1,))
         return SweepImages(*self._image_tokens(feats[-1], samples.mask), feats)
 
     def sweep_text(self, captions, device=None):

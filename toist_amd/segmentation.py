@@ -479,11 +479,198 @@ class DETRsegm(nn.Module):
         out["pred_masks"] = self._masks(stack[-1], mem, src, c4, c3, c2, nat["feat_mask"], B, Q, h, w)
         return out
 
-    # ---- task sweep: detection models only ------------------------------------------------------------------
+    # ---- task sweep with the mask head: an image's terms computed once, shared by its pairs (inference only) ---------------
+    def _masks_sweep(self, hs_last, memory, S, src_proj, c4, c3, c2, feat_mask, pair_image, Q, h, w, pairs_per_pass, mask_sink=None):
+        """_masks for the P (image, caption) pairs of a sweep, forward only: hs_last [P*Q, d], memory [P*S, d] (the first h*w rows of a pair are its image
+        rows), src_proj [B*h*w, d], c4 / c3 / c2 and feat_mask per IMAGE (B of them), pair_image int32 [P] on the device -> mask logits [P, Q, Hm, Wm] f32.
+        Per image, once: lay1 on src_proj, the three adapter terms, lay4 / lay5 of the last two (fused tail), the key-padding bytes.  Per pair, in
+        passes of at most pairs_per_pass pairs, each on its slice of the device table: the attention map and every per-map tensor -- the kernels find a
+        map's image as pair_image[map // Q] (toist_sweep_gather, toist_resize_add_pairs, toist_mask_stage_fwd_pairs).
+        mask_sink: callable(lo, hi, logits [hi - lo, Q, Hm, Wm]) called behind every pass; the logits of the P pairs are then never held together
+        and None is returned."""
+        from .sweep import pair_passes
+        H = self.bbox_attention.num_heads
+        d = self.bbox_attention.hidden_dim
+        dh = d // H
+        HW = h * w
+        ld = ops.round8(HW)
+        scale = self.bbox_attention.normalize_fact
+        named = OrderedDict(("bbox_attention." + n, p) for n, p in self.bbox_attention.named_parameters())
+        named.update(("mask_head." + n, p) for n, p in self.mask_head.named_parameters())
+        transforms = {n: _krsc_bf16 for n, p in named.items() if p.dim() == 4}
+        key_pad = feat_mask.flatten(1).to(torch.uint8).contiguous()
+        dev = hs_last.device
+        B, P = c4.shape[0], pair_image.numel()
+        passes = pair_passes(P, pairs_per_pass)
+
+        def prog(tape, ps, hs, mem, src, f4, f3, f2):
+            A = lambda n: ps["bbox_attention." + n]
+            M = lambda n: ps["mask_head." + n]
+            f32 = lambda n: M(n).f32
+
+            def conv_gn_relu(x, wk, bias, i, n, H_, W_, extra_res=None, res_bcast=None):
+                """relu(GN8(conv3x3(x) + bias [+ broadcast residual])) of n maps: _conv_gn_relu's forward"""
+                pre = ops.conv2d(x, wk, pad=1, shift=(bias if extra_res is None else None), res=extra_res, res_bcast=res_bcast)
+                stats = torch.empty(n, 8, 2, dtype=torch.float32, device=dev)
+                y = torch.empty_like(pre)
+                k.groupnorm_fwd(pre, f32(f"gn{i}.weight"), f32(f"gn{i}.bias"), n, H_ * W_, wk.shape[0], 8, 1e-5, True, y, stats)
+                return y
+
+            def adapter(feat, i):
+                Wa = M(f"adapter{i}.weight")
+                Cx, Cin_f = Wa.w.shape[0], feat.data.shape[-1]
+                return ops.linear(feat.data.view(-1, Cin_f), Wa.w.view(Cx, Cin_f), f32(f"adapter{i}.bias"))
+
+            # ---- per image, once ----
+            W1 = M("lay1.weight")
+            w1_img, w1_att = W1.w[..., :d].contiguous(), W1.w[..., d:d + H].contiguous()
+            y_img = ops.conv2d(src.data.view(B, h, w, d), w1_img, pad=1, shift=f32("lay1.bias"))            # [B,h,w,264]
+            C1 = w1_img.shape[0]
+            (h4, w4), (h3, w3), (Hm, Wm) = f4.data.shape[1:3], f3.data.shape[1:3], f2.data.shape[1:3]
+            doubling = (h4, w4, h3, w3, Hm, Wm) == (2 * h, 2 * w, 4 * h, 4 * w, 8 * h, 8 * w)
+            f1 = adapter(f4, 1)
+            fa = adapter(f3, 2)
+            fb = adapter(f2, 3)
+            W2, W3, W4, W5, Wo = M("lay2.weight"), M("lay3.weight"), M("lay4.weight"), M("lay5.weight"), M("out_lay.weight")
+            C2, C3, C4, C5 = W2.w.shape[0], W3.w.shape[0], W4.w.shape[0], W5.w.shape[0]
+            fused = FUSED_TAIL and doubling and (C3, C4, C5) == (64, 32, 16) and W4.w.shape[-1] == 64 and W5.w.shape[-1] == 32 and Wo.w.shape[0] == 1
+            if fused:
+                fa_conv = ops.conv2d(fa.view(B, h3, w3, C3), W4.w, pad=1, shift=f32("lay4.bias"))
+                fb_conv = ops.conv2d(fb.view(B, Hm, Wm, C4), W5.w, pad=1, shift=f32("lay5.bias"), tile=64)
+            else:
+                wo8 = torch.zeros(8, 3, 3, C5, dtype=BF16, device=dev)
+                wo8[:1] = Wo.w
+                bo8 = torch.zeros(8, dtype=torch.float32, device=dev)
+                bo8[:1] = f32("out_lay.bias")
+            # ---- the attention map's projections: per pair, one GEMM each over all of them ----
+            q = engine.linear_chain(tape, hs, [(A("q_linear.weight"), A("q_linear.bias"), k.ACT_NONE, False)]).data
+            if S == HW:
+                mem_img = mem.data
+            else:                                      # the image rows of every pair's sequence
+                mem_img = mem.data.view(P, S, d)[:, :HW].reshape(P * HW, d)
+            kk = engine.linear_chain(tape, engine.Var(mem_img), [(A("k_linear.weight"), A("k_linear.bias"), k.ACT_NONE, False)]).data
+            masks = torch.empty(P, Q, Hm, Wm, dtype=torch.float32, device=dev) if mask_sink is None else None
+
+            # ---- per pass: the per-map program on a slice of the device table ----
+            for lo, hi in passes:
+                n = hi - lo
+                nQ = n * Q
+                table = pair_image[lo:hi]
+                m_pass = masks[lo:hi] if mask_sink is None else torch.empty(n, Q, Hm, Wm, dtype=torch.float32, device=dev)
+                kp = k.sweep_gather(key_pad, table)                                                     # [n, HW] bytes
+                yi = k.sweep_gather(y_img.view(B, HW * C1), table)                                       # [n, HW * 264]
+                scores = torch.empty(n, Q, H, ld, dtype=BF16, device=dev)
+                k.gemm(Q, HW, dh, k.A_ROWK, k.operand(q[lo * Q:hi * Q], d, bs_outer=Q * d, bs_inner=dh), k.B_ROWK,
+                       k.operand(kk[lo * HW:hi * HW], d, bs_outer=HW * d, bs_inner=dh), scores, H * ld, batch=n * H, batch_inner=H,
+                       cs_outer=Q * H * ld, cs_inner=ld, alpha=scale, tile=64)
+                prob = torch.empty(nQ, h, w, H, dtype=BF16, device=dev)
+                k.attnmap_softmax_fwd(scores, kp, n, Q, H, HW, ld, prob)
+                del scores
+                a1 = conv_gn_relu(prob, w1_att, None, 1, nQ, h, w, extra_res=yi.view(n * HW, C1), res_bcast=(Q * HW, HW))
+                del prob, yi
+                a2 = conv_gn_relu(a1, W2.w, f32("lay2.bias"), 2, nQ, h, w)
+                del a1
+                up = torch.empty(nQ, h4, w4, C2, dtype=BF16, device=dev)
+                k.resize_add_pairs(a2, f1, table, nQ, Q, h, w, h4, w4, C2, up)
+                del a2
+                a3 = conv_gn_relu(up, W3.w, f32("lay3.bias"), 3, nQ, h4, w4)
+                del up
+                if fused:
+                    pre4 = torch.empty(nQ, h3, w3, C4, dtype=BF16, device=dev)
+                    st4 = torch.empty(nQ, 8, 2, dtype=torch.float32, device=dev)
+                    k.mask_stage_fwd_pairs(a3, None, None, None, fa_conv, W4.w, None, pre4, st4, nQ, Q, h3, w3, C3, C4, C4, False, True, table)
+                    del a3
+                    pre5 = torch.empty(nQ, Hm, Wm, C5, dtype=BF16, device=dev)
+                    st5 = torch.empty(nQ, 8, 2, dtype=torch.float32, device=dev)
+                    k.mask_stage_fwd_pairs(pre4, st4, f32("gn4.weight"), f32("gn4.bias"), fb_conv, W5.w, None, pre5, st5, nQ, Q, Hm, Wm, C4, C5, C5, True, True,
+                                           table)
+                    del pre4
+                    k.mask_stage_fwd(pre5, st5, f32("gn5.weight"), f32("gn5.bias"), None, Wo.w, f32("out_lay.bias"), m_pass, None, nQ, Q, Hm, Wm, C5, 1, 1,
+                                     True, False)
+                    del pre5
+                    if mask_sink is not None:
+                        mask_sink(lo, hi, m_pass)
+                    continue
+                up = torch.empty(nQ, h3, w3, C3, dtype=BF16, device=dev)
+                k.resize_add_pairs(a3, fa, table, nQ, Q, h4, w4, h3, w3, C3, up)
+                del a3
+                a4 = conv_gn_relu(up, W4.w, f32("lay4.bias"), 4, nQ, h3, w3)
+                up = torch.empty(nQ, Hm, Wm, C4, dtype=BF16, device=dev)
+                k.resize_add_pairs(a4, fb, table, nQ, Q, h3, w3, Hm, Wm, C4, up)
+                del a4
+                a5 = conv_gn_relu(up, W5.w, f32("lay5.bias"), 5, nQ, Hm, Wm)
+                del up
+                o8 = ops.conv2d(a5, wo8, pad=1, shift=bo8)                                       # [nQ,Hm,Wm,8] bf16
+                m_pass.copy_(o8[..., 0].view(n, Q, Hm, Wm))
+                del a5, o8
+                if mask_sink is not None:
+                    mask_sink(lo, hi, m_pass)
+            return [engine.Var(masks if masks is not None else torch.empty(0, device=dev))], None
+
+        (masks,) = functions.run_program(prog, named, [hs_last, memory, src_proj, c4, c3, c2], cache=self._cache, training=False, transforms=transforms)
+        return masks if mask_sink is None else None
+
+    def mask_sweep_stages(self, samples, captions):
+        """The image stage with every FPN level and the text stage, side by side (MDETR.sweep_stages for a mask head) -> (sweep.SweepImages whose feats are
+        (c2, c3, c4, c5), EncodedText).  captions may be an EncodedText kept from an earlier call."""
+        det = self.detr
+        if not isinstance(samples, NestedTensor):
+            samples = NestedTensor.from_tensor_list(samples)
+        det._sweep_ready(samples.tensors)
+        text, side = det._text_branch(captions, samples.tensors.device)
+        state = det.sweep_images(samples, levels=(1, 2, 3, 4))
+        det._join(side)
+        return state, text
+
+    def mask_sweep_pairs(self, image_state, text, pair_image, pair_caption, out=None, tokenized=None, check=None):
+        """MDETR.sweep_pairs on stages kept from mask_sweep_stages -> the memory cache of P rows that decode_mask_sweep takes: its `_native` carries
+        features (all four levels), feat_mask and src_proj per IMAGE and the device tables pair_image / pair_caption."""
+        if len(image_state.feats) != 4:
+            raise ValueError("mask_sweep_pairs needs the image stage of mask_sweep_stages: the backbone levels (1, 2, 3, 4), not only C5")
+        return self.detr.sweep_pairs(image_state, text, pair_image, pair_caption, out=out, tokenized=tokenized, check=check)
+
+    def encode_mask_sweep(self, samples, captions, pairs=None):
+        """encode for a task sweep with the mask head: ONE image pass per image (backbone levels 1-4, input_proj, positions), ONE text pass per caption,
+        the pair stage over `pairs` (a list of (image, caption) indices; default every caption on every image, image-major) -> the memory cache of P
+        rows.  Inference only (model.eval() under torch.no_grad())."""
+        from . import sweep
+        state, text = self.mask_sweep_stages(samples, captions)
+        pi, pc, _ = sweep.pair_tables(state.tok.shape[0], text.key_pad.shape[0], pairs)
+        return self.mask_sweep_pairs(state, text, pi, pc)
+
+    def decode_mask_sweep(self, memory_cache, pairs_per_pass=8, mask_sink=None):
+        """decode for encode_mask_sweep's cache -> MDETR.decode's outputs of the P pairs + "pred_masks" [P, Q, Hm, Wm] f32.  The per-image terms of the
+        mask head (lay1 on src_proj, the three adapter terms, lay4 / lay5 of them, the key padding) are computed once for the B images; the per-map
+        program runs in passes of at most `pairs_per_pass` pairs (8 = 800 maps at Q = 100, the size every mask-head kernel was measured at), so a
+        step holds one pass's intermediates whatever P is.  Padding pairs (0, 0) are computed like any other.
+        mask_sink: callable(lo, hi, logits [hi - lo, Q, Hm, Wm]) that consumes every pass's logits in place of "pred_masks" (CapturedMaskSweepStep packs
+        them into bit planes pass by pass)."""
+        from .sweep import pair_passes
+        nat = memory_cache.get("_native") or {}
+        if "pair_image" not in nat or len(nat.get("features", ())) != 4:
+            raise ValueError("decode_mask_sweep takes the memory cache of encode_mask_sweep / mask_sweep_pairs (pair tables and four feature levels)")
+        self.detr._sweep_ready(nat["src_proj"])
+        pi = nat["pair_image"]
+        P = pi.numel()
+        pair_passes(P, pairs_per_pass)                      # ValueError before anything is launched
+        out = self.detr.decode(memory_cache)
+        c2, c3, c4, c5 = nat["features"]
+        B, h, w, _ = c5.shape
+        stack = out["_stacked"]["hs"]                                   # [L, P*Q, d] bf16
+        Q = stack.shape[1] // P
+        d = stack.shape[-1]
+        out["pred_masks"] = self._masks_sweep(stack[-1], nat["memory"].view(-1, d), nat["S"], nat["src_proj"].reshape(B * h * w, d), c4, c3, c2,
+                                              nat["feat_mask"], pi, Q, h, w, pairs_per_pass, mask_sink)
+        if mask_sink is not None:
+            del out["pred_masks"]
+        return out
+
+    # ---- the detection model's sweep entry points stay refused: the mask head's sweep has its own (above) ---------------------
     def _no_sweep(self, *args, **kw):
         raise NotImplementedError("task sweep with a mask head: the mask program indexes its per-image FPN terms by row / Q, so a batch of (image, caption) "
                                   "pairs needs a pair table inside the mask-head kernels -- the follow-up 'DETRsegm sweeps: share the FPN terms of an "
-                                  "image among its pairs'.  Sweep a detection model (MDETR.encode_sweep), or run the per-pair path")
+                                  "image among its pairs'.  Sweep a detection model (MDETR.encode_sweep), or run the per-pair path -- or call the mask "
+                                  "head's own entry points: encode_mask_sweep / mask_sweep_stages / mask_sweep_pairs / decode_mask_sweep")
 
     sweep_images = sweep_text = sweep_pairs = sweep_stages = encode_sweep = _no_sweep
 

@@ -83,6 +83,18 @@ def pair_tables(n_images, n_captions, pairs=None, capacity=None):
     return pi, pc, live
 
 
+def pair_passes(n_pairs, pairs_per_pass):
+    """The (lo, hi) slices of P pairs that the mask program of a sweep runs one after the other: at most `pairs_per_pass` pairs each, in table order,
+    the last one holding the remainder.  The per-map intermediates of a pass are what the step holds at a time (DETRsegm.decode_mask_sweep).
+    ValueError: no pair, or a pass size that is not a positive integer."""
+    if isinstance(n_pairs, bool) or isinstance(pairs_per_pass, bool) or int(n_pairs) != n_pairs or int(pairs_per_pass) != pairs_per_pass:
+        raise ValueError(f"pair_passes: whole numbers of pairs (got {n_pairs!r} pairs, {pairs_per_pass!r} per pass)")
+    n_pairs, pairs_per_pass = int(n_pairs), int(pairs_per_pass)
+    if n_pairs <= 0 or pairs_per_pass <= 0:
+        raise ValueError(f"pair_passes: {n_pairs} pairs in passes of {pairs_per_pass}: both must be positive")
+    return [(lo, min(lo + pairs_per_pass, n_pairs)) for lo in range(0, n_pairs, pairs_per_pass)]
+
+
 class SweepTokenized(TokenizedText):
     """The tokenized captions of a sweep as the pairs see them: input_ids / attention_mask hold caption pair_caption[p] in row p, and
     char_to_token(p, c) answers for that caption -- ClusterCriterion.infer_choice finds the word 'something' of every pair through it."""

@@ -648,6 +648,24 @@ TOIST_API int toist_kmeans_init(const float* banks, int64_t bank_stride, float* 
                  int max_iter, int32_t* pick, float* chosen_center, int32_t* iters, const float* full_label, const int32_t* init_rows,
                  int32_t* status, void* stream);
 
+/* ---- the prototype choice of a task sweep in one launch (ClusterCriterion.infer_choice, models/mdetr.py:282-312, over the P (image, caption) pairs
+ * of toist_sweep_assemble; replaces its per-sample feature mean :240-260, memory_cluster :213-234 and the img_memory_mod clone + row writes :300-310).
+ *   memory     bf16 [P, S, D], S = HW + L : the encoder output, read only          memory_mod bf16 [P, S, D] : holds a copy of memory on entry
+ *   pair_caption i32 [P], live i32 [1]    : device tables; the pairs p >= *live are padding and are never looked at
+ *   W_sth f32 [T, L], sub_sth u8 [T, L], cap_task i32 [T] : per CAPTION -- mean weights and marks of the tokens of the word 'something', task index
+ *   group_task i32 [T]                    : the distinct tasks of the captions, one per slot, -1 (or anything outside [0, n_tasks)) = unused slot
+ *   banks f32 [n_tasks, N, D] (stride bank_stride), centers f32 [n_tasks, K, D] (stride centers_stride, updated IN PLACE)
+ * One 1024-thread workgroup per slot walks p = 0 .. *live-1 in ascending order and serves the pairs with cap_task[pair_caption[p]] == its task:
+ *   features[p, d] = sum over l ascending of W_sth[c, l] * float(memory[p, HW + l, d]) -- fp32, every product formed and rounded, no contraction;
+ *   toist_kmeans' iterations from the centres the task's previous pair left (tol, max_iter) and its nearest-centre pick; centers[task] stored back;
+ *   memory_mod[p, HW + l, :] = bf16(centre[pick]) (round to nearest even) for every l with sub_sth[c, l].  Nothing else of memory_mod is written.
+ * pair_caption[p] outside [0, T) is never used as an index: the pair is skipped and *status = max(*status, p + 1) (toist_sweep_assemble's word and
+ * rule).  pick i32 [P], features f32 [P, D], iters i32 [P]: optional (NULL), written for served pairs only.  Limits: toist_kmeans', and L <= 256. */
+TOIST_API int toist_sweep_prototypes(const void* memory, void* memory_mod, const int32_t* pair_caption, const int32_t* live, const float* W_sth,
+                 const uint8_t* sub_sth, const int32_t* cap_task, const int32_t* group_task, const float* banks, int64_t bank_stride,
+                 float* centers, int64_t centers_stride, int P, int HW, int L, int T, int n_tasks, int N, int D, int K, float tol, int max_iter,
+                 int32_t* status, int32_t* pick, float* features, int32_t* iters, void* stream);
+
 /* ---- FIFO update of the memory banks with its bookkeeping on the device (mdetr.py:85-97; update_count / full_label: mdetr.py:90-92).  Group g =
  * the n = group_off[g+1] - group_off[g] samples members[group_off[g] ..) of task t = group_task[g] (n_groups slots, n_groups <= B <= N), rows f32
  * [B, D] the new features by sample.  With label = full_label[t] as the launch finds it:

@@ -637,11 +637,15 @@ class CapturedSweepStep(_CapturedStep):
     reads: its status word and the XCD-resident decoder's are read after every replay, where the results are handed out (one synchronisation).  A
     refused entry raises ValueError (and the tables are uploaded afresh by the next step); a failed decoder launch drops every graph, and the same
     batch runs again on the per-op launches and is captured again, as in CapturedEvalStep.
-    No prototype choice inside the graph: a cluster criterion raises ValueError -- harness.evaluate_sweep's eager loop serves it."""
+    Prototype choice: with a `cluster_criterion` (a distill.ClusterCriterion) it runs inside the graph, between the pair stage and decode:
+    ClusterCriterion.infer_choice_pairs, ONE toist_sweep_prototypes launch on the encoder's bf16 rows, reading a distill.SweepChoiceTables image of
+    the bucket.  step / step_rows then take dataset_names= and captions=: T strings each (the tokenized captions must answer char_to_token); the image
+    is uploaded, with the pair tables, when it changes.  Padding pairs are encoded and decoded as before and never enter the k-means walk.  After a
+    step ent["img_memory_mod"] is the bucket's memory with the chosen prototypes, a bf16 [S, pairs, d] view.  The preconditions are
+    ClusterCriterion._static_ok's; k-means moves cluster_centers in place.  Anything but a ClusterCriterion raises ValueError."""
 
     def __init__(self, model, cluster_criterion=None, *, batch, captions, pairs=None, pad_hw=64, pad_tokens=1, max_graphs=4, device=None):
-        if cluster_criterion is not None:
-            raise ValueError("CapturedSweepStep takes no cluster criterion: the prototype choice of a sweep runs in harness.evaluate_sweep's eager loop")
+        self._take_criterion(cluster_criterion)
         if hasattr(model, "detr"):
             model.encode_sweep()                           # a mask-head model: NotImplementedError naming the follow-up
         self.model = model
@@ -654,24 +658,69 @@ class CapturedSweepStep(_CapturedStep):
         self.num_queries = model.query_embed.weight.shape[0]
         self._init_capture_state()
 
+    # -- the prototype choice (shared with CapturedMaskSweepStep) ----------------------------------------------------------------------------------
+    def _take_criterion(self, cluster_criterion):
+        from .distill import ClusterCriterion
+        if cluster_criterion is not None and not isinstance(cluster_criterion, ClusterCriterion):
+            raise ValueError(f"{type(self).__name__}: the cluster criterion of a captured sweep is a distill.ClusterCriterion "
+                             f"(got {type(cluster_criterion).__name__})")
+        self.cluster_criterion = cluster_criterion
+
+    def _choice_inputs(self, Lp):
+        """What a bucket holds for the prototype choice: the caption-side tables (memory_mod hangs off them)."""
+        from .distill import SweepChoiceTables
+        return {"choice": SweepChoiceTables(self.captions, Lp, self.device) if self.cluster_criterion is not None else None, "img_memory_mod": None}
+
+    def _choice_args(self, tokenized, dataset_names, captions):
+        """Host check of a step's dataset names and captions (ValueError; nothing has been launched) -> (dataset_names, captions) as lists, or
+        (None, None) without a criterion."""
+        cc = self.cluster_criterion
+        if cc is None:
+            return None, None
+        if dataset_names is None or captions is None:
+            raise ValueError(f"{type(self).__name__} with a cluster criterion needs the captions' dataset_names and captions")
+        dataset_names, captions = list(dataset_names), list(captions)
+        if len(dataset_names) != self.captions or len(captions) != self.captions:
+            raise ValueError(f"{type(self).__name__} with a cluster criterion: {len(dataset_names)} dataset names and {len(captions)} caption strings "
+                             f"for {self.captions} captions")
+        from .distill import task_index
+        if any(not 0 <= task_index(n) < cc.task_count for n in dataset_names):
+            raise ValueError(f"{type(self).__name__}: the dataset names {dataset_names!r} name a task outside the cluster criterion's {cc.task_count}")
+        if not hasattr(tokenized, "char_to_token"):
+            raise ValueError(f"{type(self).__name__} with a cluster criterion: the tokenized captions must answer char_to_token")
+        cc._static_ok()
+        cc.eval()
+        return dataset_names, captions
+
+    def _choose(self, ent, mc):
+        """The prototype stage of _forward, between the pair stage and decode."""
+        if self.cluster_criterion is None:
+            return mc
+        mc = self.cluster_criterion.infer_choice_pairs(mc, ent["choice"], ent["pair_caption"])
+        nat = mc["_native"]
+        ent["img_memory_mod"] = nat["memory_mod"].view(nat["B"], nat["S"], -1).permute(1, 0, 2)     # bf16 [S, pairs, d]: a view, readable after any step
+        return mc
+
     def _static_inputs(self, key):
         Hp, Wp, Lp = key
         pad_id = _pad_id(self.model)
         return {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, self.device), **pair_inputs(self.captions, self.pairs, Lp, pad_id, self.device, sizes=True),
-                **_NO_GRAPH, "uploaded": None, "out": None}
+                **_NO_GRAPH, "uploaded": None, "out": None, **self._choice_inputs(Lp)}
 
-    def _fill(self, ent, samples, tokenized, pi, pc, sizes):
+    def _fill(self, ent, samples, tokenized, pi, pc, sizes, choice=None):
         upload(ent, samples, tokenized)
         tables = (pi.tolist(), pc.tolist(), sizes)
         if ent["uploaded"] != tables:                      # (the full product of a whole evaluation is uploaded once)
             fill_pair_inputs(ent, pi, pc, sizes)
             ent["uploaded"] = tables
+        if choice is not None:                             # (tokenized, captions, dataset_names, live): uploaded when the image changes
+            ent["choice"].load(*choice)
 
     def _forward(self, ent):
         """The launches of one batch on the bucket's static inputs (eagerly, and once more under capture)."""
         state, text = self.model.sweep_stages(ent["samples"], ent["tok"])
         mc = self.model.sweep_pairs(state, text, ent["pair_image"], ent["pair_caption"], check=False)       # (step reads the status word)
-        outputs = self.model.decode(mc)
+        outputs = self.model.decode(self._choose(ent, mc))
         ent["out"] = kernels.postprocess(outputs["pred_logits"], outputs["pred_boxes"], ent["sizes"], outputs.get("pred_isfinal"), out=ent["out"])
 
     def _handed_out(self, ent):
@@ -680,19 +729,23 @@ class CapturedSweepStep(_CapturedStep):
             kernels.sweep_check()
         except ValueError:
             ent["uploaded"] = None                         # whatever the device tables hold now, the next step uploads them afresh
+            if ent["choice"] is not None:
+                ent["choice"].invalidate()
             raise
 
-    def step(self, samples, tokenized, orig_sizes, pairs=None):
-        out, pi, pc, live = self.step_rows(samples, tokenized, orig_sizes, pairs=pairs)
+    def step(self, samples, tokenized, orig_sizes, pairs=None, dataset_names=None, captions=None):
+        out, pi, pc, live = self.step_rows(samples, tokenized, orig_sizes, pairs=pairs, dataset_names=dataset_names, captions=captions)
         return row_results(out, self.pairs, live, self.num_queries, self.device), pi, pc, live
 
     @torch.no_grad()
-    def step_rows(self, samples, tokenized, orig_sizes, pairs=None):
+    def step_rows(self, samples, tokenized, orig_sizes, pairs=None, dataset_names=None, captions=None):
         """step() without the per-row dicts -> (out, pair_image, pair_caption, live): out = the bucket's kernels.postprocess dict (scores [pairs, Q],
         boxes [pairs, Q, 4]; rows from `live` on are padding), valid until the next step of that bucket -- what a consumer that takes a whole batch
         of rows reads in place (coco_eval.SweepEvaluator.update_rows)."""
         from . import sweep
         if isinstance(tokenized, (list, tuple)) and len(tokenized) and isinstance(tokenized[0], str):
+            if captions is None:
+                captions = list(tokenized)
             tokenized = self.model.transformer._tokenize(list(tokenized), self.device)
         if samples.tensors.shape[0] != self.batch or tokenized["input_ids"].shape[0] != self.captions:
             raise ValueError(f"CapturedSweepStep was built for {self.batch} images and {self.captions} captions "
@@ -702,11 +755,12 @@ class CapturedSweepStep(_CapturedStep):
             raise ValueError(f"CapturedSweepStep: {len(orig)} original sizes for {self.batch} images, or a size that is not positive")
         pi, pc, live = sweep.pair_tables(self.batch, self.captions, pairs, capacity=self.pairs)           # ValueError before anything is launched
         sizes = [orig[i] for i in pi.tolist()]
+        dataset_names, captions = self._choice_args(tokenized, dataset_names, captions)              # the same
         if self.model.training:
             self.model.eval()
         key = self.bucket_of(samples, tokenized)
         ent = self._entry(key)
-        self._fill(ent, samples, tokenized, pi, pc, sizes)
+        self._fill(ent, samples, tokenized, pi, pc, sizes, (tokenized, captions, dataset_names, live) if captions is not None else None)
         out = self._replay_checked(ent, lambda: self._forward(ent), lambda: ent["out"], lambda: self._handed_out(ent))
         return out, pi, pc, live
 
@@ -728,13 +782,13 @@ class CapturedMaskSweepStep(CapturedSweepStep):
     toist_mask_resize_pack_batch -- are gathered by pair_image on the host and uploaded with the pair tables when any of them changes.  The first
     resize target is the bucket's (Hp, Wp), as in CapturedEvalStep; capacity and size checks are CapturedEvalStep.check_sizes's, raised before
     anything is launched.  The status words (the sweep launches' and the XCD-resident decoder's) are read where results are handed out.
-    No prototype choice inside the graph: a cluster criterion raises ValueError."""
+    Prototype choice: a `cluster_criterion` runs inside the graph between mask_sweep_pairs and decode, as in CapturedSweepStep (dataset_names= and
+    captions= in step / step_rows)."""
 
     def __init__(self, model, cluster_criterion=None, *, batch, captions, pairs=None, max_orig_hw=None, pairs_per_pass=8, threshold=0.5, pad_hw=64,
                  pad_tokens=1, max_graphs=4, device=None):
         from .sweep import pair_passes
-        if cluster_criterion is not None:
-            raise ValueError("CapturedMaskSweepStep takes no cluster criterion: the prototype choice of a sweep runs in harness.evaluate_sweep's eager loop")
+        self._take_criterion(cluster_criterion)
         if not hasattr(model, "detr") or not hasattr(model, "decode_mask_sweep"):
             raise ValueError("CapturedMaskSweepStep needs a model with a mask head (DETRsegm); CapturedSweepStep serves a detection model")
         if max_orig_hw is None:
@@ -763,14 +817,16 @@ class CapturedMaskSweepStep(CapturedSweepStep):
         pad_id = _pad_id(self.model)
         return {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, self.device),
                 **pair_inputs(self.captions, self.pairs, Lp, pad_id, self.device, sizes=True, crops=True), **_NO_GRAPH, "uploaded": None, "out": None,
-                "bits": torch.zeros(self.pairs * self.capacity_words, dtype=torch.int64, device=self.device)}
+                "bits": torch.zeros(self.pairs * self.capacity_words, dtype=torch.int64, device=self.device), **self._choice_inputs(Lp)}
 
-    def _fill(self, ent, samples, tokenized, pi, pc, sizes, crops):
+    def _fill(self, ent, samples, tokenized, pi, pc, sizes, crops, choice=None):
         upload(ent, samples, tokenized)
         tables = (pi.tolist(), pc.tolist(), sizes, crops)
         if ent["uploaded"] != tables:
             fill_pair_inputs(ent, pi, pc, sizes, crops)
             ent["uploaded"] = tables
+        if choice is not None:
+            ent["choice"].load(*choice)
 
     def _forward(self, ent, key):
         """The launches of one batch on the bucket's static inputs (eagerly, and once more under capture)."""
@@ -781,7 +837,7 @@ class CapturedMaskSweepStep(CapturedSweepStep):
 
         state, text = self.model.mask_sweep_stages(ent["samples"], ent["tok"])
         mc = self.model.mask_sweep_pairs(state, text, ent["pair_image"], ent["pair_caption"], check=False)          # (step reads the status word)
-        outputs = self.model.decode_mask_sweep(mc, self.pairs_per_pass, mask_sink=pack)
+        outputs = self.model.decode_mask_sweep(self._choose(ent, mc), self.pairs_per_pass, mask_sink=pack)
         ent["out"] = kernels.postprocess(outputs["pred_logits"], outputs["pred_boxes"], ent["sizes"], outputs.get("pred_isfinal"), out=ent["out"])
 
     def _planes(self, ent, p, hw):
@@ -790,23 +846,25 @@ class CapturedMaskSweepStep(CapturedSweepStep):
         Q, cap = self.num_queries, self.capacity_words
         return ent["bits"][p * cap:p * cap + Q * w * words].view(Q, w, words)
 
-    def step(self, samples, tokenized, orig_sizes, sizes, pairs=None):
-        ent, sizes_p, pi, pc, live = self._step(samples, tokenized, orig_sizes, sizes, pairs)
+    def step(self, samples, tokenized, orig_sizes, sizes, pairs=None, dataset_names=None, captions=None):
+        ent, sizes_p, pi, pc, live = self._step(samples, tokenized, orig_sizes, sizes, pairs, dataset_names, captions)
         results = row_results(ent["out"], self.pairs, live, self.num_queries, self.device)
         for p, r in enumerate(results):
             r["mask_bits"], r["mask_size"] = self._planes(ent, p, sizes_p[p]), sizes_p[p]
         return results, pi, pc, live
 
-    def step_rows(self, samples, tokenized, orig_sizes, sizes, pairs=None):
+    def step_rows(self, samples, tokenized, orig_sizes, sizes, pairs=None, dataset_names=None, captions=None):
         """step() without the per-row dicts -> (out, masks, pair_image, pair_caption, live); rows from `live` on are padding."""
         from .coco_eval import RowMasks
-        ent, sizes_p, pi, pc, live = self._step(samples, tokenized, orig_sizes, sizes, pairs)
+        ent, sizes_p, pi, pc, live = self._step(samples, tokenized, orig_sizes, sizes, pairs, dataset_names, captions)
         return ent["out"], RowMasks(ent["bits"], self.capacity_words, ent["sizes"], sizes_p), pi, pc, live
 
     @torch.no_grad()
-    def _step(self, samples, tokenized, orig_sizes, sizes, pairs):
+    def _step(self, samples, tokenized, orig_sizes, sizes, pairs, dataset_names=None, captions=None):
         from . import sweep
         if isinstance(tokenized, (list, tuple)) and len(tokenized) and isinstance(tokenized[0], str):
+            if captions is None:
+                captions = list(tokenized)
             tokenized = self.model.detr.transformer._tokenize(list(tokenized), self.device)
         if samples.tensors.shape[0] != self.batch or tokenized["input_ids"].shape[0] != self.captions:
             raise ValueError(f"CapturedMaskSweepStep was built for {self.batch} images and {self.captions} captions "
@@ -816,10 +874,11 @@ class CapturedMaskSweepStep(CapturedSweepStep):
         pi, pc, live = sweep.pair_tables(self.batch, self.captions, pairs, capacity=self.pairs)           # the same
         rows = pi.tolist()
         sizes_p, crops_p = [orig[i] for i in rows], [crop[i] + orig[i] for i in rows]
+        dataset_names, captions = self._choice_args(tokenized, dataset_names, captions)                  # the same
         if self.model.training:
             self.model.eval()
         ent = self._entry(key)
-        self._fill(ent, samples, tokenized, pi, pc, sizes_p, crops_p)
+        self._fill(ent, samples, tokenized, pi, pc, sizes_p, crops_p, (tokenized, captions, dataset_names, live) if captions is not None else None)
         self._replay_checked(ent, lambda: self._forward(ent, key), lambda: None, lambda: self._handed_out(ent))
         return ent, sizes_p, pi, pc, live
 

@@ -277,6 +277,71 @@ class FillTables:
         return self
 
 
+class SweepChoiceTables:
+    """Fixed-address device image of what the prototype choice of a task sweep reads per CAPTION (toist_sweep_prototypes): the sibling of
+    DistillTables for a batch whose rows are (image, caption) PAIRS.  Nothing here is indexed by pair -- the launch finds a pair's caption in the
+    sweep's own pair_caption table -- so the image changes only when the captions, their tasks or the number of live pairs do.
+
+    Arena (T = captions, L = tokens of the bucket):
+      W_sth    f32 [T, L]   mean weights of the tokens of the word 'something' in caption t (something_tables)
+      sub_sth   u8 [T, L]   tokens of 'something'
+      cap_task i32 [T]      task index of the caption (its dataset name)
+      group_task i32 [T]    the distinct tasks in first-appearance order, one group slot (= workgroup) each; -1 in unused slots.  Two captions of one
+                            task share a slot: the walk over the pairs keeps the reference's order inside a task whatever the captions are.
+      live     i32 [1]      the pairs p >= live are padding: they never enter the k-means walk
+    `memory_mod` (bf16 [P * S, d], allocated by ClusterCriterion.infer_choice_pairs on first use) hangs off the same object: both belong to a bucket."""
+
+    def __init__(self, captions, tokens, device):
+        self.T, self.L = int(captions), int(tokens)
+        self.device = torch.device(device)
+        T, L = self.T, self.L
+        self._views, self.nbytes = staging.typed_views([(torch.float32, (T, L)), (torch.uint8, (T, L)), (torch.int32, (T,)), (torch.int32, (T,)),
+                                                        (torch.int32, (1,))])
+        self._stage = staging.Staging(torch.zeros(self.nbytes, dtype=torch.uint8), self.device)
+        self._dev = torch.zeros(self.nbytes, dtype=torch.uint8, device=self.device)
+        self.W_sth, self.sub_sth, self.cap_task, self.group_task, self.live = self._views(self._dev)
+        self.group_task.fill_(-1)                                # (until the first load every slot is unused)
+        self._loaded = None                                      # the host image the device holds
+        self.memory_mod = None
+
+    def pack(self, tokenized, captions, dataset_names, live, out=None):
+        """Host image (uint8 [nbytes]) of one sweep.  tokenized: the T captions' BatchEncoding (needs char_to_token); captions / dataset_names: T
+        strings each; live: the number of live pairs.  Needs no device."""
+        if len(captions) != self.T or len(dataset_names) != self.T:
+            raise ValueError(f"SweepChoiceTables holds {self.T} captions; got {len(captions)} captions and {len(dataset_names)} dataset names")
+        if isinstance(live, bool) or int(live) != live or int(live) < 0:
+            raise ValueError(f"SweepChoiceTables: live = {live!r} is not a count of pairs")
+        host = out if out is not None else torch.zeros(self.nbytes, dtype=torch.uint8)
+        host.zero_()
+        W_sth, sub_sth, cap_task, group_task, live_w = (v.numpy() for v in self._views(host))
+        W, sub, _ = something_tables(tokenized, list(captions), self.L)
+        W_sth[:], sub_sth[:] = W, sub.T
+        tasks = [task_index(n) for n in dataset_names]
+        if any(t < 0 for t in tasks):
+            raise ValueError(f"SweepChoiceTables: dataset names {list(dataset_names)!r} name a task below 1")
+        order = list(dict.fromkeys(tasks))                       # distinct, first appearance first
+        cap_task[:] = tasks
+        group_task[:] = -1
+        group_task[:len(order)] = order
+        live_w[0] = int(live)
+        return host
+
+    def load(self, tokenized, captions, dataset_names, live):
+        """pack() and, when the image differs from what the device holds, one copy through the staging buffer -> whether it was uploaded."""
+        host = self.pack(tokenized, captions, dataset_names, live)
+        if self._loaded is not None and torch.equal(host, self._loaded):
+            return False
+        stage = self._stage.open()
+        stage.copy_(host)
+        self._stage.upload((self._dev, stage))
+        self._loaded = host
+        return True
+
+    def invalidate(self):
+        """The next load() uploads whatever it packs (the owner's pair tables were refused: nothing on the device is trusted)."""
+        self._loaded = None
+
+
 # ---- k-means (kmeans.py) ---------------------------------------------------------------------------------------
 def _sq_dist(x, centers):
     return ((x.unsqueeze(1) - centers.unsqueeze(0)) ** 2.0).sum(-1)
@@ -598,6 +663,37 @@ class ClusterCriterion(nn.Module):
         self._static_ok()
         self._substitute_batch(memory_cache_sth, tb.W_sth, tb.sub_sth, lambda f: self._cluster_static(f, tb))
         return memory_cache_sth
+
+    @torch.no_grad()
+    def infer_choice_pairs(self, memory_cache, tables, pair_caption=None):
+        """infer_choice (mdetr.py:279-312) for the P (image, caption) pairs of a task sweep, in ONE launch on the encoder's own bf16 rows
+        (toist_sweep_prototypes): memory_cache is MDETR.sweep_pairs' cache, tables a loaded SweepChoiceTables, pair_caption the sweep's int32 device
+        table (default: the one the cache carries).  tables.memory_mod -- allocated here on first use, reused afterwards -- receives a copy of the
+        memory and, in the rows of the word 'something' of every live pair, the chosen prototype; the cache gains it as `_native["memory_mod"]`, which
+        MDETR.decode reads as it stands, and a lazy fp32 "img_memory_mod" [S, P, d] for whoever reads that key.  The memory itself is not touched:
+        the contrastive head and "img_memory" / "text_memory" keep the unmodified rows, as the reference's clone guarantees.  k-means moves
+        `cluster_centers` in place.  Preconditions: _static_ok()'s.  No host value enters the launch: a captured sweep records it."""
+        from . import kernels as k
+        self._static_ok()
+        nat = memory_cache.get("_native")
+        if nat is None or not hasattr(memory_cache, "set_lazy"):
+            raise ValueError("infer_choice_pairs takes the memory cache of MDETR.sweep_pairs (the encoder's bf16 rows under '_native')")
+        if pair_caption is None:
+            pair_caption = nat.get("pair_caption")
+        if pair_caption is None:
+            raise ValueError("infer_choice_pairs: the memory cache carries no pair_caption table; pass the sweep's")
+        mem = nat["memory"]
+        P, S, L, d = nat["B"], nat["S"], nat["L"], mem.shape[-1]
+        if tables.L != L or pair_caption.numel() != P:
+            raise ValueError(f"infer_choice_pairs: tables of {tables.L} tokens and {pair_caption.numel()} pairs for a memory of {L} tokens and {P} pairs")
+        mod = tables.memory_mod
+        if mod is None or mod.shape != mem.shape or mod.device != mem.device:
+            mod = tables.memory_mod = torch.empty_like(mem)
+        mod.copy_(mem)
+        k.sweep_prototypes(mem, mod, pair_caption, tables, self.feature_bank, self.cluster_centers, S - L)
+        nat["memory_mod"] = mod
+        memory_cache.set_lazy("img_memory_mod", lambda: mod.view(P, S, d).permute(1, 0, 2).float())
+        return memory_cache
 
     def update_memory(self, memory_cache_noun, targets_noun, captions_noun):
         """Teacher side (mdetr.py:105-205): push this batch's noun features into the banks, then replace the noun

@@ -249,7 +249,8 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
     cluster_criterion: the prototype choice (ClusterCriterion.infer_choice) runs per pair stage, with each pair's dataset name and caption; it needs the
     tasks' dataset names, and captions that answer char_to_token (strings through the model's tokenizer, or tokenized= a BatchEncoding of them).
     captured: a CapturedSweepStep built around `model` -- image stage, text stage, assembly, decode and post-processing of a batch are one graph
-    replay; it takes no cluster criterion.  tokenized: the T captions already tokenized (offline use; else the strings go through the tokenizer).
+    replay.  With cluster_criterion it must be the step's own (captured.cluster_criterion, recorded into its graphs as one toist_sweep_prototypes
+    launch); the tasks' dataset names and captions are passed through.  tokenized: the T captions already tokenized (offline use; else the strings go through the tokenizer).
     observe: callable(memory_cache, outputs, pair_image, pair_caption) called after every eager pair stage (tests, logging).
     evaluator: a coco_eval.SweepEvaluator holding every task's ground truth -- each pair stage's rows are scored on the device inside the loop
     (update_rows: two launches per stage, read in place, so the captured step's reused output buffers are consumed before the next replay), no keyed
@@ -280,13 +281,15 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
         raise ValueError("task names must be unique: they key the results")
     T = len(tasks)
     if cluster_criterion is not None:
-        if captured is not None:
-            raise ValueError("a captured sweep takes no cluster criterion: run the eager loop (captured=None) for the prototype choice")
+        if captured is not None and cluster_criterion is not getattr(captured, "cluster_criterion", None):
+            raise ValueError("a captured sweep runs the cluster criterion it was built with (captured.cluster_criterion): pass that one, or run the "
+                             "eager loop (captured=None) for the prototype choice")
         if any(n is None for n in dataset_names):
             raise ValueError("the prototype choice needs every task's dataset name: tasks = [(name, caption, dataset_name)]")
         cluster_criterion.eval()
     model.eval()
     text = tokenized if tokenized is not None else captions
+    choice = {"dataset_names": dataset_names, "captions": captions} if captured is not None and cluster_criterion is not None else {}
     out = {}
     for batch in batches:
         samples, image_ids, orig = batch["samples"], list(batch["image_ids"]), size_pairs(batch["orig_sizes"])
@@ -303,17 +306,17 @@ def evaluate_sweep(model, postprocessor, batches, tasks, device, cluster_criteri
                 raise ValueError(f"a batch of {B} images with {len(crop)} sizes")
         if captured is not None and evaluator is not None:
             if segm:
-                rows, masks, pi, pc, live = captured.step_rows(samples, text, orig, crop, pairs=batch.get("pairs"))
+                rows, masks, pi, pc, live = captured.step_rows(samples, text, orig, crop, pairs=batch.get("pairs"), **choice)
                 evaluator.update_rows(rows, image_ids, names, pi, pc, live, masks=masks)
                 continue
-            rows, pi, pc, live = captured.step_rows(samples, text, orig, pairs=batch.get("pairs"))
+            rows, pi, pc, live = captured.step_rows(samples, text, orig, pairs=batch.get("pairs"), **choice)
             evaluator.update_rows(rows, image_ids, names, pi, pc, live)
             continue
         if captured is not None:
             if segm:
-                results, pi, pc, live = captured.step(samples, text, orig, crop, pairs=batch.get("pairs"))
+                results, pi, pc, live = captured.step(samples, text, orig, crop, pairs=batch.get("pairs"), **choice)
             else:
-                results, pi, pc, live = captured.step(samples, text, orig, pairs=batch.get("pairs"))
+                results, pi, pc, live = captured.step(samples, text, orig, pairs=batch.get("pairs"), **choice)
             out.update(sweep.keyed_results(results, image_ids, names, pi, pc, live))
             continue
         samples = samples.to(device)

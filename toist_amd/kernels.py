@@ -927,6 +927,46 @@ def kmeans(banks, centers, group_task, group_off, members, features, tol, max_it
                                        max_iter, _p(pick, torch.int32), _p(chosen_center, torch.float32), _p(iters, torch.int32), _stream()), "toist_kmeans")
 
 
+def sweep_prototypes(memory, memory_mod, pair_caption, tables, banks, centers, HW, tol=1e-4, max_iter=10000, pick=None, features=None, iters=None):
+    """The prototype choice of a task sweep in one launch (include/toist_hip.h: toist_sweep_prototypes).  memory bf16 [P, S, D] (or [P * S, D]), the
+    encoder output, read only; memory_mod: the same shape, holding a copy of it -- the rows of the word 'something' of every live pair receive the
+    chosen prototype; pair_caption int32 [P] ON THE DEVICE; tables: a distill.SweepChoiceTables on that device (W_sth, sub_sth, cap_task, group_task,
+    live); banks [T_tasks, N, D] f32, centers [T_tasks, K, D] f32 (updated in place); HW: the image rows in front of every pair's L caption rows.
+    pick int32 [P] / features f32 [P, D] / iters int32 [P]: optional outputs, written for served pairs only.  ValueError before any launch: shapes that
+    disagree, D > 256, K > 8, K * D > 1024, L > 256, a bank of more than 32768 rows (its choice bytes are the launch's dynamic LDS).  A pair_caption
+    entry outside the captions raises the sweep status word (sweep_check)."""
+    T, L = tables.W_sth.shape
+    P = pair_caption.numel()
+    n_tasks, N, D = banks.shape
+    K = centers.shape[1]
+    S = int(HW) + L
+    dev = memory.device
+    if memory.numel() != P * S * D or memory_mod.shape != memory.shape or memory.dtype != torch.bfloat16 or memory_mod.dtype != torch.bfloat16:
+        raise ValueError(f"sweep_prototypes: memory and memory_mod are bf16 [P, S, D] = [{P}, {S}, {D}] (got {tuple(memory.shape)}, {tuple(memory_mod.shape)})")
+    if memory.data_ptr() == memory_mod.data_ptr():
+        raise ValueError("sweep_prototypes: memory_mod is a copy of memory, not memory itself (memory is never written)")
+    if centers.shape[0] != n_tasks or centers.shape[2] != D or tuple(tables.sub_sth.shape) != (T, L) or tables.cap_task.numel() != T or \
+            tables.group_task.numel() != T or tables.live.numel() != 1 or pair_caption.dim() != 1:
+        raise ValueError("sweep_prototypes: banks [T_tasks, N, D], centers [T_tasks, K, D] and tables of T captions x L tokens must agree")
+    if D > 256 or K > 8 or K * D > 1024 or L > 256 or N > 32768 or HW < 0:
+        raise ValueError(f"sweep_prototypes: D <= 256, K <= 8, K * D <= 1024, L <= 256, N <= 32768 (D={D} K={K} L={L} N={N})")
+    for t in (memory, memory_mod, pair_caption, banks[0], centers[0], tables.W_sth, tables.sub_sth):
+        if not t.is_contiguous():
+            raise ValueError("sweep_prototypes: every tensor must be contiguous (banks and centers per task)")
+    for t, n in ((pick, P), (features, P * D), (iters, P)):
+        if t is not None and (t.numel() != n or not t.is_contiguous()):
+            raise ValueError("sweep_prototypes: pick [P], features [P, D] and iters [P], contiguous")
+    status = sweep_status(dev)
+    if status is None:
+        raise RuntimeError("sweep_prototypes: the first sweep launch on a device cannot be captured (its status word is allocated outside any graph)")
+    _lib.check(_lib.lib().toist_sweep_prototypes(_p(memory, torch.bfloat16), _p(memory_mod, torch.bfloat16), _p(pair_caption, torch.int32),
+                                                 _p(tables.live, torch.int32), _p(tables.W_sth, torch.float32), _p(tables.sub_sth, torch.uint8),
+                                                 _p(tables.cap_task, torch.int32), _p(tables.group_task, torch.int32), _p(banks, torch.float32),
+                                                 banks.stride(0), _p(centers, torch.float32), centers.stride(0), P, int(HW), L, T, n_tasks, N, D, K, tol,
+                                                 max_iter, _p(status, torch.int32), _p(pick, torch.int32), _p(features, torch.float32),
+                                                 _p(iters, torch.int32), _stream()), "toist_sweep_prototypes")
+
+
 def kmeans_init(banks, centers, group_task, group_off, members, features, tol, max_iter, pick, chosen_center, full_label, init_rows, status, iters=None):
     """kmeans() whose start the device decides per sample: full_label f32 [T], init_rows i32 [B, K] (bank rows drawn on the host, or -1), status i32 [1]
     (bit 0 = the two disagreed); see toist_kmeans_init."""

@@ -413,7 +413,10 @@ class MDETR(nn.Module):
         key = "img_memory_mod" if (self.args is not None and getattr(self.args, "cluster", False)) else "img_memory"
         lazy = getattr(memory_cache, "is_lazy", None)
         if native is not None and lazy is not None and lazy(key):
-            # the fp32 API copies were never read, let alone replaced: decode straight from the encoder's bf16 buffers
+            # the fp32 API copies were never read, let alone replaced: decode straight from the encoder's bf16 buffers -- with the prototype choice of a
+            # sweep (ClusterCriterion.infer_choice_pairs) from its bf16 memory_mod, beside the same pos and key padding
+            if key == "img_memory_mod":
+                native = {**native, "memory": native["memory_mod"]}
             stack = self.transformer.decode_native(None, None, None, native["query_embed"], native=native)
         else:
             stack = self.transformer.decode_native(memory_cache[key], memory_cache["pos_embed"], memory_cache["mask"],

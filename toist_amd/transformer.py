@@ -154,6 +154,11 @@ class MemoryCache(dict):
     def is_lazy(self, key):
         return key in self._lazy
 
+    def set_lazy(self, key, thunk):
+        """Register (or replace) `key` as an entry that thunk() materialises on first read."""
+        dict.pop(self, key, None)
+        self._lazy[key] = thunk
+
     def _force(self, key):
         f = self._lazy.pop(key, None)
         if f is not None:

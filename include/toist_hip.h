@@ -368,6 +368,19 @@ TOIST_API int toist_mask_stage_fwd_pairs(const void* src, const float* src_stats
 TOIST_API int toist_resize_add_pairs(const void* in, const void* fpn, const int32_t* pair_image, int n_images, int n, int Q, int H, int W, int OH, int OW,
                         int C, void* out, int32_t* status, void* stream);
 TOIST_API int toist_sum_segments(const void* in, const int32_t* seg, int B, int rows, int64_t per, void* out, void* stream);
+/* The mask head's BACKWARD over pairs (shared-image training: P pairs of Q maps each, pair p on image pair_image[p], a DEVICE int32 table of P entries).
+ * toist_resize_add_rows_pairs: toist_resize_add on a gathered subset (rows int64 [n], n need not be a multiple of Q) whose image is read through the
+ * table: out[i, Y, X, :] = fpn[pair_image[rows[i] / Q], Y, X, :] + in[i, src(Y), src(X), :], the arithmetic of toist_resize_add (fp32 add of two bf16
+ * values, one rounding; the shift form for exact doublings).  A pair rows[i] / Q outside [0, P) or an image outside [0, n_images) is never used as an
+ * index: its image term counts as zero and *status = max(*status, pair + 1) (P + 1 for a negative pair).
+ * toist_sum_maps_by_image: in bf16 [rows, per] -> out bf16 [n_images, per]: out[b, :] = the fp32 sum, rounded once, of the maps of every pair p with
+ * pair_image[p] == b, in ascending pair order and ascending map order -- no atomics: the same bits every run, whatever the order of the table.  Pair p's
+ * maps are [seg[p], seg[p + 1]) clamped to [0, rows) (seg int32 [P + 1] on the device), or [p Q, (p + 1) Q) with seg = NULL.  An image without a pair
+ * gets zeros; a table entry outside [0, n_images) is skipped and reported in *status as above.  per % 8 == 0. */
+TOIST_API int toist_resize_add_rows_pairs(const void* in, const void* fpn, const int64_t* rows, const int32_t* pair_image, int n_images, int P, int n, int Q,
+                        int H, int W, int OH, int OW, int C, void* out, int32_t* status, void* stream);
+TOIST_API int toist_sum_maps_by_image(const void* in, const int32_t* seg, const int32_t* pair_image, int P, int Q, int n_images, int rows, int64_t per,
+                        void* out, int32_t* status, void* stream);
 TOIST_API int toist_mask_loss_fwd(const float* pred, const int32_t* pred_row, const uint8_t* gt, const int32_t* gt_row, int T, int h, int w,
                         int TH, int TW, float alpha, float* sums, const int32_t* valid_hw, void* stream);
 TOIST_API int toist_mask_loss_bwd(const float* pred, const int32_t* pred_row, const uint8_t* gt, const int32_t* gt_row, int T, int h, int w,

@@ -1,4 +1,4 @@
-"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedPairTrainStep, CapturedEvalStep, CapturedSweepStep, CapturedMaskSweepStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
+"""The steps replayed from hipGraphs -- CapturedTrainStep, CapturedPairTrainStep, CapturedMaskPairTrainStep, CapturedEvalStep, CapturedSweepStep, CapturedMaskSweepStep, CapturedDistillStep (also importable from toist_amd.harness) -- and the one
 core they share: bucket keys, the static image / text inputs of a bucket and the upload into them, the pair tables of a pair-shaped bucket and
 their fill (pair_inputs / fill_pair_inputs), the LRU of buckets, the eager pass followed by the capture, the rule that voids captured graphs once
 the XCD-resident decoder launches have been turned off, and the bodies of a step on a filled bucket: _CapturedStep._train_tail and
@@ -393,18 +393,28 @@ class CapturedPairTrainStep(_CapturedStep):
             model.encode_pairs()                           # a mask-head model: NotImplementedError
         if "masks" in getattr(criterion, "losses", ()):
             raise ValueError("CapturedPairTrainStep takes no mask losses: the mask losses index ground-truth masks by image row, not by pair")
+        self._init_pair_step(model, criterion, optimizer, weight_dict, batch, captions, pairs, max_targets_per_image, pad_hw, pad_tokens, max_graphs,
+                             contrastive, device)
+
+    masks = False                                          # the bucket's StaticTargets carry no ground-truth masks (CapturedMaskPairTrainStep: they may)
+
+    def _init_pair_step(self, model, criterion, optimizer, weight_dict, batch, captions, pairs, max_targets_per_image, pad_hw, pad_tokens, max_graphs,
+                        contrastive, device):
+        """Everything of the constructor behind the refusals (shared with CapturedMaskPairTrainStep); nothing here touches the device."""
+        name = type(self).__name__
         self.batch, self.captions, self.pairs = int(batch), int(captions), int(pairs)
         if self.batch <= 0 or self.captions <= 0 or self.pairs <= 0:
-            raise ValueError(f"CapturedPairTrainStep: batch = {batch}, captions = {captions}, pairs = {pairs}")
+            raise ValueError(f"{name}: batch = {batch}, captions = {captions}, pairs = {pairs}")
         if _is_distributed():
-            raise RuntimeError("CapturedPairTrainStep is single-process: MDETR.encode_pairs has no data-parallel path (run CapturedTrainStep on the "
+            raise RuntimeError(f"{name} is single-process: MDETR.encode_pairs has no data-parallel path (run CapturedTrainStep on the "
                                "expanded batch under torch.distributed)")
         self.model, self.criterion, self.optimizer, self.weight_dict = model, criterion, optimizer, weight_dict
         self.max_t = int(max_targets_per_image)
         self.pad_hw, self.pad_tokens, self.max_graphs = int(pad_hw), int(pad_tokens), int(max_graphs)
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
-        self.num_queries = model.query_embed.weight.shape[0]
-        self.contrastive = bool(getattr(model, "contrastive_align_loss", False)) if contrastive is None else bool(contrastive)
+        det = getattr(model, "detr", model)
+        self.num_queries = det.query_embed.weight.shape[0]
+        self.contrastive = bool(getattr(det, "contrastive_align_loss", False)) if contrastive is None else bool(contrastive)
         self._init_capture_state(xdec_seen=kernels.XDEC_FAILED)
         self._ready = False                                # device state (seed word, guard words) is set up by the first step that passed the checks
 
@@ -423,20 +433,21 @@ class CapturedPairTrainStep(_CapturedStep):
         Hp, Wp, Lp = key
         pad_id = _pad_id(self.model)
         return {**static_inputs(self.batch, Hp, Wp, Lp, pad_id, self.device), **pair_inputs(self.captions, self.pairs, Lp, pad_id, self.device),
-                **_NO_GRAPH, "targets": StaticTargets(self.pairs, self.max_t, self.num_queries, 256, self.device)}
+                **_NO_GRAPH, "targets": StaticTargets(self.pairs, self.max_t, self.num_queries, 256, self.device, mask_hw=(Hp, Wp) if self.masks else None)}
 
     def check_batch(self, samples, tokenized, pair_image, pair_caption, targets):
         """Host check of a step's arguments (ValueError; nothing has been uploaded or launched) -> the two tables as int32 host tensors."""
         from . import sweep
+        name = type(self).__name__
         B, T = samples.tensors.shape[0], tokenized["input_ids"].shape[0]
         if B != self.batch or T != self.captions:
-            raise ValueError(f"CapturedPairTrainStep was built for {self.batch} images and {self.captions} captions (got {B} and {T})")
+            raise ValueError(f"{name} was built for {self.batch} images and {self.captions} captions (got {B} and {T})")
         pi, pc = sweep.check_tables(pair_image, pair_caption, self.batch, self.captions)
         if pi.numel() != self.pairs:
-            raise ValueError(f"CapturedPairTrainStep was built for exactly {self.pairs} pairs (got {pi.numel()}): a padding pair would add no-object "
+            raise ValueError(f"{name} was built for exactly {self.pairs} pairs (got {pi.numel()}): a padding pair would add no-object "
                              "loss terms")
         if targets is not None and len(targets) != self.pairs:
-            raise ValueError(f"CapturedPairTrainStep: {len(targets)} target dicts for {self.pairs} pairs (targets are in pair order)")
+            raise ValueError(f"{name}: {len(targets)} target dicts for {self.pairs} pairs (targets are in pair order)")
         return pi, pc
 
     def _fill(self, ent, samples, tokenized, pi, pc, targets, positive_map):
@@ -457,12 +468,54 @@ class CapturedPairTrainStep(_CapturedStep):
 
     def step(self, samples, tokenized, pair_image, pair_caption, targets, positive_map):
         if _is_distributed():
-            raise RuntimeError("CapturedPairTrainStep is single-process: MDETR.encode_pairs has no data-parallel path")
+            raise RuntimeError(f"{type(self).__name__} is single-process: MDETR.encode_pairs has no data-parallel path")
         pi, pc = self.check_batch(samples, tokenized, pair_image, pair_caption, targets)
         self._device_state()
         ent = self._entry(self.bucket_of(samples, tokenized))
         self._fill(ent, samples, tokenized, pi, pc, targets, positive_map)
         return self._replay_or_capture(ent)
+
+    __call__ = step
+
+
+class CapturedMaskPairTrainStep(CapturedPairTrainStep):
+    """CapturedPairTrainStep for a model with a mask head (DETRsegm) -- configs[2] on shared images: DETRsegm.encode_mask_pairs / decode_mask_pairs
+    replayed from one hipGraph per bucket, the mask program and its backward reading the bucket's pair table, so the ResNet's forward and backward
+    run once per IMAGE while the mask head runs on all `pairs` * Q maps.  The criterion may carry "masks" or not; with them the bucket's
+    StaticTargets hold the ground-truth masks (mask_hw = the bucket's (Hp, Wp)) and the targets -- in PAIR order, target dict p belongs to pair p --
+    carry "masks" [T_p, h, w] at the padded batch's size, as CapturedTrainStep's do on the expanded batch.  A model built with freeze_detr=True
+    trains the mask head and bbox_attention alone.
+    Everything else is CapturedPairTrainStep's: the exact pair count, the host-checked tables, single process, buckets and their LRU, the eager first
+    step, the finite-loss guard and resolve_skipped().
+    Out of scope (ValueError before anything is uploaded or launched): ground truth prepared on the device -- step(target_masks=...) and targets
+    that carry "mask_size" instead of "masks"; and a model without a mask head (CapturedPairTrainStep is the step for it)."""
+
+    def __init__(self, model, criterion, optimizer, weight_dict, *, batch, captions, pairs, max_targets_per_image=16, pad_hw=64, pad_tokens=1,
+                 max_graphs=4, contrastive=None, device=None):
+        if not hasattr(model, "decode_mask_pairs"):
+            raise ValueError("CapturedMaskPairTrainStep takes a model with a mask head (DETRsegm); a detection model trains through CapturedPairTrainStep")
+        self.masks = "masks" in getattr(criterion, "losses", ())
+        self._init_pair_step(model, criterion, optimizer, weight_dict, batch, captions, pairs, max_targets_per_image, pad_hw, pad_tokens, max_graphs,
+                             contrastive, device)
+
+    def check_batch(self, samples, tokenized, pair_image, pair_caption, targets):
+        pi, pc = super().check_batch(samples, tokenized, pair_image, pair_caption, targets)
+        if any("mask_size" in t and "masks" not in t for t in targets or ()):
+            raise ValueError("CapturedMaskPairTrainStep: the targets carry \"mask_size\" instead of \"masks\" -- ground truth prepared on the device is "
+                             "out of scope for the shared-image step (CapturedTrainStep(target_masks=) on the expanded batch serves it)")
+        if self.masks and any("masks" not in t for t in targets or ()):
+            raise ValueError("CapturedMaskPairTrainStep: the criterion has mask losses, so every target dict (in pair order) carries \"masks\"")
+        return pi, pc
+
+    def _fwd_bwd_opt(self, ent):
+        kernels.SEED_DEV.add_(1000003)
+        mc = self.model.encode_mask_pairs(ent["samples"], ent["tok"], ent["pair_image"], ent["pair_caption"], check=False)      # (host-checked tables)
+        return self._train_tail(mc, self.model.decode_mask_pairs(mc), ent["targets"])
+
+    def step(self, samples, tokenized, pair_image, pair_caption, targets, positive_map, target_masks=None):
+        if target_masks is not None:
+            raise ValueError("CapturedMaskPairTrainStep: target_masks= (ground truth prepared on the device) is out of scope for the shared-image step")
+        return super().step(samples, tokenized, pair_image, pair_caption, targets, positive_map)
 
     __call__ = step
 

@@ -324,10 +324,13 @@ __device__ __forceinline__ int nearest_src(int dst, float scale, int in) {
 }
 // pairs (a task sweep's maps, rows == nullptr): map bq belongs to pair bq / Q, its image is pair_image[bq / Q] (device int32).  An entry outside
 // [0, n_images) is never used as an index: that pair's FPN term counts as zero and pair + 1 goes into *status with atomicMax (toist_sweep_assemble's rule)
-template <bool twice, bool pairs = false>        // twice: OH = 2 H and OW = 2 W (image sides that are multiples of 32: the shift form, no float index arithmetic)
+// gathered (with pairs; shared-image training's matched-rows backward): map i is map rows[i] of the P * Q maps of `n_pairs` pairs, its pair rows[i] / Q.
+// A pair outside [0, n_pairs) is never used as an index into the table either: a zero term, and *status gets pair + 1 (n_pairs + 1 for a negative one)
+template <bool twice, bool pairs = false, bool gathered = false>   // twice: OH = 2 H and OW = 2 W (image sides that are multiples of 32: the shift form, no float index arithmetic)
 __global__ __launch_bounds__(256) void upsample_add_kernel(const bf16_t* __restrict__ in, const bf16_t* __restrict__ fpn, const long long* __restrict__ rows,
                                                             int BQ, int Q, int H, int W, int OH, int OW, int C, bf16_t* __restrict__ out,
-                                                            const int32_t* __restrict__ pair_image, int n_images, int32_t* __restrict__ status) {
+                                                            const int32_t* __restrict__ pair_image, int n_images, int32_t* __restrict__ status,
+                                                            int n_pairs) {
     const int c8 = C >> 3;
     const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
     const long long total = (long long)BQ * OH * OW * c8;
@@ -340,7 +343,19 @@ __global__ __launch_bounds__(256) void upsample_add_kernel(const bf16_t* __restr
         const int ys = twice ? (Y >> 1) : nearest_src(Y, sy, H), xs = twice ? (X >> 1) : nearest_src(X, sx, W);
         float a[8], f[8];
         unpack8(*reinterpret_cast<const uint4*>(in + ((((size_t)bq * H + ys) * W + xs) * C) + cc * 8), a);
-        if constexpr (pairs) {
+        if constexpr (pairs && gathered) {
+            const long long map = rows[bq], pair = map < 0 ? -1 : map / Q;            // (C division truncates: -1 / Q would be pair 0)
+            const bool known = pair >= 0 && pair < (long long)n_pairs;
+            const int img = known ? pair_image[pair] : -1;
+            if ((unsigned)img < (unsigned)n_images) {
+                unpack8(*reinterpret_cast<const uint4*>(fpn + ((((size_t)img * OH + Y) * OW + X) * C) + cc * 8), f);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) f[j] = 0.f;
+                if (cc == 0 && X == 0 && Y == 0)
+                    atomicMax(status, pair < 0 ? n_pairs + 1 : pair >= 0x7fffffffLL ? 0x7fffffff : (int)pair + 1);
+            }
+        } else if constexpr (pairs) {
             const int pair = bq / Q, img = pair_image[pair];
             if ((unsigned)img < (unsigned)n_images) {
                 unpack8(*reinterpret_cast<const uint4*>(fpn + ((((size_t)img * OH + Y) * OW + X) * C) + cc * 8), f);
@@ -423,6 +438,58 @@ __global__ __launch_bounds__(256) void sum_segments_kernel(const bf16_t* __restr
             unpack8(reinterpret_cast<const uint4*>(in)[(long long)s * per8 + r], v);
 #pragma unroll
             for (int j = 0; j < 8; ++j) a[j] += v[j];
+        }
+        reinterpret_cast<uint4*>(out)[i] = pack8(a);
+    }
+}
+
+// out[b, i] = sum of the maps of every pair p with pair_image[p] == b, in ascending pair order and ascending map order inside a pair: one fp32
+// accumulator per element, one rounding -- no atomics, so the same bits every run whatever the table's order (shared-image training: the per-image
+// reduction of sum_queries / sum_segments when the maps belong to (image, caption) pairs).  Pair p's maps are [seg[p], seg[p + 1]) clamped to
+// [0, rows), or [p Q, (p + 1) Q) without seg.  A table entry outside [0, n_images) names no image: its maps are skipped, pair + 1 goes into *status.
+// One wave per block: n_images * per8 work items spread over every CU also for one or two images; four maps' loads are issued before their adds.
+__global__ __launch_bounds__(64) void sum_maps_by_image_kernel(const bf16_t* __restrict__ in, const int* __restrict__ seg, const int32_t* __restrict__ pair_image,
+                                                                int P, int Q, int n_images, int rows, long long per8, bf16_t* __restrict__ out,
+                                                                int32_t* __restrict__ status) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        int bad = 0;
+        for (int p = 0; p < P; ++p)
+            if ((unsigned)pair_image[p] >= (unsigned)n_images) bad = p + 1;
+        if (bad) atomicMax(status, bad);
+    }
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(in);
+    const long long total = (long long)n_images * per8;
+    for (long long i = (long long)blockIdx.x * 64 + threadIdx.x; i < total; i += (long long)gridDim.x * 64) {
+        const long long b = i / per8, r = i - b * per8;
+        float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int p = 0; p < P; ++p) {
+            if ((long long)pair_image[p] != b) continue;
+            long long s0 = seg != nullptr ? (long long)seg[p] : (long long)p * Q, s1 = seg != nullptr ? (long long)seg[p + 1] : (long long)(p + 1) * Q;
+            if (s0 < 0) s0 = 0;
+            if (s1 > rows) s1 = rows;
+            long long s = s0;
+            for (; s + 4 <= s1; s += 4) {
+                const uint4 u0 = src[s * per8 + r], u1 = src[(s + 1) * per8 + r], u2 = src[(s + 2) * per8 + r], u3 = src[(s + 3) * per8 + r];
+                float v[8];
+                unpack8(u0, v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[j] += v[j];
+                unpack8(u1, v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[j] += v[j];
+                unpack8(u2, v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[j] += v[j];
+                unpack8(u3, v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[j] += v[j];
+            }
+            for (; s < s1; ++s) {
+                float v[8];
+                unpack8(src[s * per8 + r], v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[j] += v[j];
+            }
         }
         reinterpret_cast<uint4*>(out)[i] = pack8(a);
     }
@@ -694,10 +761,10 @@ static int launch_resize_add(const char* what, const void* in, const void* fpn, 
     TOIST_REQUIRE(in && fpn && out && n > 0 && Q > 0 && H > 0 && W > 0 && OH >= H && OW >= W && (C % 8) == 0 && (rows || (n % Q) == 0), "%s: bad shape", what);
     if (OH == 2 * H && OW == 2 * W)
         hipLaunchKernelGGL(upsample_add_kernel<true>, dim3(grid_cap((long long)n * OH * OW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)in, (const bf16_t*)fpn, (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out, nullptr, 0, nullptr);
+                           (const bf16_t*)in, (const bf16_t*)fpn, (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out, nullptr, 0, nullptr, 0);
     else
         hipLaunchKernelGGL(upsample_add_kernel<false>, dim3(grid_cap((long long)n * OH * OW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)in, (const bf16_t*)fpn, (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out, nullptr, 0, nullptr);
+                           (const bf16_t*)in, (const bf16_t*)fpn, (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out, nullptr, 0, nullptr, 0);
     return check_launch(what);
 }
 extern "C" int toist_upsample_add(const void* in, const void* fpn, int BQ, int Q, int H, int W, int C, void* out, void* stream) {
@@ -717,11 +784,35 @@ extern "C" int toist_resize_add_pairs(const void* in, const void* fpn, const int
     const dim3 grid(grid_cap((long long)n * OH * OW * (C / 8), 8192));
     if (OH == 2 * H && OW == 2 * W)
         hipLaunchKernelGGL((upsample_add_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (const bf16_t*)fpn,
-                           (const long long*)nullptr, n, Q, H, W, OH, OW, C, (bf16_t*)out, pair_image, n_images, status);
+                           (const long long*)nullptr, n, Q, H, W, OH, OW, C, (bf16_t*)out, pair_image, n_images, status, 0);
     else
         hipLaunchKernelGGL((upsample_add_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (const bf16_t*)fpn,
-                           (const long long*)nullptr, n, Q, H, W, OH, OW, C, (bf16_t*)out, pair_image, n_images, status);
+                           (const long long*)nullptr, n, Q, H, W, OH, OW, C, (bf16_t*)out, pair_image, n_images, status, 0);
     return check_launch("toist_resize_add_pairs");
+}
+extern "C" int toist_resize_add_rows_pairs(const void* in, const void* fpn, const int64_t* rows, const int32_t* pair_image, int n_images, int P, int n, int Q,
+                                           int H, int W, int OH, int OW, int C, void* out, int32_t* status, void* stream) {
+    TOIST_REQUIRE(in && fpn && rows && out && pair_image && status && n_images > 0 && P > 0 && n > 0 && Q > 0 && H > 0 && W > 0 && OH >= H && OW >= W &&
+                      C > 0 && (C % 8) == 0, "toist_resize_add_rows_pairs: bad shape");
+    const dim3 grid(grid_cap((long long)n * OH * OW * (C / 8), 8192));
+    if (OH == 2 * H && OW == 2 * W)
+        hipLaunchKernelGGL((upsample_add_kernel<true, true, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (const bf16_t*)fpn,
+                           (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out, pair_image, n_images, status, P);
+    else
+        hipLaunchKernelGGL((upsample_add_kernel<false, true, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (const bf16_t*)fpn,
+                           (const long long*)rows, n, Q, H, W, OH, OW, C, (bf16_t*)out, pair_image, n_images, status, P);
+    return check_launch("toist_resize_add_rows_pairs");
+}
+extern "C" int toist_sum_maps_by_image(const void* in, const int32_t* seg, const int32_t* pair_image, int P, int Q, int n_images, int rows, int64_t per,
+                                       void* out, int32_t* status, void* stream) {
+    TOIST_REQUIRE(in && pair_image && out && status && P > 0 && Q > 0 && n_images > 0 && rows > 0 && per > 0 && (per % 8) == 0,
+                  "toist_sum_maps_by_image: bad shape");
+    const long long items = (long long)n_images * (per / 8);
+    long long blocks = (items + 63) / 64;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(sum_maps_by_image_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)in, seg, pair_image, P, Q, n_images,
+                       rows, (long long)(per / 8), (bf16_t*)out, status);
+    return check_launch("toist_sum_maps_by_image");
 }
 static int launch_resize_add_bwd(const char* what, const void* dout, int BQ, int H, int W, int OH, int OW, int C, void* din, void* stream) {
     TOIST_REQUIRE(dout && din && BQ > 0 && H > 0 && W > 0 && OH >= H && OW >= W && (C % 8) == 0, "%s: bad shape", what);

@@ -5,8 +5,8 @@ from types import SimpleNamespace
 
 import torch
 
-from .captured import (CapturedDistillStep, CapturedEvalStep, CapturedMaskSweepStep, CapturedPairTrainStep, CapturedSweepStep, CapturedTrainStep,  # noqa: F401
-                       size_pairs)
+from .captured import (CapturedDistillStep, CapturedEvalStep, CapturedMaskPairTrainStep, CapturedMaskSweepStep, CapturedPairTrainStep,  # noqa: F401
+                       CapturedSweepStep, CapturedTrainStep, size_pairs)
 from .transformer import TokenizedText
 
 
@@ -45,6 +45,16 @@ def finite_or_exit(loss_value, loss_dict=None, criterion=None):
     sys.exit(1)
 
 
+def _box_masks(boxes, height, width):
+    """One rectangle per normalised cxcywh box, at least one pixel -> bool [t, height, width]."""
+    m = torch.zeros(len(boxes), height, width, dtype=torch.bool)
+    for j in range(len(boxes)):
+        x0, y0 = int((boxes[j, 0] - boxes[j, 2] / 2) * width), int((boxes[j, 1] - boxes[j, 3] / 2) * height)
+        x1, y1 = int((boxes[j, 0] + boxes[j, 2] / 2) * width), int((boxes[j, 1] + boxes[j, 3] / 2) * height)
+        m[j, max(y0, 0):max(y1, 1), max(x0, 0):max(x1, 1)] = True
+    return m
+
+
 def synthetic_batch(batch, height=640, width=640, tokens=16, seed=1000, device="cpu", max_targets=10, with_masks=False):
     """Images ~ N(0,1) (already normalised), all-False padding mask; captions = <s> + ids + </s>;
     T_i ~ U{0..max_targets} boxes with cx,cy~U(.2,.8), w,h~U(.05,.4); positive_map rows = 1/(tokens-2)
@@ -66,12 +76,7 @@ def synthetic_batch(batch, height=640, width=640, tokens=16, seed=1000, device="
         tgt = {"boxes": boxes, "labels": torch.ones(t, dtype=torch.int64), "positive_map": pm,
                "token_spans": [[(1, tokens - 2)] for _ in range(t)]}
         if with_masks:
-            m = torch.zeros(t, height, width, dtype=torch.bool)
-            for j in range(t):
-                x0, y0 = int((boxes[j, 0] - boxes[j, 2] / 2) * width), int((boxes[j, 1] - boxes[j, 3] / 2) * height)
-                x1, y1 = int((boxes[j, 0] + boxes[j, 2] / 2) * width), int((boxes[j, 1] + boxes[j, 3] / 2) * height)
-                m[j, max(y0, 0):max(y1, 1), max(x0, 0):max(x1, 1)] = True
-            tgt["masks"] = m
+            tgt["masks"] = _box_masks(boxes, height, width)
         targets.append(tgt)
         rows.append(pm)
     positive_map = torch.cat(rows) if rows else torch.zeros(0, 256)
@@ -86,12 +91,14 @@ def synthetic_batch(batch, height=640, width=640, tokens=16, seed=1000, device="
 
 
 # ---- shared-image training: B images and T captions as P (image, caption) pairs (MDETR.encode_pairs) ----------------------------
-def synthetic_pair_batch(images, captions, pairs, height=640, width=640, tokens=16, seed=1000, max_targets=10, device="cpu"):
+def synthetic_pair_batch(images, captions, pairs, height=640, width=640, tokens=16, seed=1000, max_targets=10, device="cpu", with_masks=False):
     """What a loader that serves several captions of one augmented image delivers: `images` images, `captions` tokenized captions and P pairs.
     pairs: a list of (image, caption) in batch order, or the number P -- then pair p is (image p * images // P, caption p % captions): every image
     and caption is used when P >= max(images, captions), each image by a run of consecutive pairs.
     -> (samples [B], tokenized [T], pair_image int32 [P], pair_caption int32 [P] (host), targets [P], positive_map [sum of the targets, 256]): the
-    targets and the positive map are in PAIR order -- target dict p belongs to pair p, as batch row p of the expanded batch would carry it."""
+    targets and the positive map are in PAIR order -- target dict p belongs to pair p, as batch row p of the expanded batch would carry it.
+    with_masks: every target dict also carries "masks" bool [t, height, width], one rectangle per box (synthetic_batch's); the boxes are the same
+    with and without."""
     from . import sweep
     images, captions = int(images), int(captions)
     if not isinstance(pairs, (list, tuple)):
@@ -101,6 +108,9 @@ def synthetic_pair_batch(images, captions, pairs, height=640, width=640, tokens=
     samples = synthetic_batch(images, height, width, tokens=tokens, seed=seed, device=device, max_targets=0)[0]
     tokenized = synthetic_batch(captions, 1, 1, tokens=tokens, seed=seed + 1, device=device, max_targets=0)[1]
     _, _, targets, positive_map = synthetic_batch(P, 1, 1, tokens=tokens, seed=seed + 2, device=device, max_targets=max_targets)
+    if with_masks:
+        for t in targets:
+            t["masks"] = _box_masks(t["boxes"].cpu(), int(height), int(width)).to(device)
     return samples, tokenized, pair_image, pair_caption, targets, positive_map
 
 
@@ -121,6 +131,15 @@ def pair_train_losses(model, criterion, batch):
     samples, tokenized, pair_image, pair_caption, targets, positive_map = batch
     mc = model.encode_pairs(samples, tokenized, pair_image, pair_caption)
     outputs = model.decode(mc)
+    return criterion(mc, outputs, targets, positive_map, None), outputs
+
+
+def mask_pair_train_losses(model, criterion, batch):
+    """pair_train_losses for a model with a mask head (DETRsegm): encode_mask_pairs -> decode_mask_pairs -> criterion (with or without "masks"; the
+    targets, in pair order, carry "masks" when it has them).  -> (loss dict, outputs with "pred_masks" [P, Q, Hm, Wm])."""
+    samples, tokenized, pair_image, pair_caption, targets, positive_map = batch
+    mc = model.encode_mask_pairs(samples, tokenized, pair_image, pair_caption)
+    outputs = model.decode_mask_pairs(mc)
     return criterion(mc, outputs, targets, positive_map, None), outputs
 
 

@@ -1301,6 +1301,56 @@ def resize_add_pairs(inp, fpn, pair_image, n, Q, H, W, OH, OW, C, out):
                                                  _p(out, BF16), _p(status, torch.int32), _stream()), "toist_resize_add_pairs")
 
 
+def resize_add_rows_pairs(inp, fpn, rows, pair_image, n, Q, H, W, OH, OW, C, out):
+    """resize_add on a gathered subset of the maps of P pairs (include/toist_hip.h: toist_resize_add_rows_pairs): map i is map rows[i] (int64 [n] ON THE
+    DEVICE) of the P * Q maps, out [n, OH, OW, C] = fpn[pair_image[rows[i] // Q]] + nearest-resized inp [n, H, W, C]; n need not be a multiple of Q."""
+    what = "resize_add_rows_pairs"
+    n, Q, H, W, OH, OW, C = (int(v) for v in (n, Q, H, W, OH, OW, C))
+    if n <= 0 or Q <= 0 or H <= 0 or W <= 0 or OH < H or OW < W or C <= 0 or C % 8:
+        raise ValueError(f"{what}: n = {n} maps, Q = {Q} per pair, {H} x {W} -> {OH} x {OW}, C = {C}: positive extents, a target no smaller than the source, C % 8 == 0")
+    if inp is None or fpn is None or rows is None or out is None or pair_image is None:
+        raise ValueError(f"{what}: inp, fpn, rows, pair_image and out are required")
+    per = OH * OW * C
+    if inp.numel() != n * H * W * C or out.numel() != n * per or fpn.numel() == 0 or fpn.numel() % per:
+        raise ValueError(f"{what}: inp [{n}, {H}, {W}, {C}], fpn [n_images, {OH}, {OW}, {C}] and out [{n}, {OH}, {OW}, {C}] "
+                         f"(got {tuple(inp.shape)}, {tuple(fpn.shape)}, {tuple(out.shape)})")
+    if rows.dtype != torch.int64 or rows.dim() != 1 or rows.numel() != n:
+        raise ValueError(f"{what}: rows is an int64 vector of {n} entries (got {rows.dtype} {tuple(rows.shape)})")
+    if not (inp.is_contiguous() and fpn.is_contiguous() and out.is_contiguous() and rows.is_contiguous()):
+        raise ValueError(f"{what}: every tensor must be contiguous")
+    P = int(pair_image.numel())
+    status = _pair_table(what, pair_image, P)
+    if P <= 0:
+        raise ValueError(f"{what}: an empty pair table")
+    _lib.check(_lib.lib().toist_resize_add_rows_pairs(_p(inp, BF16), _p(fpn, BF16), _p(rows, torch.int64), _p(pair_image, torch.int32), fpn.numel() // per, P,
+                                                      n, Q, H, W, OH, OW, C, _p(out, BF16), _p(status, torch.int32), _stream()), "toist_resize_add_rows_pairs")
+
+
+def sum_maps_by_image(inp, seg, pair_image, Q, n_images, per, out):
+    """out [n_images, per] = per image the sum of the maps of its pairs (include/toist_hip.h: toist_sum_maps_by_image): inp bf16 [rows, per]; pair p's
+    maps are rows [seg[p], seg[p + 1]) (seg int32 [P + 1] ON THE DEVICE) or [p Q, (p + 1) Q) with seg = None; pair_image int32 [P] ON THE DEVICE.
+    fp32 sums in ascending pair and map order, rounded once: the same bits every run."""
+    what = "sum_maps_by_image"
+    Q, n_images, per = int(Q), int(n_images), int(per)
+    if inp is None or out is None or pair_image is None:
+        raise ValueError(f"{what}: inp, pair_image and out are required")
+    if Q <= 0 or n_images <= 0 or per <= 0 or per % 8:
+        raise ValueError(f"{what}: Q = {Q}, n_images = {n_images}, per = {per}: positive extents and per % 8 == 0")
+    if inp.numel() == 0 or inp.numel() % per or out.numel() != n_images * per:
+        raise ValueError(f"{what}: inp [rows, {per}] and out [{n_images}, {per}] (got {tuple(inp.shape)}, {tuple(out.shape)})")
+    if not (inp.is_contiguous() and out.is_contiguous()):
+        raise ValueError(f"{what}: every tensor must be contiguous")
+    P = int(pair_image.numel())
+    if P <= 0:
+        raise ValueError(f"{what}: an empty pair table")
+    status = _pair_table(what, pair_image, P)
+    if seg is not None and (seg.dtype != torch.int32 or seg.dim() != 1 or seg.numel() != P + 1 or not seg.is_contiguous() or not seg.is_cuda):
+        raise ValueError(f"{what}: seg is a contiguous int32 vector of {P + 1} entries on the device (got {seg.dtype} {tuple(seg.shape)})")
+    _lib.check(_lib.lib().toist_sum_maps_by_image(_p(inp, BF16), _p(seg, torch.int32), _p(pair_image, torch.int32), P, Q, n_images, inp.numel() // per, per,
+                                                  _p(out, BF16), _p(status, torch.int32), _stream()), "toist_sum_maps_by_image")
+    return out
+
+
 def sweep_gather(src, pair_image, out=None):
     """out[p] = src[pair_image[p]] in one launch (include/toist_hip.h: toist_sweep_gather): src [n_images, ...] of any dtype, row size and alignment,
     pair_image int32 [P] ON THE DEVICE -> [P, ...]; `out` = such a tensor to write into.  Every output byte is written; a refused pair's row is zeros

@@ -371,7 +371,7 @@ class MDETR(nn.Module):
         return state, text
 
     # ---- shared-image training: P (image, caption) pairs at the cost of B image passes and T text passes, differentiable ------------
-    def encode_pairs(self, samples, captions, pair_image, pair_caption, out=None, check=None):
+    def encode_pairs(self, samples, captions, pair_image, pair_caption, out=None, check=None, levels=(4,)):
         """encode() for a batch whose rows are PAIRS: the backbone runs on the B images, the text branch on the T captions (forked onto the text side
         stream and joined as in encode), one toist_sweep_assemble launch builds the P cross-modal sequences and the encoder runs over them -> the
         memory cache of an ordinary batch of P rows: decode() and SetCriterion take it unchanged, with P target dicts and a positive map in pair order.
@@ -381,11 +381,15 @@ class MDETR(nn.Module):
         pair_image / pair_caption: lists or host tensors (checked here, before anything is launched), or int32 DEVICE vectors (checked by the launch:
         its status word is read right away outside a capture -- check=False leaves kernels.sweep_check() to the caller).  out: (tokens, pos, key_pad)
         buffers for the assembled sequences.  The cache carries "tokenized" as a sweep.SweepTokenized over the pair rows.
+        levels: the backbone levels kept as the cache's per-IMAGE features, the last one C5 (a mask head reads (1, 2, 3, 4): DETRsegm.encode_mask_pairs).
         Not supported: backward cuts / data-parallel training (RuntimeError), mask-head models (DETRsegm raises NotImplementedError)."""
         from . import sweep
         from .transformer import EncodedText
         if not isinstance(samples, NestedTensor):
             samples = NestedTensor.from_tensor_list(samples)
+        levels = tuple(levels)
+        if not levels or levels[-1] != 4:
+            raise ValueError(f"encode_pairs: levels = {levels} must end with 4 (C5 feeds input_proj)")
         if getattr(self, "split_backward", False):
             raise RuntimeError("encode_pairs does not support backward cuts (split_backward / parallel.enable_backward_cuts, the data-parallel step): "
                                "the shared image pass is single-process; run encode() on the expanded batch there")
@@ -401,7 +405,7 @@ class MDETR(nn.Module):
             T = captions["input_ids"].shape[0]
         pi, pc, pc_host = sweep.device_tables(pair_image, pair_caption, B, T, dev)             # host tables: ValueError before anything is launched
         text, side = self._text_branch(captions, dev)                                         # beside the backbone, as in encode()
-        feats = self._backbone_stage(samples)
+        feats = self._backbone_stage(samples, levels, premasked=(len(levels) - 1,))
         self._join(side)
         image = sweep.SweepImages(*self._image_tokens(feats[-1], samples.mask), feats)
         read_status = (pc_host is None if check is None else bool(check)) and not torch.cuda.is_current_stream_capturing()

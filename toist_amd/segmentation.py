@@ -159,8 +159,13 @@ class DETRsegm(nn.Module):
         self._cache = {}
 
     # ---- the mask program ---------------------------------------------------------------------------------
-    def _masks(self, hs_last, memory, src_proj, c4, c3, c2, feat_mask, B, Q, h, w):
-        """hs_last [B*Q,d], memory / src_proj [B*h*w, d], c4/c3/c2 NHWC bf16 -> pred mask logits [B,Q,8h,8w] f32."""
+    def _masks(self, hs_last, memory, src_proj, c4, c3, c2, feat_mask, B, Q, h, w, pair_image=None):
+        """hs_last [B*Q,d], memory / src_proj [B*h*w, d], c4/c3/c2 NHWC bf16 -> pred mask logits [B,Q,8h,8w] f32.
+        pair_image (int32 [P] on the device; shared-image training): the maps are those of P (image, caption) pairs -- hs_last [P*Q, d], memory
+        [P*h*w, d] (each pair's image rows) and the logits [P,Q,8h,8w] are per PAIR, src_proj / c4 / c3 / c2 / feat_mask per IMAGE (B of them).  Every
+        per-map tensor has P where it had B; a map finds its image's terms through the table (sweep_gather, resize_add_pairs, mask_stage_fwd_pairs,
+        and in the backward resize_add_rows_pairs); every sum over an image's maps is sum_maps_by_image, so src_proj and the FPN levels receive ONE
+        gradient per image.  Without a table the launches are the ones they always were."""
         H = self.bbox_attention.num_heads
         d = self.bbox_attention.hidden_dim
         dh = d // H
@@ -172,8 +177,12 @@ class DETRsegm(nn.Module):
         transforms = {n: _krsc_bf16 for n, p in named.items() if p.dim() == 4}
         key_pad = feat_mask.flatten(1).to(torch.uint8).contiguous()
         dev = hs_last.device
+        pairs = pair_image is not None
+        N = pair_image.numel() if pairs else B          # the rows of every per-map / per-sample tensor: pairs, or images
+        if pairs:
+            key_pad = k.sweep_gather(key_pad, pair_image)                                             # [P, HW] bytes
 
-        BQ = B * Q
+        BQ = N * Q
         sel = {"rows": None, "scatter": None, "seg": None}     # set by out_bwd when only the matched maps carry a gradient
 
         def pick(t):
@@ -182,7 +191,9 @@ class DETRsegm(nn.Module):
 
         def image_sum(g, per, out):
             """out[b] = sum of the maps of image b: all Q of them, or the matched ones (packed image by image)."""
-            if sel["rows"] is None:
+            if pairs:                     # (matched maps: packed pair by pair, sel["seg"] has one segment per pair)
+                k.sum_maps_by_image(g, sel["seg"] if sel["rows"] is not None else None, pair_image, Q, B, per, out)
+            elif sel["rows"] is None:
                 k.sum_queries(g, B, Q, per, out)
             else:
                 k.sum_segments(g, sel["seg"], B, g.shape[0], per, out)
@@ -193,11 +204,11 @@ class DETRsegm(nn.Module):
             # -- attention map (segmentation.py:262-273)
             q = engine.linear_chain(tape, hs, [(A("q_linear.weight"), A("q_linear.bias"), k.ACT_NONE, False)])
             kk = engine.linear_chain(tape, mem, [(A("k_linear.weight"), A("k_linear.bias"), k.ACT_NONE, False)])
-            scores = torch.empty(B, Q, H, ld, dtype=BF16, device=dev)
+            scores = torch.empty(N, Q, H, ld, dtype=BF16, device=dev)
             k.gemm(Q, HW, dh, k.A_ROWK, k.operand(q.data, d, bs_outer=Q * d, bs_inner=dh), k.B_ROWK, k.operand(kk.data, d, bs_outer=HW * d, bs_inner=dh),
-                   scores, H * ld, batch=B * H, batch_inner=H, cs_outer=Q * H * ld, cs_inner=ld, alpha=scale, tile=64)
-            prob = torch.empty(B * Q, h, w, H, dtype=BF16, device=dev)
-            k.attnmap_softmax_fwd(scores, key_pad, B, Q, H, HW, ld, prob)
+                   scores, H * ld, batch=N * H, batch_inner=H, cs_outer=Q * H * ld, cs_inner=ld, alpha=scale, tile=64)
+            prob = torch.empty(N * Q, h, w, H, dtype=BF16, device=dev)
+            k.attnmap_softmax_fwd(scores, key_pad, N, Q, H, HW, ld, prob)
             del scores
             pv = engine.Var(prob)
 
@@ -209,16 +220,16 @@ class DETRsegm(nn.Module):
                     gd = torch.zeros(BQ + 1, h, w, H, dtype=BF16, device=dev)
                     gd.index_copy_(0, sel["scatter"], g)
                     g = gd[:BQ]
-                ds = torch.empty(B, Q, H, ld, dtype=BF16, device=dev)
-                k.attnmap_softmax_bwd(prob, g, B * Q, H, HW, ld, ds)
-                dq = torch.empty(B * Q, d, dtype=BF16, device=dev)
-                dk = torch.empty(B * HW, d, dtype=BF16, device=dev)
+                ds = torch.empty(N, Q, H, ld, dtype=BF16, device=dev)
+                k.attnmap_softmax_bwd(prob, g, N * Q, H, HW, ld, ds)
+                dq = torch.empty(N * Q, d, dtype=BF16, device=dev)
+                dk = torch.empty(N * HW, d, dtype=BF16, device=dev)
                 # dq[b,q,n,:] = scale * sum_p ds[b,q,n,p] kk[b,p,n,:] ; dk[b,p,n,:] = scale * sum_q ds[b,q,n,p] q[b,q,n,:]
                 k.gemm(Q, dh, HW, k.A_ROWK, k.operand(ds, H * ld, bs_outer=Q * H * ld, bs_inner=ld), k.B_KROW,
-                       k.operand(kk.data, d, bs_outer=HW * d, bs_inner=dh), dq, d, batch=B * H, batch_inner=H, cs_outer=Q * d, cs_inner=dh,
+                       k.operand(kk.data, d, bs_outer=HW * d, bs_inner=dh), dq, d, batch=N * H, batch_inner=H, cs_outer=Q * d, cs_inner=dh,
                        alpha=scale, tile=64)
                 k.gemm(HW, dh, Q, k.A_KROW, k.operand(ds, H * ld, bs_outer=Q * H * ld, bs_inner=ld), k.B_KROW,
-                       k.operand(q.data, d, bs_outer=Q * d, bs_inner=dh), dk, d, batch=B * H, batch_inner=H, cs_outer=HW * d, cs_inner=dh,
+                       k.operand(q.data, d, bs_outer=Q * d, bs_inner=dh), dk, d, batch=N * H, batch_inner=H, cs_outer=HW * d, cs_inner=dh,
                        alpha=scale, tile=64)
                 q.grad, kk.grad = dq, dk
 
@@ -229,10 +240,10 @@ class DETRsegm(nn.Module):
             src4 = engine.Var(src.data.view(B, h, w, d), needs_grad=src.needs_grad)
             w1_img = W1.w[..., :d].contiguous()
             y_img = ops.conv2d(src4.data, w1_img, pad=1, shift=b1.f32)            # [B,h,w,264]
-            a1, pre1 = _conv_gn_relu(tape, pv, W1, b1, M("gn1.weight"), M("gn1.bias"), (B * Q, h, w, H), extra_res=y_img.view(B * HW, -1),
-                                     res_bcast=(Q * HW, HW), w_slice=(d, d + H), pick=pick)
-
             C1 = w1_img.shape[0]
+            y_res = k.sweep_gather(y_img.view(B, HW * C1), pair_image) if pairs else y_img                # the image term of every pair's maps
+            a1, pre1 = _conv_gn_relu(tape, pv, W1, b1, M("gn1.weight"), M("gn1.bias"), (N * Q, h, w, H), extra_res=y_res.view(N * HW, -1),
+                                     res_bcast=(Q * HW, HW), w_slice=(d, d + H), pick=pick)
 
             def img_bwd():
                 g = pre1.take_grad()
@@ -251,7 +262,7 @@ class DETRsegm(nn.Module):
             # the block's backward (recorded inside _conv_gn_relu) must run BEFORE img_bwd: insert img_bwd just before it
             tape.steps.insert(len(tape.steps) - 1, img_bwd)
 
-            a2, _ = _conv_gn_relu(tape, a1, M("lay2.weight"), M("lay2.bias"), M("gn2.weight"), M("gn2.bias"), (B * Q, h, w, C1), pick=pick)
+            a2, _ = _conv_gn_relu(tape, a1, M("lay2.weight"), M("lay2.bias"), M("gn2.weight"), M("gn2.bias"), (N * Q, h, w, C1), pick=pick)
 
             def adapter(feat, i):
                 """The FPN term of stage i (adapter{i}, a 1x1 convolution of the backbone feature): [B*2H*2W, Cx] bf16."""
@@ -286,8 +297,11 @@ class DETRsegm(nn.Module):
                 Cx = x.data.shape[-1]
                 OH, OW = feat.data.shape[1], feat.data.shape[2]
                 f, wa = adapter(feat, i)                                             # [B*OH*OW, Cx]
-                up = torch.empty(B * Q, OH, OW, Cx, dtype=BF16, device=dev)
-                k.resize_add(x.data, f, None, B * Q, Q, H_, W_, OH, OW, Cx, up)
+                up = torch.empty(N * Q, OH, OW, Cx, dtype=BF16, device=dev)
+                if pairs:
+                    k.resize_add_pairs(x.data, f, pair_image, N * Q, Q, H_, W_, OH, OW, Cx, up)
+                else:
+                    k.resize_add(x.data, f, None, B * Q, Q, H_, W_, OH, OW, Cx, up)
                 uv = engine.Var(up)
 
                 def up_bwd():
@@ -297,7 +311,7 @@ class DETRsegm(nn.Module):
 
                 tape.record(up_bwd)
                 return _conv_gn_relu(tape, uv, M(f"lay{i + 2}.weight"), M(f"lay{i + 2}.bias"), M(f"gn{i + 2}.weight"), M(f"gn{i + 2}.bias"),
-                                     (B * Q, OH, OW, Cx), pick=pick)[0]
+                                     (N * Q, OH, OW, Cx), pick=pick)[0]
 
             def matched_rows_of(g):
                 """g = gradient of the mask logits [B,Q,8h,8w] exactly as autograd delivered it (Var.raw_grad) -> the rows the backward has to run on
@@ -352,13 +366,14 @@ class DETRsegm(nn.Module):
                 st4 = torch.empty(BQ, 8, 2, dtype=torch.float32, device=dev)
                 # the convolution is linear: lay(adapter(fpn) + up2(x)) = lay(adapter(fpn)) [one small convolution per IMAGE, bias included] + lay_nobias(up2(x))
                 fa_conv = ops.conv2d(fa.view(B, H4, W4_, C3), W4.w, pad=1, shift=b4.f32)
-                k.mask_stage_fwd(a3.data, None, None, None, fa_conv, W4.w, None, pre4, st4, BQ, Q, H4, W4_, C3, C4, C4, False, True)
+                stage = (lambda *a: k.mask_stage_fwd_pairs(*a, pair_image)) if pairs else k.mask_stage_fwd      # the two stages with an image term
+                stage(a3.data, None, None, None, fa_conv, W4.w, None, pre4, st4, BQ, Q, H4, W4_, C3, C4, C4, False, True)
                 fb, wa3 = adapter(f2, 3)
                 pre5 = torch.empty(BQ, H5, W5_, C5, dtype=BF16, device=dev)
                 st5 = torch.empty(BQ, 8, 2, dtype=torch.float32, device=dev)
                 fb_conv = ops.conv2d(fb.view(B, H5, W5_, C4), W5.w, pad=1, shift=b5.f32, tile=64)   # 8 images: the tiled implicit GEMM (the direct few-channel kernel is sized for 800 maps: 71 us here)
-                k.mask_stage_fwd(pre4, st4, g4w.f32, g4b.f32, fb_conv, W5.w, None, pre5, st5, BQ, Q, H5, W5_, C4, C5, C5, True, True)
-                masks = torch.empty(B, Q, H5, W5_, dtype=torch.float32, device=dev)
+                stage(pre4, st4, g4w.f32, g4b.f32, fb_conv, W5.w, None, pre5, st5, BQ, Q, H5, W5_, C4, C5, C5, True, True)
+                masks = torch.empty(N, Q, H5, W5_, dtype=torch.float32, device=dev)
                 k.mask_stage_fwd(pre5, st5, g5w.f32, g5b.f32, None, Wo.w, bo.f32, masks, None, BQ, Q, H5, W5_, C5, 1, 1, True, False)
                 mv = engine.Var(masks)
                 mv.raw_grad = True
@@ -373,7 +388,11 @@ class DETRsegm(nn.Module):
                 def up_rows(x_rows, f, H_, W_, C):
                     n = x_rows.shape[0]
                     up = torch.empty(n, 2 * H_, 2 * W_, C, dtype=BF16, device=dev)
-                    if sel["rows"] is None:
+                    if pairs and sel["rows"] is None:
+                        k.resize_add_pairs(x_rows, f, pair_image, n, Q, H_, W_, 2 * H_, 2 * W_, C, up)
+                    elif pairs:
+                        k.resize_add_rows_pairs(x_rows, f, sel["rows"], pair_image, n, Q, H_, W_, 2 * H_, 2 * W_, C, up)
+                    elif sel["rows"] is None:
                         k.upsample_add(x_rows, f, n, Q, H_, W_, C, up)
                     else:
                         k.upsample_add_rows(x_rows, f, sel["rows"], n, Q, H_, W_, C, up)
@@ -429,7 +448,7 @@ class DETRsegm(nn.Module):
             bo8 = torch.zeros(8, dtype=torch.float32, device=dev)
             bo8[:1] = bo.f32
             o8 = ops.conv2d(a5.data, wo8, pad=1, shift=bo8)                         # [BQ,Hm,Wm,8] bf16
-            masks = o8[..., 0].float().view(B, Q, Hm, Wm).contiguous()
+            masks = o8[..., 0].float().view(N, Q, Hm, Wm).contiguous()
             mv = engine.Var(masks)
             mv.raw_grad = True
 
@@ -678,6 +697,34 @@ class DETRsegm(nn.Module):
         raise NotImplementedError("shared-image training with a mask head: the mask program and the mask losses index an image's FPN terms and ground-truth "
                                   "masks by batch row, so a batch of (image, caption) pairs needs a pair table inside them.  Train a detection model "
                                   "through MDETR.encode_pairs, or run encode() on the expanded batch")
+
+    # ---- shared-image training with the mask head: its own entry points beside the refused encode_pairs (as encode_mask_sweep beside encode_sweep) ----
+    def encode_mask_pairs(self, samples, captions, pair_image, pair_caption, out=None, check=None):
+        """MDETR.encode_pairs with the backbone levels (1, 2, 3, 4): B image passes and T text passes give the memory cache of P (image, caption) pairs,
+        differentiable; its `_native` carries the four feature levels, feat_mask and src_proj per IMAGE and the device tables pair_image /
+        pair_caption.  Arguments, table checks and refusals (backward cuts, torch.distributed through them, CPU tensors) are encode_pairs'."""
+        return self.detr.encode_pairs(samples, captions, pair_image, pair_caption, out=out, check=check, levels=(1, 2, 3, 4))
+
+    def decode_mask_pairs(self, memory_cache):
+        """decode for encode_mask_pairs' cache -> MDETR.decode's outputs of the P pairs + "pred_masks" [P, Q, Hm, Wm] f32 with grad: the mask program over
+        pairs (_masks with the device pair table) -- all P * Q maps live, as B * Q are in forward(); the backward gives src_proj and every FPN level ONE
+        gradient per image, so the backbone's backward runs once per image.  pred_masks carries `toist_matched_rows` as forward()'s does: mask_losses /
+        mask_losses_static take the outputs with targets in PAIR order."""
+        nat = memory_cache.get("_native") or {}
+        if "pair_image" not in nat or len(nat.get("features", ())) != 4:
+            raise ValueError("decode_mask_pairs takes the memory cache of encode_mask_pairs (pair tables and four feature levels)")
+        out = self.detr.decode(memory_cache)
+        pi = nat["pair_image"]
+        P = pi.numel()
+        c2, c3, c4, c5 = nat["features"]
+        B, h, w, _ = c5.shape
+        HW = h * w
+        stack = out["_stacked"]["hs"]                                   # [L, P*Q, d] bf16
+        Q = stack.shape[1] // P
+        d = stack.shape[-1]
+        mem = nat["memory"].view(P, nat["S"], d)[:, :HW].reshape(P * HW, d)
+        out["pred_masks"] = self._masks(stack[-1], mem, nat["src_proj"].reshape(B * HW, d), c4, c3, c2, nat["feat_mask"], B, Q, h, w, pair_image=pi)
+        return out
 
 
 # ------------------------------------------------------------------------------------------ mask losses

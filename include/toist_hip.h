@@ -249,6 +249,17 @@ TOIST_API int toist_embed_fwd(const int64_t* ids, const int64_t* pos_ids, const 
                     int n, int D, void* out, void* stream);
 TOIST_API int toist_embed_bwd(const void* g, const int64_t* ids, const int64_t* pos_ids, int n, int D, int64_t pad_id, float* dword,
                     float* dpos, float* dtype0, void* stream); /* rows whose id == pad_id get no gradient (padding_idx) */
+/* Row-sparse gradient slots.  A slot of numel fp32 elements comes with `touched`, one byte per `chunk` elements (slot-relative,
+ * ceil(numel / chunk) bytes); invariant: every element outside a chunk whose byte is set is +0.
+ *   toist_embed_bwd_sparse  toist_embed_bwd that also keeps the invariant: the wave that owns a table row (first token with that id, id != pad_id)
+ *                           stores 1 into the byte of every chunk the row overlaps, id*D / chunk .. ((id+1)*D - 1) / chunk.  touched_word /
+ *                           touched_pos: the bytes of dword / dpos, either may be NULL (that gradient is then written as by toist_embed_bwd).
+ *   toist_sparse_clear      one workgroup per chunk of up to two slots (numel1 == 0: one slot): a chunk whose byte is set is zeroed and its
+ *                           byte cleared; the others cost a byte read.  Afterwards both slots are +0 throughout and every byte is clear. */
+TOIST_API int toist_embed_bwd_sparse(const void* g, const int64_t* ids, const int64_t* pos_ids, int n, int D, int64_t pad_id, float* dword,
+                    float* dpos, float* dtype0, uint8_t* touched_word, uint8_t* touched_pos, int chunk, void* stream);
+TOIST_API int toist_sparse_clear(float* g0, uint8_t* touched0, int64_t numel0, float* g1, uint8_t* touched1, int64_t numel1, int chunk,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Set-criterion losses for all decoder layers at once.  Replaces SetCriterion.loss_labels / loss_boxes
@@ -797,6 +808,22 @@ TOIST_API int toist_opt_adamw_ema(const toist_opt_tensor* table, const int64_t* 
 TOIST_API int toist_opt_adamw_ema_blocks(const toist_opt_tensor* table, const int64_t* grads, const int32_t* chunks, int n_chunks,
                                const toist_opt_group* groups, const toist_opt_state* state, float beta1, float beta2, float eps,
                                float ema_decay, int max_blocks, void* stream);
+/* The same two launches for tables that hold row-sparse gradients (toist_embed_bwd_sparse).  touched, hot: device tables parallel to grads, one
+ * device address per tensor; chunk c of tensor i is chunk c of its toist_opt_chunk_elems() cut.
+ *   touched[i]  0 = a dense gradient; else the gradient's `touched` bytes (owned by whoever writes the gradient): a clear byte means the chunk
+ *               of the gradient is +0 throughout
+ *   hot[i]      0 = tensor i always takes the dense path; else bytes owned by the optimizer: a clear byte means m and v of the chunk are +0
+ *               throughout.  The update sets a chunk's byte whenever its gradient is dense or touched, and never clears one.
+ * sqnorm stores +0 for an untouched chunk without loading it (what the loads would have summed to).  adamw_ema takes the COLD path on a chunk
+ * that is neither touched nor hot: it loads p and ema only, runs the same arithmetic on zeros for g, m, v, stores p, ema and w, and stores m, v
+ * (setting the hot byte) only where a result is not the bit pattern +0 -- a NaN clip coefficient or a non-finite lr poisons them as the dense
+ * path does.  Every byte written equals what toist_opt_sqnorm / toist_opt_adamw_ema_blocks write.  touched = NULL (sqnorm) or touched = hot =
+ * NULL (adamw_ema): exactly those entry points.  A skipped step (state.skipped) changes no hot byte either. */
+TOIST_API int toist_opt_sqnorm_sparse(const toist_opt_tensor* table, const int64_t* grads, const int64_t* touched, const int32_t* chunks,
+                               int n_chunks, float* partial, void* stream);
+TOIST_API int toist_opt_adamw_ema_sparse(const toist_opt_tensor* table, const int64_t* grads, const int64_t* touched, const int64_t* hot,
+                               const int32_t* chunks, int n_chunks, const toist_opt_group* groups, const toist_opt_state* state,
+                               float beta1, float beta2, float eps, float ema_decay, int max_blocks, void* stream);
 
 /* ---- evaluation masks (replaces PostProcessSegm's dense resizes, models/postprocessors.py:73-109, and what
  * datasets/coco_eval.py:307-332 asks of pycocotools: mask_util.encode, and maskUtils.iou / area inside COCOeval).

@@ -422,13 +422,15 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const long long* __restr
 // row of the word / position table owns it and adds the gradients of every token that reads it, in token order
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const bf16_t* __restrict__ g, const long long* __restrict__ ids,
                                                          const long long* __restrict__ pos_ids, int n, int D, long long pad_id,
-                                                         float* __restrict__ dword, float* __restrict__ dpos) {
+                                                         float* __restrict__ dword, float* __restrict__ dpos, uint8_t* __restrict__ tword,
+                                                         uint8_t* __restrict__ tpos, int chunk) {
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= n) return;
     for (int which = 0; which < 2; ++which) {
         const long long* key = which ? pos_ids : ids;
         float* table = which ? dpos : dword;
+        uint8_t* touched = which ? tpos : tword;
         if (table == nullptr) continue;
         const long long id = key[t];
         // nn.Embedding(padding_idx=pad_id) never accumulates a gradient into the padding row
@@ -436,6 +438,10 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const bf16_t* __restrict
         bool dup = false;
         for (int u = lane; u < t; u += 64) dup |= (key[u] == id);
         if (__any(dup)) continue;                       // an earlier token owns this row
+        // row-sparse slot (toist_embed_bwd_sparse): the owner flags every chunk of the table gradient its row overlaps; several owners may
+        // store the same byte, all of them the value 1
+        if (touched != nullptr && lane == 0)
+            for (long long c = id * (long long)D / chunk; c <= ((id + 1) * (long long)D - 1) / chunk; ++c) touched[c] = 1;
         float* row = table + id * (long long)D;
         for (int c0 = 0; c0 < D; c0 += 64) {
             const int c = c0 + lane;
@@ -469,6 +475,28 @@ __global__ __launch_bounds__(256) void embed_type_bwd_kernel(const bf16_t* __res
         for (int r = 0; r < 8; ++r) s += red[r][cx];
         dtype0[c] += s;
     }
+}
+
+// Row-sparse gradient slots (engine.ParamSet): touched[c] != 0 <=> chunk c of the slot (chunk elements, slot-relative) may hold a value other than
+// +0.  One workgroup per chunk: a flagged chunk is zeroed and its flag cleared, the others cost one byte read.  Two slots per launch.
+__global__ __launch_bounds__(256) void sparse_clear_kernel(float* __restrict__ g0, uint8_t* __restrict__ t0, long long n0, int chunks0,
+                                                            float* __restrict__ g1, uint8_t* __restrict__ t1, long long n1, int chunk) {
+    const bool second = (int)blockIdx.x >= chunks0;
+    const int c = second ? (int)blockIdx.x - chunks0 : (int)blockIdx.x;
+    uint8_t* flag = (second ? t1 : t0) + c;
+    const bool set = *flag != 0;
+    __syncthreads();                        // thread 0 clears the flag below: every wave has read it first
+    if (!set) return;
+    const long long numel = second ? n1 : n0;
+    const long long beg = (long long)c * chunk;
+    long long end = beg + chunk;
+    if (end > numel) end = numel;
+    float* p = (second ? g1 : g0) + beg;
+    const int n = (int)(end - beg);
+    const int n4 = (((size_t)p & 15) == 0) ? (n >> 2) : 0;
+    for (int i = threadIdx.x; i < n4; i += 256) reinterpret_cast<float4*>(p)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) p[i] = 0.f;
+    if (threadIdx.x == 0) *flag = 0;
 }
 
 static inline int grid_for(long long n, int cap = 2048) {
@@ -568,13 +596,29 @@ extern "C" int toist_embed_fwd(const int64_t* ids, const int64_t* pos_ids, const
     return check_launch("toist_embed_fwd");
 }
 
-extern "C" int toist_embed_bwd(const void* g, const int64_t* ids, const int64_t* pos_ids, int n, int D, int64_t pad_id, float* dword,
-                               float* dpos, float* dtype0, void* stream) {
-    TOIST_REQUIRE(n > 0 && D > 0, "toist_embed_bwd: bad shape");
+extern "C" int toist_embed_bwd_sparse(const void* g, const int64_t* ids, const int64_t* pos_ids, int n, int D, int64_t pad_id, float* dword,
+                                      float* dpos, float* dtype0, uint8_t* touched_word, uint8_t* touched_pos, int chunk, void* stream) {
+    TOIST_REQUIRE(n > 0 && D > 0 && chunk > 0, "toist_embed_bwd: bad shape");
     if (dword != nullptr || dpos != nullptr)
         hipLaunchKernelGGL(embed_bwd_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, (const long long*)ids,
-                           (const long long*)pos_ids, n, D, (long long)pad_id, dword, dpos);
+                           (const long long*)pos_ids, n, D, (long long)pad_id, dword, dpos, touched_word, touched_pos, chunk);
     if (dtype0 != nullptr)
         hipLaunchKernelGGL(embed_type_bwd_kernel, dim3((D + 31) / 32), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, n, D, dtype0);
     return check_launch("toist_embed_bwd");
+}
+
+extern "C" int toist_embed_bwd(const void* g, const int64_t* ids, const int64_t* pos_ids, int n, int D, int64_t pad_id, float* dword,
+                               float* dpos, float* dtype0, void* stream) {
+    return toist_embed_bwd_sparse(g, ids, pos_ids, n, D, pad_id, dword, dpos, dtype0, nullptr, nullptr, 1, stream);
+}
+
+extern "C" int toist_sparse_clear(float* g0, uint8_t* touched0, int64_t numel0, float* g1, uint8_t* touched1, int64_t numel1, int chunk,
+                                  void* stream) {
+    TOIST_REQUIRE(chunk > 0 && numel0 >= 0 && numel1 >= 0 && (numel0 == 0 || (g0 && touched0)) && (numel1 == 0 || (g1 && touched1)),
+                  "toist_sparse_clear: bad args");
+    const long long c0 = (numel0 + chunk - 1) / chunk, c1 = (numel1 + chunk - 1) / chunk;
+    TOIST_REQUIRE(c0 + c1 > 0 && c0 + c1 < (1ll << 31), "toist_sparse_clear: bad size");
+    hipLaunchKernelGGL(sparse_clear_kernel, dim3((unsigned)(c0 + c1)), dim3(256), 0, (hipStream_t)stream, g0, touched0, (long long)numel0, (int)c0,
+                       g1, touched1, (long long)numel1, chunk);
+    return check_launch("toist_sparse_clear");
 }

@@ -196,6 +196,49 @@ def copy_of(t):
     return ent if ent is not None and ent.master() is t and ent.ptr == t.data_ptr() else None
 
 
+# ---- row-sparse gradient slots ------------------------------------------------------------------------------------
+# A gradient that only a row scatter writes (the embedding tables: a batch reads a few hundred of 50 265 rows) comes with `touched`, one byte per
+# chunk of kernels.opt_chunk_elems() elements of the tensor.  Invariant: every element outside a chunk whose byte is set is +0.  The writer sets
+# bytes (kernels.embed_bwd_sparse), ParamSet._clear zeroes only flagged chunks, and the optimizer tail skips what is neither touched nor holds a
+# non-zero moment (toist_amd/optim.py).  The bytes only ever over-approximate: whatever else may write such a gradient calls mark_all_touched.
+# The bytes are training state like the gradient they describe, and live as long as it does: this registry, the view and the layout memo hold them.
+SPARSE_TAIL = knob("TOIST_SPARSE_TAIL", True)   # False: no row-sparse slots, and the embedding tables get their bf16 compute copy again (A/B)
+TOUCHED = {}          # gradient data_ptr -> (weakref to the gradient tensor, its touched bytes)
+_OPT_CHUNK = None
+
+
+def opt_chunk():
+    global _OPT_CHUNK
+    if _OPT_CHUNK is None:
+        _OPT_CHUNK = k.opt_chunk_elems()
+    return _OPT_CHUNK
+
+
+def register_touched(g, touched):
+    for ptr in [ptr for ptr, ent in TOUCHED.items() if ent[0]() is None]:
+        del TOUCHED[ptr]
+    TOUCHED[g.data_ptr()] = (weakref.ref(g), touched)
+
+
+def touched_of(g):
+    """The touched bytes of exactly this gradient tensor object, or None (like copy_of: an address match alone is not enough)."""
+    ent = TOUCHED.get(g.data_ptr()) if g is not None and TOUCHED else None
+    return ent[1] if ent is not None and ent[0]() is g else None
+
+
+def touched_in(flat):
+    """the touched bytes of every live row-sparse gradient that lies inside the flat buffer `flat`"""
+    lo, hi = flat.data_ptr(), flat.data_ptr() + flat.numel() * flat.element_size()
+    return [ent[1] for ptr, ent in TOUCHED.items() if lo <= ptr < hi and ent[0]() is not None]
+
+
+def mark_all_touched(g):
+    """`g` is about to be written (or has been) by something that does not keep its touched bytes: from now on it counts as dense."""
+    t = touched_of(g)
+    if t is not None:
+        t.fill_(1)
+
+
 def _cast_bf16(m):
     return m.detach().to(BF16)
 
@@ -251,7 +294,7 @@ class ParamView:
     record, so a second weight-gradient launch on an already stored range accumulates (whatever view object it came through), and
     rows no launch reached are zeroed at the end of the backward pass (unwritten_rows)."""
 
-    __slots__ = ("w", "g", "f32", "fresh", "parent", "_lo", "_hi", "_ranges")
+    __slots__ = ("w", "g", "f32", "fresh", "parent", "_lo", "_hi", "_ranges", "touched")
 
     def __init__(self, w_bf16, grad_f32, f32=None, fresh=False, parent=None, lo=None, hi=None):
         self.w = w_bf16    # bf16 tensor used by the kernels (None for fp32-only params)
@@ -261,6 +304,13 @@ class ParamView:
         self.parent = parent
         self._lo, self._hi = lo, hi   # row range inside the root (None: all of it)
         self._ranges = []          # root only: row ranges [a, b) covered by weight-gradient launches of the current backward; (None, None) = everything
+        self.touched = None        # root only: the touched bytes of a row-sparse gradient slot (see TOUCHED above), else None
+
+    def mark_all_touched(self):
+        """a writer that does not keep the touched bytes is about to write this gradient: flag every chunk"""
+        t = self._root().touched
+        if t is not None:
+            t.fill_(1)
 
     def _root(self):
         v = self
@@ -343,15 +393,22 @@ class ParamSet:
     `named` is an ordered {name: tensor(fp32 master)}; weights (dim >= 2) get a bf16 copy, vectors
     are used in fp32 directly.  grads() returns gradients in the same order (None for frozen)."""
 
-    def __init__(self, named, trainable, need_grads, bf16_cache=None, transforms=None, store_once=None):
-        """store_once(name, tensor) -> True marks a parameter whose gradient is produced by exactly one weight-gradient GEMM per
+    def __init__(self, named, trainable, need_grads, bf16_cache=None, transforms=None, store_once=None, row_sparse=None):
+        """row_sparse: names of 2-D tables whose only gradient writer is a row scatter that keeps touched bytes (kernels.embed_bwd_sparse) and
+        that the program reads in fp32 only.  They get NO bf16 compute copy (the tail would rewrite 2 B/parameter nobody reads), and their
+        gradient slots sit between the zeroed head and the store-once tail: zeroed in full when the buffer is allocated, and from then on
+        (REUSE_GRAD_BUFFERS) only in the chunks a backward pass flagged -- one kernels.sparse_clear launch instead of a fill.  Ignored with
+        SPARSE_TAIL off.
+        store_once(name, tensor) -> True marks a parameter whose gradient is produced by exactly one weight-gradient GEMM per
         backward (every nn.Linear / nn.Conv2d weight of the hot path): its slot lives in the tail of the flat buffer, is NOT zeroed
         -- the GEMM overwrites it (Tape.linear_wgrad / conv_wgrad, accumulate=False) -- which removes 0.74 GB of zero-fill writes and
         as many read-modify-write reads per step.  Everything else (biases, LayerNorm and embedding gradients: atomics, scatter-adds)
         sits in the zeroed head of the buffer.  A store-once slot no launch reached is zeroed by Tape.backward."""
         self.names = list(named.keys())
         self.views = {}
-        self.zero_elems = 0
+        self.zero_elems = self.fresh_off = 0
+        self.sparse = []            # the row-sparse views
+        fp32_only = frozenset(row_sparse or ()) if SPARSE_TAIL else frozenset()
         # The slicing of the flat gradient buffer into ~600 per-parameter views costs ~4 ms of host time per step; with
         # REUSE_GRAD_BUFFERS the layout is memoised in the program's cache and reused (buffer zeroed in place) as long as the
         # parameters are the same objects and no parameter's .grad still aliases the buffer (gradient accumulation gets a
@@ -360,37 +417,42 @@ class ParamSet:
         params = list(named.values())
         sig = (need_grads, len(params), tuple(trainable.get(n, False) for n in self.names), id(params[0]) if params else 0,
                params[0].data_ptr() if params else 0, id(params[-1]) if params else 0, params[-1].data_ptr() if params else 0,
-               STORE_ONCE and store_once is not None)
+               STORE_ONCE and store_once is not None, fp32_only)
         if REUSE_GRAD_BUFFERS and memo is not None and memo["sig"] == sig and need_grads and memo["flat"] is not None:
             lo, hi = memo["flat"].data_ptr(), memo["flat"].data_ptr() + memo["flat"].numel() * 4
             if not any(p.grad is not None and lo <= p.grad.data_ptr() < hi for p in params):
                 self.flat = memo["flat"]
-                self.zero_elems = memo["zero_elems"]
-                self._clear()
+                self.zero_elems, self.fresh_off, self.sparse = memo["zero_elems"], memo["fresh_off"], memo["sparse"]
+                self._clear(reused=True)
                 for n, t in named.items():
                     pv = memo["views"][n]
                     pv.written = False
-                    if t.dim() >= 2:
+                    if t.dim() >= 2 and n not in fp32_only:
                         pv.w = compute_copy(t, (transforms or {}).get(n) or _cast_bf16, bf16_cache, n)
                     self.views[n] = pv
                 return
         fresh_names = set()
         if need_grads and STORE_ONCE and store_once is not None:
             fresh_names = {n for n in self.names if trainable.get(n, False) and store_once(n, named[n])}
+        sparse_names = set()
+        if need_grads:
+            sparse_names = {n for n in self.names if n in fp32_only and trainable.get(n, False) and n not in fresh_names and named[n].dim() == 2
+                            and named[n].is_contiguous()}
         pad = lambda t: (t.numel() + 63) // 64 * 64
         total = 0
         if need_grads:
-            self.zero_elems = sum(pad(named[n]) for n in self.names if trainable.get(n, False) and n not in fresh_names)
-            total = self.zero_elems + sum(pad(named[n]) for n in fresh_names)
+            self.zero_elems = sum(pad(named[n]) for n in self.names if trainable.get(n, False) and n not in fresh_names and n not in sparse_names)
+            self.fresh_off = self.zero_elems + sum(pad(named[n]) for n in sparse_names)
+            total = self.fresh_off + sum(pad(named[n]) for n in fresh_names)
         dev = next(iter(named.values())).device if named else None
         self.flat = torch.empty(total, dtype=torch.float32, device=dev) if total else None
         self._clear()
-        off_zero, off_fresh = 0, self.zero_elems
+        off_zero, off_sparse, off_fresh = 0, self.zero_elems, self.fresh_off
         for n in self.names:
             t = named[n]
             g = None
             if need_grads and trainable.get(n, False):
-                off = off_fresh if n in fresh_names else off_zero
+                off = off_fresh if n in fresh_names else off_sparse if n in sparse_names else off_zero
                 g = self.flat[off:off + t.numel()].view(t.shape)
                 if t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last):
                     # channels_last conv weights (physically KRSC): the gradient keeps the parameter's layout
@@ -398,25 +460,44 @@ class ParamSet:
                     g = self.flat[off:off + t.numel()].view(O, R, S, I).permute(0, 3, 1, 2)
                 if n in fresh_names:
                     off_fresh += pad(t)
+                elif n in sparse_names:
+                    off_sparse += pad(t)
                 else:
                     off_zero += pad(t)
             wb = None
-            if t.dim() >= 2:
+            if t.dim() >= 2 and n not in fp32_only:
                 make = (transforms or {}).get(n) or _cast_bf16
                 wb = compute_copy(t, make, bf16_cache, n)
-            self.views[n] = ParamView(wb, g, t.detach(), fresh=n in fresh_names)
+            pv = self.views[n] = ParamView(wb, g, t.detach(), fresh=n in fresh_names)
+            if n in sparse_names:
+                # (the slot was zeroed in full just above: no byte is set)
+                pv.touched = torch.zeros((t.numel() + opt_chunk() - 1) // opt_chunk(), dtype=torch.uint8, device=dev)
+                register_touched(g, pv.touched)
+                self.sparse.append(pv)
         if REUSE_GRAD_BUFFERS and bf16_cache is not None and need_grads and (memo is None or memo["sig"] != sig):
-            bf16_cache["__layout__"] = {"sig": sig, "flat": self.flat, "views": dict(self.views), "zero_elems": self.zero_elems}
+            bf16_cache["__layout__"] = {"sig": sig, "flat": self.flat, "views": dict(self.views), "zero_elems": self.zero_elems,
+                                        "fresh_off": self.fresh_off, "sparse": self.sparse}
 
-    def _clear(self):
+    def _clear(self, reused=False):
         """zero the accumulating head of the flat buffer; the store-once tail is left as it is (POISON_FRESH: NaN, so that a slot
-        nothing wrote shows up in the tests)"""
+        nothing wrote shows up in the tests).  The row-sparse slots between the two: zeroed with the head when the buffer is new, else
+        (reused: they held the invariant of their touched bytes so far) only where a backward pass flagged a chunk."""
         if self.flat is None:
             return
-        if self.zero_elems:
-            self.flat[:self.zero_elems].zero_()
-        if POISON_FRESH and self.zero_elems < self.flat.numel():
-            self.flat[self.zero_elems:].fill_(float("nan"))
+        if reused and self.sparse:
+            if self.zero_elems:
+                self.flat[:self.zero_elems].zero_()
+            for i in range(0, len(self.sparse), 2):
+                k.sparse_clear([(v.g, v.touched) for v in self.sparse[i:i + 2]], opt_chunk())
+        elif self.fresh_off:
+            self.flat[:self.fresh_off].zero_()
+        if POISON_FRESH and self.fresh_off < self.flat.numel():
+            self.flat[self.fresh_off:].fill_(float("nan"))
+
+    def mark_all_touched(self):
+        """the gradients of this set leave through a route that does not keep the touched bytes (torch's AccumulateGrad and whatever hooks it)"""
+        for v in self.sparse:
+            v.mark_all_touched()
 
     def fresh_views(self):
         return [v for v in self.views.values() if v.fresh and v.g is not None]

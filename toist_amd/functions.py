@@ -55,9 +55,11 @@ class _TapeFn(torch.autograd.Function):
         need = tape_kw.pop('need_grads')  # grad mode is off inside Function.forward: decided by the caller
         transforms = tape_kw.pop('transforms')
         store_once = tape_kw.pop('store_once')
+        row_sparse = tape_kw.pop('row_sparse')
         named = dict(zip(names, params))
         trainable = {n: p.requires_grad for n, p in named.items()}
-        ps = engine.ParamSet(named, trainable, need_grads=need, bf16_cache=cache, transforms=transforms, store_once=store_once)
+        ps = engine.ParamSet(named, trainable, need_grads=need, bf16_cache=cache, transforms=transforms, store_once=store_once,
+                             row_sparse=row_sparse)
         tape = engine.Tape(**tape_kw)
         tape.fresh_views = ps.fresh_views() if need else []
         in_vars = [None if t is None else engine.Var(t, needs_grad=(need and t.requires_grad and t.is_floating_point()))
@@ -103,6 +105,7 @@ class _TapeFn(torch.autograd.Function):
         if ctx.via_autograd:
             # torch DistributedDataParallel (or any other per-parameter hook) is listening: hand the gradients to autograd
             par_grads = [g if (g is not None and p.requires_grad) else None for p, g in zip(ctx.params, ps.grads())]
+            ps.mark_all_touched()       # AccumulateGrad and its hooks (a bucketed all-reduce) write these gradients without keeping touched bytes
             if ctx.rejoin is not None:
                 ctx.rejoin.wait_stream(torch.cuda.current_stream())
             ctx.tape = ctx.ps = ctx.in_vars = ctx.out_vars = ctx.params = None
@@ -117,6 +120,7 @@ class _TapeFn(torch.autograd.Function):
             if p.grad is None:
                 p.grad = g
             else:
+                engine.mark_all_touched(p.grad)     # a row-sparse slot of an earlier backward: this sum does not keep its touched bytes
                 p.grad.add_(g)
                 ps.flat = None  # accumulated into an older buffer: GradSync.finish() reduces those gradients one by one
         if GRAD_SYNC is not None:
@@ -130,11 +134,12 @@ class _TapeFn(torch.autograd.Function):
         return (None, None, None, None, None, *in_grads, *([None] * n_par))
 
 
-def run_program(body, named_params, inputs, cache=None, training=False, drop_p=0.0, seed=0, transforms=None, group_wgrads=False, store_once=None):
-    """body(tape, ps, *input_vars) -> (list_of_output_vars, extra).  Returns (outputs_tuple)."""
+def run_program(body, named_params, inputs, cache=None, training=False, drop_p=0.0, seed=0, transforms=None, group_wgrads=False, store_once=None,
+                row_sparse=None):
+    """body(tape, ps, *input_vars) -> (list_of_output_vars, extra).  Returns (outputs_tuple).  row_sparse: see engine.ParamSet."""
     names = tuple(named_params.keys())
     params = tuple(named_params.values())
     need = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (*inputs, *params))
     tape_kw = dict(training=training, drop_p=drop_p, seed=seed, need_grads=need, transforms=transforms, rejoin=REJOIN, group_wgrads=group_wgrads,
-                   via_autograd=need and _via_autograd(), store_once=store_once)
+                   via_autograd=need and _via_autograd(), store_once=store_once, row_sparse=row_sparse)
     return _TapeFn.apply(body, names, cache, len(inputs), tape_kw, *inputs, *params)

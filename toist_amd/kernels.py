@@ -481,6 +481,31 @@ def embed_bwd(g, ids, pos_ids, pad_id, dword, dpos, dtype0):
                "toist_embed_bwd")
 
 
+def embed_bwd_sparse(g, ids, pos_ids, pad_id, dword, dpos, dtype0, touched_word, touched_pos, chunk):
+    """embed_bwd into row-sparse gradient slots: touched_word / touched_pos (uint8, one byte per `chunk` elements of dword / dpos, or None) receive 1
+    for every chunk a written row overlaps (include/toist_hip.h: toist_embed_bwd_sparse)"""
+    n, D = g.shape
+    for grad, t in ((dword, touched_word), (dpos, touched_pos)):
+        if t is not None and (grad is None or t.numel() * chunk < grad.numel()):
+            raise ValueError("embed_bwd_sparse: a touched array needs one byte per chunk of its gradient")
+    _lib.check(_lib.lib().toist_embed_bwd_sparse(_p(g, torch.bfloat16), _p(ids, torch.int64), _p(pos_ids, torch.int64), n, D, pad_id,
+                                                 _p(dword, torch.float32), _p(dpos, torch.float32), _p(dtype0, torch.float32),
+                                                 _p(touched_word, torch.uint8), _p(touched_pos, torch.uint8), chunk, _stream()),
+               "toist_embed_bwd_sparse")
+
+
+def sparse_clear(slots, chunk):
+    """slots: one or two (gradient, touched) pairs of row-sparse slots: zero every chunk whose byte is set and clear the byte, in one launch"""
+    if not 1 <= len(slots) <= 2:
+        raise ValueError("sparse_clear: one or two slots per launch")
+    for grad, t in slots:
+        if not grad.is_contiguous() or t.numel() * chunk < grad.numel():
+            raise ValueError("sparse_clear: a contiguous gradient and one byte per chunk of it")
+    (g0, t0), (g1, t1) = slots[0], (slots[1] if len(slots) > 1 else (None, None))
+    _lib.check(_lib.lib().toist_sparse_clear(_p(g0, torch.float32), _p(t0, torch.uint8), g0.numel(), _p(g1, torch.float32), _p(t1, torch.uint8),
+                                             0 if g1 is None else g1.numel(), chunk, _stream()), "toist_sparse_clear")
+
+
 def criterion_fwd(logits, boxes, tgt_boxes, pos_map, tgt_off, match_off, src_idx, tgt_idx, num_boxes, eos_coef, losses, status=None):
     L, B, Q, K = logits.shape
     _lib.check(_lib.lib().toist_criterion_fwd(_p(logits, torch.float32), _p(boxes, torch.float32), _p(tgt_boxes, torch.float32),
@@ -636,7 +661,12 @@ def opt_chunk_elems():
     return int(_lib.lib().toist_opt_chunk_elems())
 
 
-def opt_sqnorm(table, grads, chunks, n_chunks, partial):
+def opt_sqnorm(table, grads, chunks, n_chunks, partial, touched=None):
+    """touched: int64 device table parallel to grads (the addresses of the row-sparse gradients' touched bytes, 0 = dense), or None"""
+    if touched is not None:
+        _lib.check(_lib.lib().toist_opt_sqnorm_sparse(_p(table, torch.uint8), _p(grads, torch.int64), _p(touched, torch.int64), _p(chunks, torch.int32),
+                                                      n_chunks, _p(partial, torch.float32), _stream()), "toist_opt_sqnorm_sparse")
+        return
     _lib.check(_lib.lib().toist_opt_sqnorm(_p(table, torch.uint8), _p(grads, torch.int64), _p(chunks, torch.int32), n_chunks,
                                            _p(partial, torch.float32), _stream()), "toist_opt_sqnorm")
 
@@ -654,7 +684,13 @@ def opt_finish_norm_guarded(partial, n_chunks, max_norm, beta1, beta2, state, ve
                "toist_opt_finish_norm_guarded")
 
 
-def opt_adamw_ema(table, grads, chunks, n_chunks, groups, state, beta1, beta2, eps, ema_decay, max_blocks=0):
+def opt_adamw_ema(table, grads, chunks, n_chunks, groups, state, beta1, beta2, eps, ema_decay, max_blocks=0, touched=None, hot=None):
+    """touched, hot: int64 device tables parallel to grads (include/toist_hip.h: toist_opt_adamw_ema_sparse), both or neither"""
+    if touched is not None or hot is not None:
+        _lib.check(_lib.lib().toist_opt_adamw_ema_sparse(_p(table, torch.uint8), _p(grads, torch.int64), _p(touched, torch.int64), _p(hot, torch.int64),
+                                                         _p(chunks, torch.int32), n_chunks, _p(groups, torch.float32), _p(state, torch.uint8), beta1,
+                                                         beta2, eps, ema_decay, max_blocks, _stream()), "toist_opt_adamw_ema_sparse")
+        return
     _lib.check(_lib.lib().toist_opt_adamw_ema_blocks(_p(table, torch.uint8), _p(grads, torch.int64), _p(chunks, torch.int32), n_chunks,
                                                      _p(groups, torch.float32), _p(state, torch.uint8), beta1, beta2, eps, ema_decay, max_blocks, _stream()),
                "toist_opt_adamw_ema")

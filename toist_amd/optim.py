@@ -14,7 +14,7 @@ There is no CPU path: tensors must live on the GPU and the HIP library must be l
 import numpy as np
 import torch
 
-from . import _lib, engine
+from . import _lib, devcache, engine
 from . import kernels as k
 from .knobs import knob
 
@@ -167,11 +167,23 @@ class FusedClipAdamWEMA:
         # gradient-pointer table: two pinned host copies used alternately, each guarded by an event recorded behind its upload, so a host
         # that runs ahead of the GPU never rewrites a table whose asynchronous copy has not been consumed; the upload is skipped
         # altogether when no pointer changed (REUSE_GRAD_BUFFERS, hipGraph replay)
-        self._grads_host = [torch.zeros(n_t, dtype=torch.int64).pin_memory() for _ in range(2)]
+        # Row-sparse gradients (engine.TOUCHED: the embedding tables).  The addresses of their touched bytes travel behind the gradient addresses
+        # in the same table (rows n_t .. 2 n_t), under the same protocol.  `hot` is this optimizer's own state beside the moments: one byte per
+        # chunk of every parameter, set once m or v of the chunk may be non-zero; its address table never changes.
+        self._n_t = n_t
+        self._sparse = bool(engine.SPARSE_TAIL)
+        nch = [(p.numel() + self._chunk - 1) // self._chunk for p in params]
+        self._hot = torch.zeros(sum(nch), dtype=torch.uint8, device=self.device)
+        self._hot_off = np.concatenate([[0], np.cumsum(nch)]).astype(np.int64)
+        hot_rows = np.zeros(n_t, dtype=np.int64)
+        hot_rows[:len(params)] = self._hot.data_ptr() + self._hot_off[:-1]
+        self._hot_dev = torch.from_numpy(hot_rows).to(self.device)
+        self._touched_held = []          # the touched arrays the device table points at
+        self._grads_host = [torch.zeros(2 * n_t, dtype=torch.int64).pin_memory() for _ in range(2)]
         self._grads_event = [None, None]
         self._grads_turn = 0
         self._grads_last = None
-        self._grads_dev = torch.zeros(n_t, dtype=torch.int64, device=self.device)
+        self._grads_dev = torch.zeros(2 * n_t, dtype=torch.int64, device=self.device)
         self._table = None
         self._chunks = self._partial = self._ema_table = self._ema_chunks = self._ema_grads = None
         self._retired = []
@@ -310,14 +322,24 @@ class FusedClipAdamWEMA:
         if self._grads_event[turn] is not None and not capturing:
             self._grads_event[turn].synchronize()      # the copy that last read this host table has completed
         gh = self._grads_host[turn].numpy()
+        n_t, held = self._n_t, []
+        sparse = self._sparse and bool(engine.TOUCHED)
         for i, p in enumerate(self.params):
             g = p.grad
+            gh[n_t + i] = 0
             if g is None:
                 gh[i] = 0
                 continue
             if g.dtype != torch.float32 or g.shape != p.shape or g.stride() != p.stride():
                 raise TypeError("FusedClipAdamWEMA: every gradient must be fp32 with its parameter's shape and strides")
             gh[i] = g.data_ptr()
+            if sparse:
+                tb = engine.touched_of(g)
+                if tb is not None:
+                    gh[n_t + i] = tb.data_ptr()
+                    held.append(tb)
+        self._touched_held = held       # (state, like the moments and `hot`: owned here and by the gradient's ParamSet, rewritten every step)
+        devcache.keep(self._hot_dev)    # the constant address table a captured launch reads: the graph's owner keeps it (devcache)
         if self._grads_last is None or capturing or not np.array_equal(gh, self._grads_last):
             self._grads_dev.copy_(self._grads_host[turn], non_blocking=True)
             if not capturing:
@@ -329,11 +351,12 @@ class FusedClipAdamWEMA:
         if self._early_done and self._e_hi > self._e_lo:
             # partial[e_lo:e_hi] were written by norm_early() of this step (the text branch, joined before the tail)
             if self._e_lo:
-                k.opt_sqnorm(self._table, self._grads_dev, self._chunks, self._e_lo, self._partial)
+                k.opt_sqnorm(self._table, self._grads_dev, self._chunks, self._e_lo, self._partial, touched=self._touched_dev())
             if self._n_chunks > self._e_hi:
-                k.opt_sqnorm(self._table, self._grads_dev, self._chunks[self._e_hi:], self._n_chunks - self._e_hi, self._partial[self._e_hi:])
+                k.opt_sqnorm(self._table, self._grads_dev, self._chunks[self._e_hi:], self._n_chunks - self._e_hi, self._partial[self._e_hi:],
+                             touched=self._touched_dev())
         else:
-            k.opt_sqnorm(self._table, self._grads_dev, self._chunks, self._n_chunks, self._partial)
+            k.opt_sqnorm(self._table, self._grads_dev, self._chunks, self._n_chunks, self._partial, touched=self._touched_dev())
         self._early_done = False
         if self.skip_nonfinite:
             k.opt_finish_norm_guarded(self._partial, self._n_chunks, self.max_norm, self.betas[0], self.betas[1], self.state,
@@ -342,13 +365,31 @@ class FusedClipAdamWEMA:
             k.opt_finish_norm(self._partial, self._n_chunks, self.max_norm, self.betas[0], self.betas[1], self.state)
         if self._n_now:
             k.opt_adamw_ema(self._table, self._grads_dev, self._chunks, self._n_now, self._groups_dev, self.state, self.betas[0],
-                            self.betas[1], self.eps, self.ema_decay)
+                            self.betas[1], self.eps, self.ema_decay, touched=self._touched_dev(), hot=self._hot_dev if self._sparse else None)
         self._ema_pending = self.defer_ema
         # the masters changed behind torch's version counters: every compute copy of THESE parameters is stale except the ones just rewritten
         self._bump_epoch()
         if self._n_late:
             self._late_pending = True
             self._late_grads = [p.grad for p, l in zip(self.params, self._late) if l]     # the pointers in the device table must stay valid
+
+    def _touched_dev(self):
+        """the touched-address rows of the gradient table (None with the switch off: the launches are then the dense ones)"""
+        return self._grads_dev[self._n_t:] if self._sparse else None
+
+    def hot_chunks(self, i):
+        """the hot bytes of parameter i (a view: one byte per chunk)"""
+        return self._hot[int(self._hot_off[i]):int(self._hot_off[i + 1])]
+
+    def _recompute_hot(self):
+        """hot from the moments as they are: a chunk is hot iff any bit of its m or v is set (the chunks follow the physical element order)"""
+        for i, (m, v) in enumerate(zip(self.exp_avg, self.exp_avg_sq)):
+            n = m.numel()
+            nz = (m.as_strided((n,), (1,)).view(torch.int32) != 0) | (v.as_strided((n,), (1,)).view(torch.int32) != 0)
+            pad = (-n) % self._chunk
+            if pad:
+                nz = torch.cat([nz, nz.new_zeros(pad)])
+            self.hot_chunks(i).copy_(nz.view(-1, self._chunk).any(dim=1))
 
     def note_replayed_step(self):
         """Host-side bookkeeping of ONE replay of a hipGraph that holds this optimizer's step(): the replay rewrote the masters and the bf16 compute
@@ -389,7 +430,11 @@ class FusedClipAdamWEMA:
             g = self.params[i].grad
             if (0 if g is None else g.data_ptr()) != int(last[i]):
                 return                      # fresh gradient buffers: the table is uploaded in step(), which then sums everything
-        k.opt_sqnorm(self._table, self._grads_dev, self._chunks[self._e_lo:], self._e_hi - self._e_lo, self._partial[self._e_lo:])
+            tb = engine.touched_of(g) if self._sparse else None
+            if (0 if tb is None else tb.data_ptr()) != int(last[self._n_t + i]):
+                return                      # (a gradient that became row-sparse, or stopped being: the same)
+        k.opt_sqnorm(self._table, self._grads_dev, self._chunks[self._e_lo:], self._e_hi - self._e_lo, self._partial[self._e_lo:],
+                     touched=self._touched_dev())
         self._early_done = True
 
     @torch.no_grad()
@@ -401,7 +446,8 @@ class FusedClipAdamWEMA:
         if not self._n_late or not (self._late_pending or capturing) or (capturing and self._late_captured):
             return
         k.opt_adamw_ema(self._table, self._grads_dev, self._chunks[self._n_now:], self._n_late, self._groups_dev, self.state, self.betas[0],
-                        self.betas[1], self.eps, self.ema_decay, max_blocks=LATE_BLOCKS)
+                        self.betas[1], self.eps, self.ema_decay, max_blocks=LATE_BLOCKS, touched=self._touched_dev(),
+                        hot=self._hot_dev if self._sparse else None)
         for ent, p in self._late_copies:
             ent.epoch = engine.WEIGHT_EPOCH
         if not capturing:
@@ -463,6 +509,7 @@ class FusedClipAdamWEMA:
             self.exp_avg[i].copy_(st["exp_avg"].reshape(self.exp_avg[i].shape) if st["exp_avg"].shape != self.exp_avg[i].shape else st["exp_avg"])
             self.exp_avg_sq[i].copy_(st["exp_avg_sq"].reshape(self.exp_avg_sq[i].shape) if st["exp_avg_sq"].shape != self.exp_avg_sq[i].shape else st["exp_avg_sq"])
             steps.append(int(float(st["step"])))
+        self._recompute_hot()       # the loaded moments decide which chunks may take the cold path: a resumed run loses neither the saving nor the exactness
         if steps and min(steps) != max(steps):
             raise ValueError("FusedClipAdamWEMA.load_state_dict: parameters with different step counts (the fused tail keeps one counter)")
         raw = np.zeros(1, dtype=_STATE_DT)          # (skipped / skipped_total / veto_mask are not part of a checkpoint: zero)

@@ -10,7 +10,7 @@ so few large messages keep every link busy.
 import torch
 import torch.distributed as dist
 
-from . import functions
+from . import engine, functions
 
 
 class GradSync:
@@ -56,6 +56,7 @@ class GradSync:
         work = dist.all_reduce(flat, op=op, group=self.group, async_op=True)
         self.pending.append((work, flat, op))
         self.ranges.append((flat.data_ptr(), flat.data_ptr() + flat.numel() * flat.element_size()))
+        self.pending.extend((w, None, dist.ReduceOp.MAX) for w in _touched_works([flat], self.group))
 
     def _local_states(self, params):
         state = []
@@ -114,6 +115,20 @@ class GradSync:
         self.pending, self.ranges = [], []
 
 
+def _touched_works(tensors, group=None):
+    """Row-sparse gradient slots inside the buffers about to be reduced (engine.TOUCHED): afterwards a row is non-zero if ANY rank wrote it, so
+    the slots' touched bytes are reduced with MAX in the same segment (a few KB of uint8), before the tail reads them -> the pending works.
+    Where the backend cannot do that, every chunk is flagged: the tail then treats the gradient as dense."""
+    works = []
+    for t in tensors:
+        for tb in engine.touched_in(t):
+            try:
+                works.append(dist.all_reduce(tb, op=dist.ReduceOp.MAX, group=group, async_op=True))
+            except (RuntimeError, TypeError, ValueError):
+                tb.fill_(1)
+    return works
+
+
 def _mean_op(group=None):
     """RCCL averages in the collective; gloo (CPU tests, smoke runs) sums and the caller divides."""
     return dist.ReduceOp.AVG if dist.get_backend(group) == "nccl" else dist.ReduceOp.SUM
@@ -142,6 +157,7 @@ def all_reduce_mean_async(flats, group=None, bf16=False):
     op = _mean_op(group)
     wire = [f.to(torch.bfloat16) for f in flats] if bf16 else None
     works = [dist.all_reduce(t, op=op, group=group, async_op=True) for t in (wire if bf16 else flats)]
+    works += _touched_works(flats, group)
     return _MeanHandle(works, list(flats), op, dist.get_world_size(group), wire)
 
 

@@ -433,7 +433,11 @@ class Transformer(nn.Module):
                 g = emb.take_grad()
                 if g is None or wv.g is None:
                     return
-                k.embed_bwd(g, ids_flat, pos_ids.view(-1), cfg.pad_token_id, wv.g, pv.g, tv.g[0] if tv.g is not None else None)
+                if wv.touched is not None or pv.touched is not None:      # row-sparse slots (engine.ParamSet): the scatter flags the chunks it writes
+                    k.embed_bwd_sparse(g, ids_flat, pos_ids.view(-1), cfg.pad_token_id, wv.g, pv.g, tv.g[0] if tv.g is not None else None,
+                                       wv.touched, pv.touched, engine.opt_chunk())
+                else:
+                    k.embed_bwd(g, ids_flat, pos_ids.view(-1), cfg.pad_token_id, wv.g, pv.g, tv.g[0] if tv.g is not None else None)
 
             tape.record(emb_bwd)
             x = engine.layernorm(tape, emb, P("embeddings.LayerNorm.weight"), P("embeddings.LayerNorm.bias"), cfg.layer_norm_eps)
@@ -462,7 +466,9 @@ class Transformer(nn.Module):
 
         (out,) = functions.run_program(prog, named, [], cache=self._cache_text, training=self.training, drop_p=cfg.hidden_dropout_prob,
                                        seed=self._next_seed(), group_wgrads=True, transforms=transforms,
-                                       store_once=lambda n, t: t.dim() == 2 and "embeddings" not in n)
+                                       store_once=lambda n, t: t.dim() == 2 and "embeddings" not in n,
+                                       # read in fp32 by embed_fwd, written by embed_bwd alone: no bf16 copy, row-sparse gradient slots
+                                       row_sparse=("text_encoder.embeddings.word_embeddings.weight", "text_encoder.embeddings.position_embeddings.weight"))
         return out, key_pad
 
     # ---- encoder ----------------------------------------------------------------------------------
